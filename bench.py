@@ -19,10 +19,14 @@ carves ~512^3 voxels holding the same share of the object; the carve itself need
 (voxels are independent).  For N > 1 ``value`` is SURVEY 8d's ``t_device + collective``: K steps of
 carve + pack to 2 bits per label + RCCL all-gather, every GPU ending every step with the whole grid (packed: the
 form ``proc3d.vol2pcd`` reads), the collective of step k running beside the carve of step k + 1 and the last one
-waited for inside the timed region.  Beside it: ``value_carve_only`` (no collective), ``assembly`` (the same
+waited for inside the timed region.  Beside it (``--full``): ``value_carve_only`` (no collective), ``assembly`` (the same
 steps one after the other, with the unpack kernel, at 1 bit, as int8), the time of ``gather_to_host`` (the
 reference's ``get_values``, cl.py:229-232), and ``strong``: BASELINE's own metric -- ONE 512^3 x 72 grid split
 over the N ranks -- with and without the assembly.
+
+A plain run sets up, warms up, times the K steps and prints the line: ``value``, ``ms_per_step`` (one timed step), the
+roofline of those steps.  ``--dump-outputs DIR`` writes the labels the last timed step left (``dump_outputs``): the
+inputs are seeded, so two builds can be compared output for output.  Everything below runs with ``--full`` only.
 
 Beside the headline, in the same line (N = 1):
   stream   one launch per view as the reference does (cl.py:223-226), the formulation SURVEY 8d's
@@ -105,6 +109,10 @@ def valu_ceiling(form, nvv):
 GRIDS_512 = {1: (512, 512, 512), 2: (640, 640, 640), 4: (808, 800, 832), 8: (1024, 1024, 1024)}
 
 
+# Without --full: seconds of untimed steps in front of the warm-up, where --full runs its other legs -- the clock ramp
+# after the idle spell of the scene's set-up (profiles/r04_clock_ramp.txt) is over before the timed steps
+LEAD_IN_S = 0.1
+
 COLLECTIVE = False
 COMM_STUCK = False  # a thread of this process never came back from sc_comm_create (the ranks fell back together)
 BARRIER = None  # the library communicator's barrier once it exists (sc_comm_barrier), else torch.distributed's
@@ -172,7 +180,44 @@ def parse():
     ap.add_argument("--rccl-rehearsal", action="store_true",
                     help="one rank, but with an RCCL process group of one: barriers, the timing all-reduce and the "
                          "assembly collectives run as they do at N > 1 (reported under 'assembly')")
+    ap.add_argument("--full", action="store_true",
+                    help="also every leg beside the headline: the other schedules, scenes and averaging forms, e2e, cold "
+                         "starts, traffic passes, the per-kernel breakdown, the pipelined leg, the parity check against the "
+                         "oracle, the CPU baseline; at N > 1 the carve-only figure, the assembly variants, the strong leg and "
+                         "the one-engine comparison.  The options that size those legs act only with --full.  Without it a "
+                         "run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the labels the last one left (rank 0's engine) as .npy files "
+                         "under DIR (see dump_outputs)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: the whole volume up to this many voxels, a seeded sample of this many above
+DUMP_SEED = 1234
+
+
+def dump_outputs(dirpath, labels):
+    """--dump-outputs: the int32 labels (-1 / 0 / 1) the timed path's last step left in the engine's volume -- what
+    get_values() hands its caller -- as float32 / float64 .npy files under `dirpath`, 17 MB at most whatever the grid:
+      labels_sample.npy     float32: every voxel in C order up to DUMP_SAMPLE voxels, else DUMP_SAMPLE voxels at the
+                            flat indices default_rng(DUMP_SEED).integers(0, size, DUMP_SAMPLE), sorted (the same for
+                            the same grid in every run);
+      labels_histogram.npy  float64 [3]: the voxels holding -1, 0, 1;
+      labels_per_plane.npy  float64 [nx, 3]: the same per x-plane (every voxel counts).
+    Returns the names written."""
+    os.makedirs(dirpath, exist_ok=True)
+    flat = labels.reshape(-1)
+    if flat.size <= DUMP_SAMPLE:
+        sample = flat
+    else:
+        sample = flat[np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.size, DUMP_SAMPLE))]
+    planes = labels.reshape(labels.shape[0], -1)
+    per_plane = np.stack([np.count_nonzero(planes == v, axis=1) for v in (-1, 0, 1)], axis=1).astype(np.float64)
+    out = {"labels_sample": sample.astype(np.float32), "labels_histogram": per_plane.sum(axis=0),
+           "labels_per_plane": per_plane}
+    for name, arr in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
+    return sorted(out)
 
 
 def global_shape(n, gpus):
@@ -362,7 +407,7 @@ def traffic_passes(a):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(work, counter)
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-                   sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                   sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
                    "--cpu-seconds", "0", "--extra-steps", "0", "--e2e-reps", "0", "--skip-other-path", "--cold-reps", "0",
                    "--traffic-passes", "off", "--parity-check", "off", "--cold-process", "off", "--n", str(a.n), "--views", str(a.views), "--scene", a.scene,
                    "--scene-cache", a.scene_cache]
@@ -1253,7 +1298,7 @@ def main():
     live_traffic = None
     profiled = any(k in os.environ for k in ("ROCPROFILER_TOOL_LIBRARIES", "ROCP_TOOL_LIBRARIES", "ROCPROF_OUTPUT_PATH")) or \
         "rocprofiler" in os.environ.get("LD_PRELOAD", "")
-    if world == 1 and rank == 0 and a.path == "fused" and not a.rccl_rehearsal and \
+    if a.full and world == 1 and rank == 0 and a.path == "fused" and not a.rccl_rehearsal and \
             (a.traffic_passes == "on" or (a.traffic_passes == "auto" and not profiled)):
         sys.path.insert(0, ROOT)
         from plant3dvision_amd import scenes as _scenes
@@ -1261,7 +1306,7 @@ def main():
         live_traffic = traffic_passes(a)
     # a cold Voxels run measured where it happens: a fresh process, before this one touches the GPU
     cold_proc = None
-    if world == 1 and rank == 0 and a.path == "fused" and not a.rccl_rehearsal and not profiled and \
+    if a.full and world == 1 and rank == 0 and a.path == "fused" and not a.rccl_rehearsal and not profiled and \
             (a.cold_process == "on" or (a.cold_process == "auto" and a.cold_reps > 0)):
         from plant3dvision_amd import scenes as _scenes
         _g, _o, _v, _views = cached_scene(a, _scenes, global_shape(a.n, 1))
@@ -1398,10 +1443,12 @@ def main():
     # kernel of the batch ~6 % slower during the first ~15 ms of device activity after an idle spell (scene
     # building on the host) than in the sustained state; the headline's W warm-up + K timed steps follow these
     # legs' device work, so `value` is the sustained rate whatever K is.  (--skip-other-path: no such lead-in.)
+    # Without --full those legs are not run: untimed steps of the headline's own schedule, LEAD_IN_S of them, take
+    # their place in front of the warm-up.
     t_legs0 = time.perf_counter()
     res_other = per_view = None
     eng.set_option(nat.SC_OPT_VIEW_BRICK, 0)  # "stream" is the streaming kernel: every view reads the whole state
-    if not a.skip_other_path:
+    if a.full and not a.skip_other_path:
         osteps = max(4, a.steps // 4) if other == "stream" else a.steps
         run_steps(eng, nat, *call, 1, vpl[other])
         eng.synchronize()
@@ -1420,33 +1467,50 @@ def main():
                     "note": "one launch (+ its verdict kernel) per view, the reference's cadence cl.py:223-226, brick "
                             "verdicts and dead-brick skipping (SC_OPT_VIEW_BRICK 1, the default)"}
     eng.set_option(nat.SC_OPT_VIEW_BRICK, 0 if a.path == "stream" else 1)
+    if not a.full and not a.skip_other_path:
+        while time.perf_counter() - t_legs0 < LEAD_IN_S:
+            run_steps(eng, nat, *call, 8, vpl[a.path])
+            eng.synchronize()
     t_device_before = time.perf_counter() - t_legs0
 
-    # warmup (untimed), in the timing mode of the timed steps: the first batches with event pairs create
-    # their HIP events (tens of microseconds each), which is warm-up work, not a step's
-    eng.set_option(nat.SC_OPT_TIME_KERNELS, 2)
-    # set-up, not a step: the engine allocates its working buffers (survivor lists, brick tables, packed-mask
-    # arena: ~0.5 GB of hipMalloc) the first time a batch goes through; like the upload of the masks above this
-    # happens once per engine, whatever --warmup says
-    run_steps(eng, nat, *call, 1, vpl[a.path])
-    eng.synchronize()
-    run_steps(eng, nat, *call, a.warmup, vpl[a.path])
-    eng.synchronize()
-    dt, stats = timed(eng, nat, torch, dist, call, a.steps, vpl[a.path], world,
-                      time_kernels="span" if a.path == "fused" else 2)
-    # per-kernel breakdown: a separate short pass with events around every kernel
-    bsteps = max(2, min(a.steps, 5))
-    dtb, breakdown = timed(eng, nat, torch, dist, call, bsteps, vpl[a.path], world, time_kernels=1)
-    breakdown["ms_per_step_with_all_events"] = dtb / bsteps * 1e3
-    if a.path == "fused":
-        live, s0, s1n, ovf = eng.fused_counts()
-        breakdown["fused_counts"] = {"live_bricks": live, "alive_after_dense_stage": s0,
-                                     "alive_after_first_list_stage": s1n, "list_overflow": ovf}
+    def dump_last_step(engine):
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, engine.get_values())
+
+    # N > 1 (and the RCCL rehearsal), fused path: `value` is carve + assembly, timed further down; the carve-only steps
+    # here are the figure beside it (`value_carve_only`, the roofline's span) and run with --full only
+    assembled = collective and a.path == "fused"
+    dt = stats = None
+    if a.full or not assembled:
+        # warmup (untimed), in the timing mode of the timed steps: the first batches with event pairs create
+        # their HIP events (tens of microseconds each), which is warm-up work, not a step's
+        eng.set_option(nat.SC_OPT_TIME_KERNELS, 2)
+        # set-up, not a step: the engine allocates its working buffers (survivor lists, brick tables, packed-mask
+        # arena: ~0.5 GB of hipMalloc) the first time a batch goes through; like the upload of the masks above this
+        # happens once per engine, whatever --warmup says
+        run_steps(eng, nat, *call, 1, vpl[a.path])
+        eng.synchronize()
+        run_steps(eng, nat, *call, a.warmup, vpl[a.path])
+        eng.synchronize()
+        dt, stats = timed(eng, nat, torch, dist, call, a.steps, vpl[a.path], world,
+                          time_kernels="span" if a.path == "fused" else 2)
+        if not assembled:
+            dump_last_step(eng)
+    breakdown = None
+    if a.full:
+        # per-kernel breakdown: a separate short pass with events around every kernel
+        bsteps = max(2, min(a.steps, 5))
+        dtb, breakdown = timed(eng, nat, torch, dist, call, bsteps, vpl[a.path], world, time_kernels=1)
+        breakdown["ms_per_step_with_all_events"] = dtb / bsteps * 1e3
+        if a.path == "fused":
+            live, s0, s1n, ovf = eng.fused_counts()
+            breakdown["fused_counts"] = {"live_bricks": live, "alive_after_dense_stage": s0,
+                                         "alive_after_first_list_stage": s1n, "list_overflow": ovf}
     # Throughput with two scans in flight (N = 1): a second engine of the same grid, the two taking the steps in turn on
     # their own streams and label volumes -- a queue of scans, as a service would run them.  Reported BESIDE `value`
     # (which stays one engine, one batch at a time: the quantity every round has measured).
     pipelined = None
-    if world == 1 and not a.rccl_rehearsal and a.path == "fused" and a.pipelined_steps > 0:
+    if a.full and world == 1 and not a.rccl_rehearsal and a.path == "fused" and a.pipelined_steps > 0:
         try:  # (N = 1, no collective anywhere near: a failure here is reported, not fatal to the line)
             import hashlib
             eng2 = nat.Engine(gshape, origin, vs, nat.SC_MODE_CARVE, device=local_rank)
@@ -1485,7 +1549,7 @@ def main():
     twin = None
     twin_check = None
     dt_asm_one = None
-    if collective and a.path == "fused":
+    if assembled:
         # two engines take the steps in turn (ShardedBackprojection.twin: the double buffering of a pipeline of scans):
         # the pack of step k, on its engine's stream, is beside the carve of step k + 1 like the collective
         # (with the library's communicator only: staged through the hosts -- the gloo fallback -- a step is bound by the
@@ -1493,7 +1557,8 @@ def main():
         if a.twin_engine and sb.comm is not None:
             twin = sb.twin()
         dt_asm = assembled_steps(nat, torch, dist, sb, eng, call, a.steps, a.warmup, overlap=True, form="sparse", twin=twin)
-        if twin is not None:
+        dump_last_step(eng if twin is None else (eng, twin.engine)[(a.steps - 1) % 2])
+        if a.full and twin is not None:
             # (outside the timed regions) the twin's labels are the first engine's, which parity_check compares with the oracle
             import hashlib
             twin_check = hashlib.sha256(twin.get_local().tobytes()).hexdigest() == hashlib.sha256(sb.get_local().tobytes()).hexdigest()
@@ -1501,32 +1566,32 @@ def main():
             # (the twin is closed at the very end: behind an engine's destruction -- its hipFree / hipHostFree calls -- the
             # small device-to-host copy of the headers on the ENGINE's stream, the serial legs below, took 0.12 ms per step
             # where it takes none before: tools/dbg/sparse_steps.py VARIANTS=ACT, 0.183 -> 0.299 ms)
-    if collective and a.assembly_steps > 0:
+    if a.full and collective and a.assembly_steps > 0:
         asm = assembly(a, nat, torch, dist, sb, eng, call, a.assembly_steps, n_total, V)
         if world == 1:
             asm["rehearsal"] = "process group of one rank on one GPU: the collectives move nothing over xGMI"
     strong = None
-    if collective and a.strong_steps > 0 and a.path == "fused":
+    if a.full and collective and a.strong_steps > 0 and a.path == "fused":
         strong = strong_scaling(a, nat, torch, dist, scenes, ShardedBackprojection, rank, world, local_rank, a.strong_steps,
                                 comm_library=comm_library, all_ok=all_ok if comm_library else None)
     parity = None
-    if a.parity_check == "on" and a.path == "fused" and rank == 0:
+    if a.full and a.parity_check == "on" and a.path == "fused" and rank == 0:
         parity = parity_check(a, nat, eng, call, gshape, origin, vs, views, planes=None if world == 1 else sb.planes,
                               rank=rank, world=world)
         if twin_check is not None:  # the second engine of the assembled headline carved the same labels
             parity["twin_engine_labels_equal"] = bool(twin_check)
             parity["ok"] = bool(parity["ok"] and twin_check)
     e2e = None
-    if world == 1 and not a.rccl_rehearsal and a.e2e_reps > 0 and a.path == "fused":
+    if a.full and world == 1 and not a.rccl_rehearsal and a.e2e_reps > 0 and a.path == "fused":
         e2e = e2e_host(a, gshape, origin, vs, views, local_rank, a.e2e_reps)
     extras = avg = None
-    if world == 1 and a.extra_steps > 0 and a.path == "fused":
+    if a.full and world == 1 and a.extra_steps > 0 and a.path == "fused":
         extras = extra_scenes(a, nat, torch, eng, gshape, masks_dev, a.extra_steps)
         eng.dev_upload(masks_dev, stack)
         avg = average_forms(a, nat, torch, gshape, origin, vs, views, local_rank, max(2, a.extra_steps // 2))
 
     cold = None
-    if world == 1 and not a.rccl_rehearsal and a.cold_reps > 0 and a.path == "fused":
+    if a.full and world == 1 and not a.rccl_rehearsal and a.cold_reps > 0 and a.path == "fused":
         cold = cold_first_batch(a, nat, gshape, origin, vs, call, local_rank, a.cold_reps)
 
     # another assembly on request, once
@@ -1608,7 +1673,7 @@ def main():
         return ent.get("hbm_bytes_per_launch") if isinstance(ent, dict) else None
 
     if rank == 0:
-        value_carve = n_total * V * a.steps / dt / 1e6
+        value_carve = n_total * V * a.steps / dt / 1e6 if dt is not None else None
         dt_value = dt_asm if dt_asm is not None else dt
         value = n_total * V * a.steps / dt_value / 1e6
         out = {
@@ -1629,21 +1694,29 @@ def main():
                                       else "one GPU, the whole grid: no collective",
                        "path": a.path, "views_per_launch": V if a.path == "fused" else 1,
                        "arithmetic": "float32 projection (no contraction, correctly rounded divide) into int32 labels"},
-            "roofline": (roof(a.path, stats, live_traffic["hbm_bytes_per_launch"], live_traffic["source"])
-                         if live_traffic is not None and world == 1 and list(sb.slab_shape) == [a.n, a.n, a.n]
-                         else roof(a.path, stats, traffic_for(a.path))),
-            "kernels": {k: stats[k] for k in ("carve", "step") if stats[k]["launches"]},
-            "kernels_breakdown_pass": breakdown,
         }
+        if stats is not None:  # (the carve-only steps; at N > 1 they run with --full only)
+            out["roofline"] = (roof(a.path, stats, live_traffic["hbm_bytes_per_launch"], live_traffic["source"])
+                               if live_traffic is not None and world == 1 and list(sb.slab_shape) == [a.n, a.n, a.n]
+                               else roof(a.path, stats, traffic_for(a.path)))
+            out["kernels"] = {k: stats[k] for k in ("carve", "step") if stats[k]["launches"]}
+        if breakdown is not None:
+            out["kernels_breakdown_pass"] = breakdown
         if live_traffic is not None:
             out["roofline"]["traffic_read_bytes"] = live_traffic["read_bytes"]
             out["roofline"]["traffic_write_bytes"] = live_traffic["write_bytes"]
             out["roofline"]["traffic_per_kernel"] = live_traffic["per_kernel"]
-        out["lead_in"] = {"seconds_of_other_legs_before_warmup": t_device_before,
-                          "note": "the stream + per_view legs run before the headline's warm-up (the W warm-up and K timed "
-                                  "steps are unchanged); 0 with --skip-other-path.  Measured and NOT done: the "
-                                  "averaging forms and the other scenes in front as well -- behind 150 ms of "
-                                  "VALU-heavy averaging the same 20 steps read 0.1755-0.1840 ms (DESIGN_APPENDIX 12)"}
+        if a.full:
+            out["lead_in"] = {"seconds_of_other_legs_before_warmup": t_device_before,
+                              "note": "the stream + per_view legs run before the headline's warm-up (the W warm-up and K timed "
+                                      "steps are unchanged); 0 with --skip-other-path.  Measured and NOT done: the "
+                                      "averaging forms and the other scenes in front as well -- behind 150 ms of "
+                                      "VALU-heavy averaging the same 20 steps read 0.1755-0.1840 ms (DESIGN_APPENDIX 12)"}
+        else:
+            out["lead_in"] = {"seconds_of_untimed_steps_before_warmup": t_device_before,
+                              "note": "untimed steps of the headline's schedule for %.2f s before its warm-up, in place of "
+                                      "the legs --full runs there (the W warm-up and K timed steps are unchanged); 0 with "
+                                      "--skip-other-path" % LEAD_IN_S}
         if cold is not None:
             out["cold_first_batch_ms"] = cold["cold_first_batch_ms"]
             out["cold_first_batch"] = cold
@@ -1657,8 +1730,9 @@ def main():
         if pipelined is not None:
             out["pipelined"] = pipelined
         if dt_asm is not None:
-            out["value_carve_only"] = value_carve
-            out["ms_per_step_carve_only"] = dt / a.steps * 1e3
+            if dt is not None:
+                out["value_carve_only"] = value_carve
+                out["ms_per_step_carve_only"] = dt / a.steps * 1e3
             out["value_with_assembly"] = value  # (the name of rounds 2-4; `value` IS the with-assembly rate now)
             out["value_is"] = ("carve + assembly: K steps of clear + 72 resident masks + carve + brick-sparse pack (codes + mixed "
                                "bricks, from the batch's verdict bytes and live list) + all-gather into alternating receive "
@@ -1666,8 +1740,8 @@ def main():
                                "while step k + 1 runs, everything waited for inside the timed region; the roofline object "
                                "describes the carve-only span"
                                + ("; TWO engines on the rank's planes take the steps in turn (double buffering: the pack of "
-                                  "step k is beside the carve of step k + 1 too) -- `ms_per_step_one_engine` is the same loop "
-                                  "on one engine" if dt_asm_one is not None else ""))
+                                  "step k is beside the carve of step k + 1 too)" if twin is not None else "")
+                               + (" -- `ms_per_step_one_engine` is the same loop on one engine" if dt_asm_one is not None else ""))
             if dt_asm_one is not None:
                 out["ms_per_step_one_engine"] = dt_asm_one / a.steps * 1e3
                 out["value_one_engine"] = n_total * V * a.steps / dt_asm_one / 1e6
@@ -1694,9 +1768,9 @@ def main():
             out["average"] = avg
         if gather is not None:
             out["gather"] = gather
-        if world == 1 and a.cpu_seconds > 0:
+        if a.full and world == 1 and a.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(gshape, origin, vs, views, a.cpu_seconds)
-        else:
+        elif a.full:
             out["cpu_baseline"] = None
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

@@ -64,3 +64,36 @@ def test_a_packed_grid_needs_the_hip_engine():
     with pytest.raises(ValueError, match="overlap"):
         sb.all_gather(compress="2bit", overlap=True)
     sb.close()
+
+
+def test_dump_outputs_writes_seeded_float_arrays_of_the_labels(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 only; a volume up to DUMP_SAMPLE voxels whole, a larger one as the same seeded
+    sample in every run; the histograms count every voxel."""
+    import bench
+    rng = np.random.default_rng(7)
+    small = rng.integers(-1, 2, (4, 6, 8)).astype(np.int32)
+    assert bench.dump_outputs(str(tmp_path / "a"), small) == ["labels_histogram", "labels_per_plane", "labels_sample"]
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("labels_histogram", "labels_per_plane", "labels_sample")}
+    assert got["labels_sample"].dtype == np.float32 and np.array_equal(got["labels_sample"], small.ravel())
+    assert got["labels_histogram"].dtype == np.float64 and got["labels_per_plane"].dtype == np.float64
+    assert got["labels_histogram"].tolist() == [float((small == v).sum()) for v in (-1, 0, 1)]
+    assert got["labels_per_plane"].shape == (4, 3) and got["labels_per_plane"][2].tolist() == [float((small[2] == v).sum()) for v in (-1, 0, 1)]
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    big = rng.integers(-1, 2, (10, 20, 30)).astype(np.int32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    s1, s2 = (np.load(str(tmp_path / d / "labels_sample.npy")) for d in ("b", "c"))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, big.size, 100))
+    assert s1.shape == (100,) and np.array_equal(s1, s2) and np.array_equal(s1, big.ravel()[idx])
+    assert np.load(str(tmp_path / "b" / "labels_histogram.npy")).sum() == big.size
+
+
+def test_a_plain_run_is_the_default(monkeypatch):
+    """The legs beside the headline need --full; --dump-outputs is off unless given."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"

@@ -8,5 +8,5 @@ for rep in 1 2; do
 done
 python3 tools/bench_avg.py --reps 3 --tag base 2>/dev/null | tail -1 >> $O
 SPACECARVE_LIB=$A python3 tools/bench_avg.py --reps 3 --tag approx 2>/dev/null | tail -1 >> $O
-SPACECARVE_LIB=$A python3 bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 >> $O
+SPACECARVE_LIB=$A python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 >> $O
 cat $O

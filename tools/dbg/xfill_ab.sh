@@ -9,7 +9,7 @@ for rep in 1 2; do
   SC_X_FILL_STREAM=1 SC_X_FILL_BLOCKS=128 SPACECARVE_LIB=$X python3 tools/bench_scenes.py --steps 40 --scenes plant,dense,solid,literal --tag on128 2>/dev/null | tail -1 >> $O
   SC_X_FILL_STREAM=1 SC_X_FILL_BLOCKS=512 SPACECARVE_LIB=$X python3 tools/bench_scenes.py --steps 40 --scenes plant,dense,solid,literal --tag on512 2>/dev/null | tail -1 >> $O
 done
-SC_X_FILL_STREAM=1 SPACECARVE_LIB=$X python3 bench.py --steps 20 --warmup 5 --skip-other-path --extra-steps 0 --e2e-reps 0 --cold-reps 0 --traffic-passes off 2>/dev/null | tail -1 > gpurun_out/r06/xfill_bench.json
+SC_X_FILL_STREAM=1 SPACECARVE_LIB=$X python3 bench.py --full --steps 20 --warmup 5 --skip-other-path --extra-steps 0 --e2e-reps 0 --cold-reps 0 --traffic-passes off 2>/dev/null | tail -1 > "$(dirname $O)/xfill_bench.json"
 python3 - <<'PY'
 import json
 for l in open("gpurun_out/r06/xfill_ab.txt"):

@@ -13,14 +13,14 @@ cd "$R"
 # under the profiler the line's own child legs (traffic passes, cold process) and the parity check stay out
 QUIET="--cpu-seconds 0 --extra-steps 0 --e2e-reps 0 --cold-reps 0 --traffic-passes off --parity-check off --cold-process off"
 # the driver's own command first: THE headline
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver_cadence.json" 2> "$O/bench_driver_cadence.err" || exit 1
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver_cadence.json" 2> "$O/bench_driver_cadence.err" || exit 1
 # the same cadence under rocprofv3 (kernel means that must agree with the line's roofline) + per-dispatch trace
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_cadence" -- \
-    python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 $QUIET \
+    python3 "$R/bench.py" --full --gpus 1 --steps 20 --warmup 5 $QUIET \
     > "$O/bench_under_rocprof.json" 2> "$O/bench_under_rocprof.err" || exit 2
 rocprofv3 --kernel-trace --output-format csv -d "$O/prof_ramp" -- \
-    python3 "$R/bench.py" --gpus 1 --steps 400 --warmup 20 $QUIET --skip-other-path \
+    python3 "$R/bench.py" --full --gpus 1 --steps 400 --warmup 20 $QUIET --skip-other-path \
     > "$O/bench_ramp.json" 2> "$O/bench_ramp.err" || exit 3
 cd "$R"
 bash tools/profile_gpu.sh "$TAG" --skip-other-path --e2e-reps 0 --cold-reps 0 --traffic-passes off --parity-check off --cold-process off || exit 4
@@ -32,11 +32,11 @@ bash tools/kernel_counters.sh ${TAG}_sq_dense tools/bench_scenes.py --steps 6 --
 bash tools/kernel_counters.sh ${TAG}_avg_u8_grey tools/bench_avg.py --reps 2 --forms u8_grey > "$O/kc_avg_u8.log" 2>&1 || exit 6
 bash tools/kernel_counters.sh ${TAG}_avg_f32_grey tools/bench_avg.py --reps 2 --forms f32_grey > "$O/kc_avg_f32.log" 2>&1 || exit 6
 for sc in noise solid; do bash tools/kstats_any.sh ${TAG}_$sc tools/bench_scenes.py --steps 12 --scenes $sc; done > "$O/scene_kernel_means.txt" 2>&1
-python3 bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" || exit 8
-python3 bench.py --rccl-rehearsal --steps 20 --warmup 5 --cpu-seconds 0 --extra-steps 0 --e2e-reps 0 \
+python3 bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" || exit 8
+python3 bench.py --full --rccl-rehearsal --steps 20 --warmup 5 --cpu-seconds 0 --extra-steps 0 --e2e-reps 0 \
     > "$O/bench_rccl1.json" 2> "$O/bench_rccl1.err" || exit 9
 # N = 2 as a plain command: bench.py starts its own ranks (two of them sharing this box's one GPU, gloo as the transport)
-python3 bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --share-device --cpu-seconds 0 --extra-steps 0 --e2e-reps 0 \
+python3 bench.py --full --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --share-device --cpu-seconds 0 --extra-steps 0 --e2e-reps 0 \
     > "$O/bench_gloo2.json" 2> "$O/bench_gloo2.err" || exit 10
 python3 tools/bench_e2e.py --reps 4 > "$O/e2e.json" 2> "$O/e2e.err" || exit 11
 python3 tools/bench_ml.py > "$O/ml_averaging.json" 2> "$O/ml_averaging.err" || true

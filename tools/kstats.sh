@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/ks_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- \
-    python3 "$R/bench.py" --steps 10 --warmup 2 --cpu-seconds 0 --extra-steps 0 --skip-other-path "$@" \
+    python3 "$R/bench.py" --full --steps 10 --warmup 2 --cpu-seconds 0 --extra-steps 0 --skip-other-path "$@" \
     > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "$TAG failed"; exit 1; }
 python3 - "$OUT" "$TAG" <<'PY'
 import csv, glob, sys
