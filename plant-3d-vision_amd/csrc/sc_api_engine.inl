@@ -625,30 +625,6 @@ int sc_process_views_device(sc_engine *e, int V, const float *K, const float *R,
     return SC_OK;
 }
 
-// The first nv pending descriptors of an engine into its device ring, by a copy on its stream.
-static int stage_descriptors(sc_engine *e, size_t nv, const ViewDesc **out) {
-    if (nv > e->views_cap || e->views_head + nv > e->views_cap) {
-        HIP_TRY(schost::wait_stream(e->stream));
-        e->views_head = 0;
-    }
-    if (nv > e->views_cap) {
-        if (e->views_dev) (void)hipFree(e->views_dev);
-        if (e->views_pin) (void)hipHostFree(e->views_pin);
-        e->views_dev = e->views_pin = nullptr;
-        e->views_cap = 0;
-        size_t cap = std::max<size_t>(nv * 4, 1024);
-        HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->views_dev), cap * sizeof(ViewDesc)));
-        HIP_TRY(sc_pin_malloc(reinterpret_cast<void **>(&e->views_pin), cap * sizeof(ViewDesc), hipHostMallocDefault));
-        e->views_cap = cap;
-    }
-    ViewDesc *pin = e->views_pin + e->views_head, *dev = e->views_dev + e->views_head;
-    memcpy(pin, e->pending.data(), nv * sizeof(ViewDesc));
-    e->views_head += nv;
-    HIP_TRY(hipMemcpyAsync(dev, pin, nv * sizeof(ViewDesc), hipMemcpyHostToDevice, e->stream));
-    *out = dev;
-    return SC_OK;
-}
-
 int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, const float *R, const float *t,
                       const void *const *masks_dev, int H, int W) {
     if (!engines || !masks_dev || L < 1) return fail(SC_ERR_INVALID, "bad label set");
@@ -724,31 +700,19 @@ int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, c
         rc = enqueue_tile8(e, V, K, R, t, masks_dev[l], H, W, row, view);
         if (rc) break;
         if (e->pending[0].occ == nullptr) { rc = fail(SC_ERR_STATE, "no uniformity flags"); break; }
-        rc = stage_descriptors(e, (size_t)V, &vd[l < 64 ? l : 0]);
+        const ViewDesc *pin;
+        rc = stage_descriptors(e, (size_t)V, &vd[l < 64 ? l : 0], &pin);
         if (rc) break;
-        if (need > e->verd_cap) {
-            hipError_t he = schost::wait_stream(main);
-            if (e->verd) (void)hipFree(e->verd);
-            e->verd = nullptr;
-            e->verd_cap = 0;
-            if (he == hipSuccess) he = sc_dev_malloc(reinterpret_cast<void **>(&e->verd), need);
-            if (he != hipSuccess) { rc = fail(SC_ERR_NOMEM, "verdict buffer: %s", hipGetErrorString(he)); break; }
-            e->verd_cap = need;
-        }
+        if (hipMemcpyAsync(const_cast<ViewDesc *>(vd[l < 64 ? l : 0]), pin, (size_t)V * sizeof(ViewDesc), hipMemcpyHostToDevice, main) !=
+            hipSuccess) { rc = fail(SC_ERR_DEVICE, "descriptor copy failed"); break; }
+        rc = grow_buffer(e, reinterpret_cast<void **>(&e->verd), &e->verd_cap, need, 1);
+        if (rc) break;
     }
     if (rc == SC_OK && L > 64) rc = fail(SC_ERR_INVALID, "more than 64 labels");
     for (int l0 = 0; l0 < L && rc == SC_OK; l0 += kMaxLabels) {
         const int n = std::min(kMaxLabels, L - l0);
-        if (n == 1) {  // a label left over: its own launches
-            sc_engine *e = engines[l0];
-            hipLaunchKernelGGL(avg_flags_kernel, dim3((anb + kBlock - 1) / kBlock, (uint32_t)V), dim3(kBlock), 0, main, g, vd[l0],
-                               V, abys, abzs, anb, e->verd, static_cast<uint32_t *>(nullptr));
-            if (e->fresh)
-                hipLaunchKernelGGL(average_brick_kernel<true>, dim3(anb), dim3(kBlock), 0, main, static_cast<float *>(e->state), g,
-                                   vd[l0], V, e->default_value, e->lut_dev, abys, abzs, e->verd, static_cast<uint32_t *>(nullptr));
-            else
-                hipLaunchKernelGGL(average_brick_kernel<false>, dim3(anb), dim3(kBlock), 0, main, static_cast<float *>(e->state), g,
-                                   vd[l0], V, e->default_value, e->lut_dev, abys, abzs, e->verd, static_cast<uint32_t *>(nullptr));
+        if (n == 1) {  // a label left over: its own launches (on `main`: the engine's stream for now)
+            rc = launch_average_bricks(engines[l0], g, vd[l0], V, nullptr, false);
             continue;
         }
         MultiArgs a;

@@ -29,7 +29,8 @@ __device__ __forceinline__ uint32_t u8strip_offset(int u, int v, uint32_t strip)
     return __umul24((uint32_t)u >> 4, strip) + (((uint32_t)v << 4) | ((uint32_t)u & 15u));
 }
 
-template <bool FRESH, bool VEC>
+// (rows are padded to a multiple of 64 voxels: a group's four values are read and written as one float4)
+template <bool FRESH>
 __device__ __forceinline__ void average_body(float *__restrict__ values, const GridDesc &g,
                                              const ViewDesc *__restrict__ views, int nviews,
                                              float init, const float *__restrict__ lut) {
@@ -48,12 +49,9 @@ __device__ __forceinline__ void average_body(float *__restrict__ values, const G
     if (FRESH) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) val[e] = init;
-    } else if (VEC) {
+    } else {
         float4 q = *reinterpret_cast<const float4 *>(p);
         val[0] = q.x; val[1] = q.y; val[2] = q.z; val[3] = q.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) val[e] = (e < (int)vx.nvalid) ? p[e] : 0.0f;
     }
     float z[4];
 #pragma unroll
@@ -100,28 +98,24 @@ __device__ __forceinline__ void average_body(float *__restrict__ values, const G
         for (int e = 0; e < 4; ++e)
             if (ok[e]) val[e] = val[e] + add[e];  // :54
     }
-    if (VEC) {
-        *reinterpret_cast<float4 *>(p) = make_float4(val[0], val[1], val[2], val[3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (e < (int)vx.nvalid) p[e] = val[e];
-    }
+    *reinterpret_cast<float4 *>(p) = make_float4(val[0], val[1], val[2], val[3]);
 }
 
-template <bool FRESH, bool VEC>
+template <bool FRESH, bool VEC>  // VEC: the vector form, the only one (kept in the name profiles know)
 __global__ __launch_bounds__(kBlock) void average_kernel(float *__restrict__ values, GridDesc g,
                                                          const ViewDesc *__restrict__ views,
                                                          int nviews, float init,
                                                          const float *__restrict__ lut) {
-    average_body<FRESH, VEC>(values, g, views, nviews, init, lut);
+    static_assert(VEC, "rows are whole 16-byte groups: the values are always read and written as float4");
+    average_body<FRESH>(values, g, views, nviews, init, lut);
 }
 
-template <bool FRESH, bool VEC>
+template <bool FRESH, bool VEC>  // VEC: see average_kernel
 __global__ __launch_bounds__(kBlock) void average_kernel_1(float *__restrict__ values, GridDesc g,
                                                            ViewDesc view, float init,
                                                            const float *__restrict__ lut) {
-    average_body<FRESH, VEC>(values, g, &view, 1, init, lut);
+    static_assert(VEC, "rows are whole 16-byte groups: the values are always read and written as float4");
+    average_body<FRESH>(values, g, &view, 1, init, lut);
 }
 
 // uint8 [V][H][W] row-major -> strips of 16x8-pixel tiles (128 B each; u8strip_offset) for the averaging gather.

@@ -371,8 +371,7 @@ __global__ __launch_bounds__(64 * kConfirmWaves) void brick_confirm_kernel(
 // The dense kernel proper: a persistent grid walks the live list, one brick per block and turn
 // (wavefront w owns columns 4w..4w+3 of the brick); runs of kXcdRun consecutive entries
 // (neighbouring bricks, which project onto the same mask lines) stay on one XCD.  Blocks behind
-// the walkers, one per strip, fill the bricks found empty of strips [0, nstore) (the final list
-// stage fills the others, see carve_list_kernel).
+// the walkers pack masks (riders); the list stages fill the bricks found empty (carve_list_kernel).
 template <bool FRESH, bool ALL_SAFE = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void carve_brick_kernel(int32_t *__restrict__ labels, GridDesc g,
                                                              const ViewDesc *__restrict__ views,
@@ -381,15 +380,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
                                                              const uint8_t *__restrict__ flags,
                                                              const uint32_t *__restrict__ live,
                                                              ListCtl *ctl, uint32_t nwalkers,
-                                                             uint32_t nstore, PackJob ride, int pack_rows,
+                                                             PackJob ride, int pack_rows,
                                                              uint32_t parity, int nverd_arg, uint32_t verd_max_live,
                                                              uint32_t bulk_min_live, int nextra) {
-    // Behind the walkers come the riders, and the store blocks LAST: blocks start in the order of their numbers, and what
-    // the riders pack is waited for by the next kernel, while a store only has to be done by the end of this one
-    // (with the store blocks in front the riders started when the stores were through, and a sixteenth of the fill
-    // cost this kernel the 5.4 us it takes on its own).
-    const uint32_t nride = gridDim.x - nwalkers - nstore;
-    if (blockIdx.x >= nwalkers && blockIdx.x < nwalkers + nride) {
+    if (blockIdx.x >= nwalkers) {
         // riders: the masks of the views the later stages apply are packed here, beside the walkers
         // (this stage waits on gathers and arithmetic, the packing on HBM reads).  One short block per
         // panel: persistent riders measured the same or slower.
@@ -399,11 +393,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
         else if (pack_rows == 2) pack16_block<2>(ride, b);
         else if (pack_rows == 8) pack16_block<8>(ride, b);
         else pack16_block<4>(ride, b);
-        return;
-    }
-    if (blockIdx.x >= nwalkers) {
-        store_culled_bricks(labels, g, strip_flag(flags, blockIdx.x - nwalkers - nride, bricks_z), blockIdx.x - nwalkers - nride, bricks_y, bricks_z,
-                            Fill{init == 0 ? 1 : init, FRESH ? 1 : 0, init});
         return;
     }
     // Walkers are WAVEFRONTS: each takes the next live brick of its XCD's runs (runs of kXcdRun consecutive entries --
@@ -587,10 +576,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
 // the kernel arguments (no copy, no host-side wait), and each lane walks kStreamGroups
 // 16-byte groups with the next group's state load already in flight -- after the first view
 // nearly every wavefront only streams its state through and leaves.
-template <bool FRESH, bool VEC>
+template <bool FRESH, bool VEC>  // VEC: see carve_kernel
 __global__ __launch_bounds__(kBlock) void carve_kernel_1(int32_t *__restrict__ labels, GridDesc g,
                                                          ViewDesc view, int32_t init) {
-    constexpr int G = (!FRESH && VEC) ? kStreamGroups : 1;
+    static_assert(VEC, "rows are whole 16-byte groups: the state is always read and written as int4");
+    constexpr int G = !FRESH ? kStreamGroups : 1;
     uint32_t lb = spread_block(blockIdx.x, gridDim.x);
     uint64_t grp = (uint64_t)lb * (kBlock * G) + threadIdx.x;
     Append none{nullptr, nullptr, 0u, 0u, nullptr, 0u, 0u};
@@ -602,13 +592,13 @@ __global__ __launch_bounds__(kBlock) void carve_kernel_1(int32_t *__restrict__ l
         v4i q = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(labels + gidx * 4));
         return make_int4(q.x, q.y, q.z, q.w);
     };
-    if (!FRESH && VEC && grp < g.ngroups) cur = stream_load(grp);  // carve_group takes the stored labels from `cur`
+    if (!FRESH && grp < g.ngroups) cur = stream_load(grp);  // carve_group takes the stored labels from `cur`
 #pragma unroll 1
     for (int s = 0; s < G; ++s, grp += kBlock) {
         int4 nxt = make_int4(-1, -1, -1, -1);
         if (G > 1 && s + 1 < G && grp + kBlock < g.ngroups)
             nxt = stream_load(grp + kBlock);
-        if (grp < g.ngroups) carve_group<FRESH, VEC>(labels, g, &view, 1, init, grp, cur, none);
+        if (grp < g.ngroups) carve_group<FRESH>(labels, g, &view, 1, init, grp, cur, none);
         cur = nxt;
     }
 }

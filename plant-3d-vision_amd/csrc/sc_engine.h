@@ -48,22 +48,12 @@ struct sc_engine {
     size_t verd_cap = 0;
     uint32_t *verdf = nullptr;    // ... and, for tiled float32 masks, the value a flat footprint adds
     size_t verdf_cap = 0;
-    int64_t stage1_store_share = 5;  // sixteenths of the deferred strips filled beside the FIRST list stage
-    int64_t stage1_list_blocks = 1280; // ... and that stage's persistent list blocks then
-    int64_t defer_share = 16;     // sixteenths of the strips whose empty bricks the final list stage fills
-    int64_t defer_stores = 1536;  // list blocks of a final stage that also fills the empty bricks (0: the dense stage fills them);
-                                  // 6 per CU beside the store blocks: with six first-stage views 1280 -> 1536 is worth 3-4 % on bulky scenes
-                                  // and nothing on a plant (round 5's last sweep, tools/sweep_blocks*.json); 1600 and more lose 7 % there
     int64_t pack_rows = 0;     // 0: the band form of the 16-byte pack kernel; 1, 2, 4, 8: the panel form, tile rows per block
     int64_t view_brick = 1;    // a single-view carve launch goes through the brick kernels too (0: streaming kernel)
     uint8_t *dead = nullptr;   // per brick: an earlier launch found it empty, every voxel is -1 (until the next clear)
     bool dead_clean = false;   // `dead` describes the labels (false after a clear: the next flags kernel rewrites it)
-    int64_t final_voxels = 2;  // voxels per lane in the final survivor stage (1 or 2)
-    int64_t stage1_voxels = 2; // ... in the stages before it
-    int64_t fill_blocks = 256; // persistent store blocks of a list stage (0: one short block per strip); round 4: 256 (one per CU) from 512, measured after their loop lost its vector instructions
     int64_t pack_ride = 1;     // a device batch is packed at flush, in view order: the first views ahead of
                                // the flags kernel, the others beside the dense stage (0: all ahead)
-    int64_t brick_walkers = 1280;  // persistent blocks of the dense stage when packing rides with it (1024 until round 5: noise -4 %, plant +-0)
     int8_t *narrow = nullptr;  // scratch of sc_get_values_i8
     uint32_t *packed_labels = nullptr;  // sc_values_packed: the labels at 2 or 1 bits each
     uint32_t *wire_stage = nullptr;     // sc_get_values_wire2: page-locked landing place of the packed labels
@@ -97,8 +87,6 @@ struct sc_engine {
     bool last_bulk = false;    // the last fused launch had a bulk list
     uint4 *items = nullptr;    // the bulk units' work items (counts in ctl->count[4])
     uint32_t itemcap = 0;      // ... per sub-list
-    int64_t item_bias = 12;    // sixteenths: items are chosen over the lists when they cost at most this share
-    int64_t unit_blocks = 512; // blocks of 8 wavefronts walking the bulk list behind the confirm kernel
     // Whether the bulk units' verdicts pay is decided on the device, inside the batch, from the number of units its
     // own dense stage left (carve_special_kernel): fewer than this and their voxels take the ordinary lists
     int64_t bulk_floor = 8192;
@@ -123,10 +111,7 @@ struct sc_engine {
 
     // carve masks from the host: packed to bits by host threads into a page-locked arena (two, alternating between
     // flushes), which one copy per flush brings to its device mirror together with the table of the views' records
-    int64_t spec_share = 3;    // sixteenths of the strips set to -1 by fill blocks in front of the flags kernel (fresh volumes)
     int64_t late_road = 1;     // 1: a FULL candidate a late view rejects joins the bulk units (UnitRoad); 0: the late list, always
-    int64_t spec_blocks = 64;  // ... that many persistent blocks of 512 threads (64: a fill that does not saturate HBM leaves the verdicts their memory round trips; 128 measured 2 % slower per batch, 48 too)
-    int64_t dense_extra = 1;   // a unit the dense views thinned out to 32 .. 128 voxels takes one more pair of views there
     int64_t safe_kernels = 1;  // batches whose views are all certified take the list kernels compiled without the general path
     int64_t host_pack = 1;
     struct HostBits {
@@ -155,9 +140,6 @@ struct sc_engine {
     int64_t brick = 1;
     int64_t dense_views = 2;     // views applied to every voxel before compaction
     int64_t stage1_views = 6;    // views applied to the first survivor list (8 until round 5)
-    int64_t stage2_views = 0;    // views applied to the second survivor list (0: no such stage)
-    int64_t list_blocks = 2048;  // persistent grid of list stages without store blocks
-    int64_t view_group = 2;      // the spans of the final list stage are a multiple of this many views
 
     std::vector<TimedLaunch> timed[kNumKernels];
     hipEvent_t step_start = nullptr;

@@ -61,6 +61,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
                                                             ListCtl *ctl, int sin, int sout,
                                                             uint32_t subcap, int vgsize, CullStores cs, UnitItems ui,
                                                             UnitSpill us, int nrest) {  // nrest: views from `views` to the batch's last
+    static_assert(P == 2, "two survivors per lane: the instances with one and with four were retired in round 6");
     __shared__ uint32_t pref[kSub + 1];
     const uint32_t tid = threadIdx.x;
     const uint32_t bx = blockIdx.x, gdim = gridDim.x;
@@ -236,10 +237,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
             y[p] = g.oy + (float)(int)j * g.vs;
             z[p] = g.oz + (float)(int)k * g.vs;
         }
-        // U views per iteration: four (8 projection chains and 8 gathers in flight per lane at P = 2).  The final stage ran
+        // U views per iteration: four (8 projection chains and 8 gathers in flight per lane).  The final stage ran
         // two until round 4's end -- it was bound by its arithmetic then; beside the fill that bounds it now, four took
         // it from 67.2 to 63.3 us and the batch from 0.160 to 0.1545 ms (same box, four runs each).
-        constexpr int U = P >= 4 ? 1 : 4;
+        constexpr int U = 4;
         for (;;) {  // (once; a second time over the views behind this stage's for a chunk whose survivors find no room)
         for (int vi = v0; vi < v1; vi += U) {
             unsigned long long any = 0;
@@ -820,7 +821,7 @@ __global__ __launch_bounds__(64 * kFlagWaves) void carve_special_kernel(int32_t 
         // (a wavefront's lanes leave carve_group's view loop together: skipped lanes still vote)
         if (!skip) {
             const int4 pre = *reinterpret_cast<const int4 *>(labels + grp * 4);
-            carve_group<false, true>(labels, g, sj.rest, sj.nrest, 0, grp, pre, none);
+            carve_group<false>(labels, g, sj.rest, sj.nrest, 0, grp, pre, none);
         }
     }
 }

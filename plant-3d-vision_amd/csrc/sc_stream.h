@@ -17,9 +17,9 @@ struct Append {
 
 // carve (backprojection.c:57-84) of one 4-voxel group over views[0..nviews), state in
 // registers.  FRESH: the state is known to be `init` everywhere (nothing applied since
-// create/clear) and is not read.  VEC: nz % 4 == 0, state accessed as int4 (`pre` holds the
-// group's state, already loaded by the caller so that loads of several groups overlap).
-template <bool FRESH, bool VEC>
+// create/clear) and is not read.  The state is accessed as int4 -- rows are padded to a multiple of 64 voxels -- and
+// `pre` holds the group's state, already loaded by the caller so that loads of several groups overlap.
+template <bool FRESH>
 __device__ __forceinline__ void carve_group(int32_t *__restrict__ labels, const GridDesc &g,
                                             const ViewDesc *__restrict__ views, int nviews,
                                             int32_t init, uint64_t grp, int4 pre,
@@ -29,26 +29,23 @@ __device__ __forceinline__ void carve_group(int32_t *__restrict__ labels, const 
     // a grid whose rows are padded (nz not a multiple of 64) has groups that own fewer than four voxels:
     // they are told apart up front; on an unpadded grid a group is decoded only if something in it lives
     const bool padded = g.nzp != g.nz;  // grid-uniform
-    if (!VEC || padded) decode_group(g, grp, vx);
-    int32_t *p = labels + (VEC ? grp * 4 : vx.elem);
+    if (padded) decode_group(g, grp, vx);
+    int32_t *p = labels + grp * 4;
     if (FRESH) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) lab[e] = init;
-    } else if (VEC) {
-        lab[0] = pre.x; lab[1] = pre.y; lab[2] = pre.z; lab[3] = pre.w;
     } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lab[e] = (e < (int)vx.nvalid) ? p[e] : -1;
+        lab[0] = pre.x; lab[1] = pre.y; lab[2] = pre.z; lab[3] = pre.w;
     }
     uint32_t alive = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        if (VEC && padded && e >= (int)vx.nvalid) lab[e] = -1;  // padding counts as carved
+        if (padded && e >= (int)vx.nvalid) lab[e] = -1;  // padding counts as carved
         was[e] = lab[e];
-        if ((VEC || e < (int)vx.nvalid) && lab[e] != -1) alive |= 1u << e;  // :67
+        if (lab[e] != -1) alive |= 1u << e;  // :67
     }
     if (!FRESH && alive == 0) return;  // nothing to do and nothing to write
-    if (VEC && !padded) decode_group(g, grp, vx);
+    if (!padded) decode_group(g, grp, vx);
 
     float z[4];
 #pragma unroll
@@ -86,15 +83,8 @@ __device__ __forceinline__ void carve_group(int32_t *__restrict__ labels, const 
         }
     }
 
-    if (VEC) {
-        bool changed = FRESH || lab[0] != was[0] || lab[1] != was[1] || lab[2] != was[2] ||
-                       lab[3] != was[3];
-        if (changed) *reinterpret_cast<int4 *>(p) = make_int4(lab[0], lab[1], lab[2], lab[3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (e < (int)vx.nvalid && (FRESH || lab[e] != was[e])) p[e] = lab[e];
-    }
+    bool changed = FRESH || lab[0] != was[0] || lab[1] != was[1] || lab[2] != was[2] || lab[3] != was[3];
+    if (changed) *reinterpret_cast<int4 *>(p) = make_int4(lab[0], lab[1], lab[2], lab[3]);
 
     if (ap.list != nullptr) {
         // survivors -> sub-list `ap.sub`: one atomic per wavefront, entries = slab-local voxel
@@ -133,15 +123,16 @@ __device__ __forceinline__ void carve_group(int32_t *__restrict__ labels, const 
 }
 
 // A chunk of views per launch: one group per lane; optionally appends the survivors.
-template <bool FRESH, bool VEC>
+template <bool FRESH, bool VEC>  // VEC: the vector form, the only one (kept in the name profiles know)
 __global__ __launch_bounds__(kBlock) void carve_kernel(int32_t *__restrict__ labels, GridDesc g,
                                                        const ViewDesc *__restrict__ views,
                                                        int nviews, int32_t init, Append ap) {
+    static_assert(VEC, "rows are whole 16-byte groups: the state is always read and written as int4");
     uint32_t lb = spread_block(blockIdx.x, gridDim.x);
     uint64_t grp = (uint64_t)lb * kBlock + threadIdx.x;
     if (grp >= g.ngroups) return;
     int4 pre = make_int4(0, 0, 0, 0);
-    if (!FRESH && VEC) pre = *reinterpret_cast<const int4 *>(labels + grp * 4);
+    if (!FRESH) pre = *reinterpret_cast<const int4 *>(labels + grp * 4);
     ap.sub = (lb * 0x9E3779B1u) >> 24;  // kSub == 256: hashed, so a dense region loads every sub-list alike
-    carve_group<FRESH, VEC>(labels, g, views, nviews, init, grp, pre, ap);
+    carve_group<FRESH>(labels, g, views, nviews, init, grp, pre, ap);
 }

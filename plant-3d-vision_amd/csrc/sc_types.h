@@ -61,6 +61,20 @@ constexpr int kStreamGroups = 2; // 16-byte groups per lane in the per-view stre
 constexpr int kXcdRun = 16;      // consecutive logical blocks kept on one XCD
 constexpr int kCandSub = 8;      // sub-lists of the candidate list (see ListCtl::ncand)
 
+// Launch shape of the fused carve.  These were sc_set_option knobs until round 6, which fixed each at the value its
+// sweeps had settled on (profiles/r05_sweep_defaults.json); the keys are still accepted, with no effect.
+constexpr uint32_t kListBlocks = 2048;       // persistent blocks of a list stage without a share of the fill
+constexpr uint32_t kBrickWalkers = 1280;     // dense stage with packing riders: walkers leave wavefront slots to the riders
+constexpr uint32_t kFinalListBlocks = 1536;  // final list stage, beside its store blocks: 6 per CU (1600+ lost 7 % on a plant)
+constexpr uint32_t kStoreBlocks = 256;       // persistent store blocks of a list stage: one per CU keeps the write path busy
+constexpr uint32_t kStage1StoreShare = 5;    // sixteenths of the fill the first list stage takes (it waits on memory)
+constexpr uint32_t kStage1ListBlocks = 1280; // ... and its persistent list blocks then
+constexpr uint32_t kSpecShare = 3;           // sixteenths of the strips a fresh volume fills ahead of the verdicts (SpecFill)
+constexpr uint32_t kSpecBlocks = 64;         // ... by that many blocks: a fill short of HBM's rate leaves the verdicts room
+constexpr uint32_t kUnitBlocks = 512;        // blocks of the special kernel walking the bulk list
+constexpr uint32_t kItemBias = 12;           // sixteenths: a unit's views become work items when they cost at most this share
+constexpr int kViewGroup = 2;                // the spans of the final list stage are a multiple of this many views
+
 // Survivor lists of the fused carve (see carve_list_kernel).  Zeroed before every fused launch.
 // Every counter sits on a 128-byte line of its own: returning device-scope atomics on one
 // line serialise (~90 per microsecond measured), on different lines they do not.

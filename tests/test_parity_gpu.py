@@ -149,10 +149,8 @@ def test_failed_reservations_leave_no_holes_in_the_lists(gpu_device, device_mask
     sh, origin, vs, views = scene((11, 13, 58), 15, "solid", **kw)
     want = oracle_c.carve(sh, origin, vs, views, nthreads=4)
     assert 0 < (want == 0).sum() < want.size  # part of the grid is outside every picture
-    opts = {"SC_OPT_DENSE_VIEWS": 3, "SC_OPT_STAGE1_VIEWS": 64, "SC_OPT_DEFER_SHARE": 5, "SC_OPT_COMPACT": 1,
-            "SC_OPT_BRICK_WALKERS": 8, "SC_OPT_FILL_BLOCKS": 1, "SC_OPT_STAGE1_VOXELS": 1, "SC_OPT_VIEW_BRICK": 1,
-            "SC_OPT_STAGE1_LIST_BLOCKS": 1280, "SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_LIVE": 0, "SC_OPT_ITEM_BIAS": 0, "SC_OPT_UNIT_CULL": 0,
-            "SC_OPT_LIST_CAP": 2}
+    opts = {"SC_OPT_DENSE_VIEWS": 3, "SC_OPT_STAGE1_VIEWS": 64, "SC_OPT_COMPACT": 1, "SC_OPT_VIEW_BRICK": 1,
+            "SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_LIVE": 0, "SC_OPT_UNIT_CULL": 0, "SC_OPT_LIST_CAP": 2}
     for stage1 in (64, 4):  # a single (final) list stage, and two
         e = nat.Engine(sh, origin, vs, nat.SC_MODE_CARVE)
         for k, v in opts.items():
@@ -196,7 +194,7 @@ def test_bulk_unit_without_room_in_the_lists_is_carved_on_the_spot(gpu_device, k
     want = oracle_c.carve(sh, origin, vs, views, nthreads=4)
     e = nat.Engine(sh, origin, vs, nat.SC_MODE_CARVE)
     for k, val in ((nat.SC_OPT_LIST_CAP, 2), (nat.SC_OPT_BULK_MIN, 1), (nat.SC_OPT_BULK_LIVE, 0), (nat.SC_OPT_BULK_FLOOR, floor),
-                   (nat.SC_OPT_ITEM_BIAS, 0), (nat.SC_OPT_UNIT_CULL, 0)):
+                   (nat.SC_OPT_UNIT_CULL, 0)):
         e.set_option(k, val)
     ptr = _batch(e, views, False)
     assert np.array_equal(e.get_values(), want), (kind, floor, histogram3(want))
@@ -258,54 +256,54 @@ def test_brick_culling_is_exact(gpu_device, shape, kw, kind):
     {"SC_OPT_FLAG_VIEWS": 0},                                             # every view may veto a brick
     {"SC_OPT_FLAG_VIEWS": 1, "SC_OPT_DENSE_VIEWS": 1},
     {"SC_OPT_FLAG_VIEWS": 11, "SC_OPT_DENSE_VIEWS": 3, "SC_OPT_STAGE1_VIEWS": 3},
-    {"SC_OPT_DEFER_STORES": 0},                                           # dense stage fills empty bricks
-    {"SC_OPT_DEFER_SHARE": 0},
-    {"SC_OPT_DEFER_SHARE": 7, "SC_OPT_DEFER_STORES": 24},                 # fill split between the two
-    {"SC_OPT_LIST_BLOCKS": 8, "SC_OPT_DEFER_STORES": 8},                  # tiny persistent grids
     {"SC_OPT_STAGE1_VIEWS": 64},                                          # single (final) list stage
-    {"SC_OPT_STAGE1_VIEWS": 2, "SC_OPT_STAGE2_VIEWS": 3, "SC_OPT_VIEW_GROUP": 2},
-    {"SC_OPT_VIEW_GROUP": 5, "SC_OPT_PACK_ROWS": 1},
+    {"SC_OPT_STAGE1_VIEWS": 2},
+    {"SC_OPT_PACK_ROWS": 1},
     {"SC_OPT_FULL_BRICKS": 0},
-    {"SC_OPT_STAGE1_STORE_SHARE": 0},                                     # the final stage fills everything
-    {"SC_OPT_STAGE1_STORE_SHARE": 16, "SC_OPT_STAGE1_LIST_BLOCKS": 8},    # ... the first stage does
-    {"SC_OPT_STAGE1_STORE_SHARE": 9, "SC_OPT_DEFER_SHARE": 11, "SC_OPT_DEFER_STORES": 40},  # all three kernels fill
     {"SC_OPT_COMPACT": 0},                                                # bricks without survivor lists
     {"SC_OPT_VIEW_ORDER": 0},
-    {"SC_OPT_FILL_BLOCKS": 0},                                            # one short store block per strip
-    {"SC_OPT_FILL_BLOCKS": 3, "SC_OPT_STAGE1_STORE_SHARE": 8},            # a few persistent ones
     {"SC_OPT_PACK_RIDE": 0},                                              # every mask packed ahead
-    {"SC_OPT_FINAL_VOXELS": 1},                                           # one survivor per lane in the final stage
-    {"SC_OPT_FINAL_VOXELS": 4, "SC_OPT_STAGE1_VOXELS": 2},                # four, one view per turn; two in the first stage
-    {"SC_OPT_STAGE1_VOXELS": 4, "SC_OPT_VIEW_GROUP": 3},
-    {"SC_OPT_BRICK_WALKERS": 8, "SC_OPT_FILL_BLOCKS": 1, "SC_OPT_VIEW_ORDER": 0},
     {"SC_OPT_BULK_MIN": 0},                                               # no unit is finished as a whole
     {"SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0, "SC_OPT_BULK_LIVE": 0},  # every unit with a voxel alive is, and asked
     {"SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0, "SC_OPT_BULK_LIVE": 16},  # ... unless every brick is live: never
     {"SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_LIVE": 0},                        # ... too few for the default floor: spilled
-    {"SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0, "SC_OPT_BULK_LIVE": 0, "SC_OPT_ITEM_BIAS": 64},  # items whatever they cost
-    {"SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0, "SC_OPT_BULK_LIVE": 0, "SC_OPT_ITEM_BIAS": 0},   # never items: asked, then the lists
     {"SC_OPT_BULK_MIN": 256, "SC_OPT_FULL_BRICKS": 0, "SC_OPT_BULK_FLOOR": 0},
-    {"SC_OPT_BULK_MIN": 40, "SC_OPT_DENSE_VIEWS": 1, "SC_OPT_LIST_BLOCKS": 8, "SC_OPT_BULK_FLOOR": 0},
-    {"SC_OPT_BULK_MIN": 40, "SC_OPT_UNIT_BLOCKS": 1, "SC_OPT_BULK_FLOOR": 3},  # one block does all the special kernel has
+    {"SC_OPT_BULK_MIN": 40, "SC_OPT_DENSE_VIEWS": 1, "SC_OPT_BULK_FLOOR": 0},
+    {"SC_OPT_BULK_MIN": 40, "SC_OPT_BULK_FLOOR": 3},
     {"SC_OPT_PACK_ROWS": 4},                                              # the panel form of the pack kernel
     {"SC_OPT_PACK_ROWS": 3, "SC_OPT_PACK_RIDE": 0},                       # bands, every mask packed ahead
     {"SC_OPT_PACK_ROWS": 8, "SC_OPT_PACK_RIDE": 0},
     {"SC_OPT_UNIT_CULL": 0},                                              # no unit verdicts in the dense stage
     {"SC_OPT_UNIT_CULL": 2, "SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0},  # ... asked whatever the tiles settled
-    {"SC_OPT_UNIT_CULL": 2, "SC_OPT_PACK_RIDE": 0, "SC_OPT_BRICK_WALKERS": 8},  # by 16 views, few walkers
+    {"SC_OPT_UNIT_CULL": 2, "SC_OPT_PACK_RIDE": 0},                       # ... by 16 views
     {"SC_OPT_SAFE_KERNELS": 0},                                           # the list kernels with the general path compiled in
-    {"SC_OPT_DENSE_EXTRA": 0},                                            # no third pair of dense views for thinned-out units
-    {"SC_OPT_SPEC_SHARE": 0},                                             # no fill ahead of the verdicts
-    {"SC_OPT_SPEC_SHARE": 16, "SC_OPT_SPEC_BLOCKS": 7},                   # ... all of it, by an odd number of blocks
-    {"SC_OPT_SPEC_SHARE": 9, "SC_OPT_FILL_BLOCKS": 0},
     {"SC_OPT_LATE_ROAD": 0},                                              # failed candidates on the late list, always
     {"SC_OPT_LATE_ROAD": 1, "SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0, "SC_OPT_BULK_LIVE": 0},  # ... among many bulk units
     {"SC_OPT_LATE_ROAD": 1, "SC_OPT_BULK_FLOOR": 1 << 30},               # ... alone: the bulk units spill, the late ones are asked
-    {"SC_OPT_DEFER_SHARE": 5},                                            # the dense kernel fills most strips itself (and nobody rides)
-    {"SC_OPT_DEFER_SHARE": 2, "SC_OPT_FILL_BLOCKS": 0},
-    {"SC_OPT_FILL_BLOCKS": 64, "SC_OPT_DEFER_SHARE": 11, "SC_OPT_STAGE1_STORE_SHARE": 3},  # few store blocks, odd shares
     {"SC_OPT_DENSE_VIEWS": 3, "SC_OPT_UNIT_CULL": 0},
-    {"SC_OPT_DEFER_STORES": 1280, "SC_OPT_STAGE1_VIEWS": 8, "SC_OPT_STAGE1_STORE_SHARE": 4, "SC_OPT_BRICK_WALKERS": 1024},  # rounds 3-5's defaults
+    {"SC_OPT_STAGE1_VIEWS": 8},                                           # rounds 3-5's default
+    {"SC_OPT_BRICK": 0},                                                  # linear dense blocks, then the survivor lists
+    {"SC_OPT_BRICK": 0, "SC_OPT_STAGE1_VIEWS": 64},
+    {"SC_OPT_BRICK": 0, "SC_OPT_COMPACT": 0},                             # every view applied densely, linear blocks
+    {"SC_OPT_HOST_PACK": 0},                                              # host masks through the ring, packed on the device
+    {"SC_OPT_HOST_PACK": 0, "SC_OPT_PACK_ROWS": 4},
+    {"SC_OPT_LIST_CAP": 64},                                              # survivor sub-lists that overflow
+    {"SC_OPT_LIST_CAP": 2, "SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0, "SC_OPT_BULK_LIVE": 0},  # ... bulk units without room
+    {"SC_OPT_DENSE_VIEWS": 4, "SC_OPT_STAGE1_VIEWS": 4},
+    {"SC_OPT_STAGE1_VIEWS": 1},                                           # a first list stage of one view
+    {"SC_OPT_FLAG_VIEWS": 2, "SC_OPT_PACK_RIDE": 0},
+    {"SC_OPT_FLAG_VIEWS": 0, "SC_OPT_FULL_BRICKS": 0},
+    {"SC_OPT_COMPACT": 0, "SC_OPT_FULL_BRICKS": 0},                       # the light kernel's fill without FULL bricks
+    {"SC_OPT_COMPACT": 0, "SC_OPT_PACK_RIDE": 0},
+    {"SC_OPT_SAFE_KERNELS": 0, "SC_OPT_STAGE1_VIEWS": 64},
+    {"SC_OPT_SAFE_KERNELS": 0, "SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0, "SC_OPT_BULK_LIVE": 0},
+    {"SC_OPT_LATE_ROAD": 0, "SC_OPT_BULK_MIN": 1, "SC_OPT_BULK_FLOOR": 0, "SC_OPT_BULK_LIVE": 0},
+    {"SC_OPT_UNIT_CULL": 0, "SC_OPT_PACK_RIDE": 0},
+    {"SC_OPT_BULK_MIN": 64, "SC_OPT_STAGE1_VIEWS": 64, "SC_OPT_BULK_FLOOR": 0},  # bulk units with a single list stage
+    {"SC_OPT_VIEW_ORDER": 0, "SC_OPT_PACK_RIDE": 0},
+    {"SC_OPT_PACK_ROWS": 2},
+    {"SC_OPT_PACK_ROWS": 2, "SC_OPT_PACK_RIDE": 0, "SC_OPT_FLAG_VIEWS": 0},
+    {"SC_OPT_FULL_BRICKS": 0, "SC_OPT_LATE_ROAD": 0},
 ])
 @pytest.mark.parametrize("kind,shape", [("plant", (24, 32, 128)), ("noise", (6, 16, 64)), ("plant", (9, 48, 192)),
                                         ("dense", (14, 48, 192)),    # a bulky object: whole-brick masks at work
@@ -344,13 +342,14 @@ def test_fused_pipeline_knobs_never_change_a_label(gpu_device, opts, kind, shape
     e.close()
 
 
-@pytest.mark.parametrize("opts", [{"SC_OPT_BRICK_WALKERS": 8}, {"SC_OPT_LIST_BLOCKS": 8, "SC_OPT_PACK_RIDE": 0},
-                                  {"SC_OPT_BRICK_WALKERS": 24}, {}])
+@pytest.mark.parametrize("opts", [{"SC_OPT_UNIT_CULL": 0}, {"SC_OPT_PACK_RIDE": 0}, {"SC_OPT_UNIT_CULL": 2}, {}])
 def test_few_walker_blocks_on_a_long_live_list(gpu_device, opts):
     """The dense stage's walkers draw their bricks from eight ticket counters per XCD, each dealing every eighth run of
-    16 live-list entries.  With 8 walker blocks an XCD has four wavefronts: they must share four counters -- with
+    16 live-list entries.  With 8 walker blocks an XCD had four wavefronts: they must share four counters -- with
     eight, the runs of the counters nobody holds went to nobody, and a live list of more than 512 bricks kept labels no
-    view had been applied to (round 4, found by the fuzz sweep once it drew grids of this size)."""
+    view had been applied to (round 4, found by the fuzz sweep once it drew grids of this size).  The walker counts
+    are fixed now (kBrickWalkers with riders, kListBlocks without): a long live list under both, with the units of
+    every live brick asked about (the default), never asked, or asked whatever the tiles settled."""
     sh, origin, vs, views = scene((36, 142, 208), 12, "noise")
     want = oracle_c.carve(sh, origin, vs, views, nthreads=8)
     e = nat.Engine(sh, origin, vs, nat.SC_MODE_CARVE)
@@ -415,10 +414,12 @@ def test_bricks_every_view_keeps_whole(gpu_device, shape, default_value, defer):
         vv = [(K, R, t, m) for (K, R, t, _), m in zip(views, masks)]
         want = oracle_c.carve(sh, origin, vs, vv, default_value, nthreads=4)
         e = nat.Engine(sh, origin, vs, nat.SC_MODE_CARVE, default_value=default_value)
-        e.set_option(nat.SC_OPT_DEFER_STORES, defer)
+        # who fills the bricks found empty: the store blocks beside the final list stage's 1536 blocks (defer 1536), or
+        # the light dense kernel of a batch without survivor stages (defer 0)
+        e.set_option(nat.SC_OPT_COMPACT, 1 if defer else 0)
         for K, R, t, m in vv:
             e.process_view(K, R, t, m, nat.SC_MASK_U8)
-        assert np.array_equal(e.get_values(), want), ("fresh", histogram3(want))
+        assert np.array_equal(e.get_values(), want), ("fresh", defer, histogram3(want))
         for K, R, t, m in vv:
             e.process_view(K, R, t, m, nat.SC_MASK_U8)
         assert np.array_equal(e.get_values(), want), "stored state"
@@ -1214,10 +1215,26 @@ def _device_batch_carve(shape, origin, vs, views, opts=(), default_value=0, prel
 def test_device_batch_packed_at_flush_equals_oracle(gpu_device, ride, kind, shape, v):
     _, origin, vs, views = scene(shape, v, kind)
     want = oracle_c.carve(list(shape), origin, vs, views, nthreads=4)
-    for walkers in (1024, 8):
-        got, _ = _device_batch_carve(shape, origin, vs, views,
-                                     opts=((nat.SC_OPT_PACK_RIDE, ride), (nat.SC_OPT_BRICK_WALKERS, walkers)))
-        assert np.array_equal(got, want), (kind, ride, walkers, histogram3(got), histogram3(want))
+    got, _ = _device_batch_carve(shape, origin, vs, views, opts=((nat.SC_OPT_PACK_RIDE, ride),))
+    assert np.array_equal(got, want), (kind, ride, histogram3(got), histogram3(want))
+
+
+@pytest.mark.parametrize("key", ["SC_OPT_LIST_BLOCKS", "SC_OPT_VIEW_GROUP", "SC_OPT_STAGE2_VIEWS", "SC_OPT_DEFER_STORES",
+                                 "SC_OPT_DEFER_SHARE", "SC_OPT_STAGE1_STORE_SHARE", "SC_OPT_STAGE1_LIST_BLOCKS",
+                                 "SC_OPT_BRICK_WALKERS", "SC_OPT_FILL_BLOCKS", "SC_OPT_FINAL_VOXELS", "SC_OPT_STAGE1_VOXELS",
+                                 "SC_OPT_ITEM_BIAS", "SC_OPT_UNIT_BLOCKS", "SC_OPT_DENSE_EXTRA", "SC_OPT_SPEC_SHARE",
+                                 "SC_OPT_SPEC_BLOCKS", "SC_OPT_LDS_TILES"])
+def test_retired_keys_are_accepted_without_effect(gpu_device, key):
+    """The retired tuning keys keep their numbers (ABI): sc_set_option accepts 0 and a large value for each, and a
+    fused batch (riders, store blocks, bulk units) then labels every voxel as the oracle and a default engine do."""
+    shape = (20, 48, 192)
+    _, origin, vs, views = scene(shape, 18, "dense")
+    want = oracle_c.carve(list(shape), origin, vs, views, nthreads=4)
+    default, _ = _device_batch_carve(shape, origin, vs, views)
+    k = getattr(nat, key)
+    got, _ = _device_batch_carve(shape, origin, vs, views, opts=((k, 0), (k, 1 << 20)))
+    assert np.array_equal(default, want), histogram3(want)
+    assert np.array_equal(got, default), (key, histogram3(got), histogram3(default))
 
 
 @pytest.mark.parametrize("odd", [0, 3, 7, 11, 13])
@@ -1623,7 +1640,7 @@ def test_bricks_no_view_sees_keep_their_labels(gpu_device, kind, default_value):
         assert h[1] > 0.3 * want.size, h  # a good part of the grid is seen by no view (label 0 stays)
         assert h[0] > 0 or kind != "plant", h
     for opts in ((), ((nat.SC_OPT_FLAG_VIEWS, 3),), ((nat.SC_OPT_PACK_RIDE, 0),), ((nat.SC_OPT_FULL_BRICKS, 0),),
-                 ((nat.SC_OPT_DEFER_STORES, 0),), ((nat.SC_OPT_VIEWS_PER_LAUNCH, 1),), ((nat.SC_OPT_VIEWS_PER_LAUNCH, 5),),
+                 ((nat.SC_OPT_VIEWS_PER_LAUNCH, 1),), ((nat.SC_OPT_VIEWS_PER_LAUNCH, 5),),
                  ((nat.SC_OPT_VIEWS_PER_LAUNCH, 1), (nat.SC_OPT_VIEW_BRICK, 0)), ((nat.SC_OPT_COMPACT, 0),)):
         got, counts = _device_batch_carve(shape, origin, vs, views, opts=opts, default_value=default_value)
         assert np.array_equal(got, want), (kind, default_value, opts, histogram3(got), histogram3(want))

@@ -12,18 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from plant3dvision_amd import _native as nat, scenes  # noqa: E402
 
 SWEEP = [
-    (),
-    (("SC_OPT_STAGE1_STORE_SHARE", 0), ("SC_OPT_STAGE1_LIST_BLOCKS", 2048)),
-    (("SC_OPT_STAGE1_STORE_SHARE", 0), ("SC_OPT_STAGE1_LIST_BLOCKS", 1792)),
-    (("SC_OPT_STAGE1_STORE_SHARE", 0), ("SC_OPT_STAGE1_LIST_BLOCKS", 1536)),
-    (("SC_OPT_STAGE1_STORE_SHARE", 0), ("SC_OPT_STAGE1_LIST_BLOCKS", 1280)),
-    (("SC_OPT_STAGE1_STORE_SHARE", 2), ("SC_OPT_STAGE1_LIST_BLOCKS", 1792)),
-    (("SC_OPT_STAGE1_STORE_SHARE", 2), ("SC_OPT_STAGE1_LIST_BLOCKS", 1536)),
-    (("SC_OPT_STAGE1_STORE_SHARE", 4), ("SC_OPT_STAGE1_LIST_BLOCKS", 1792), ("SC_OPT_FILL_BLOCKS", 256)),
-    (("SC_OPT_STAGE1_VOXELS", 1), ("SC_OPT_STAGE1_LIST_BLOCKS", 1792), ("SC_OPT_STAGE1_STORE_SHARE", 0)),
-    (("SC_OPT_STAGE1_VOXELS", 1),),
-    (("SC_OPT_FINAL_VOXELS", 1),), (("SC_OPT_FINAL_VOXELS", 4),),
-    (("SC_OPT_DEFER_SHARE", 14),), (("SC_OPT_DEFER_SHARE", 12),),
+    (),  # the defaults, before and after: a sweep of the live keys comes from sets.json
     (),
 ]
 
