@@ -42,6 +42,9 @@ def load():
     lib.oracle_carve_view_planes.restype = ctypes.c_int
     lib.oracle_average_view.argtypes = [fp, ip, fp, fp, fp, fp, fp] + common_tail
     lib.oracle_average_view.restype = ctypes.c_int
+    lib.oracle_average_view_planes.argtypes = [fp, ip, fp, fp, fp, fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
+    lib.oracle_average_view_planes.restype = ctypes.c_int
     lib.oracle_project.argtypes = [ip, ctypes.c_int64, fp, fp, fp, fp, ctypes.c_int,
                                    ctypes.c_int, ip, ip, ip]
     lib.oracle_project.restype = ctypes.c_int
@@ -144,6 +147,28 @@ def average(shape, origin, voxel_size, views, default_value=0, nthreads=1):
     for K, R, t, mask in views:
         vol.process_view(K, R, t, mask, nthreads=nthreads)
     return vol.values
+
+
+def average_planes(shape, origin, voxel_size, views, first, stride, nplanes, default_value=0, nthreads=1, values=None):
+    """A rank's share of the average, as ``carve_planes``: planes first, first + stride, ... of the grid,
+    coordinates from the GLOBAL plane index, float32 masks summed in the order given.  ``values`` (float32
+    [nplanes][ny][nz]) continues a sum already made; otherwise it starts at ``default_value``."""
+    lib = load()
+    shape_h = np.array([int(s) for s in shape], dtype=np.int32)
+    volinfo = np.array([*origin, voxel_size], dtype=np.float32)
+    if values is None:
+        values = np.full((int(nplanes), int(shape[1]), int(shape[2])), default_value, dtype=np.float32)
+    assert values.dtype == np.float32 and values.flags["C_CONTIGUOUS"]
+    assert values.shape == (int(nplanes), int(shape[1]), int(shape[2])), values.shape
+    for K, R, t, mask in views:
+        K, R, t = _f32(K, 4), _f32(R, 9), _f32(t, 3)
+        H, W = mask.shape
+        mask_h = np.ascontiguousarray(mask, dtype=np.float32)  # cl.py:215
+        rc = lib.oracle_average_view_planes(_fp(values), _ip(shape_h), _fp(volinfo), _fp(K), _fp(R), _fp(t),
+                                            _fp(mask_h), W, H, int(first), int(stride), int(nplanes), int(nthreads))
+        if rc != 0:
+            raise RuntimeError(f"oracle returned {rc}")
+    return values
 
 
 def project(ijk, origin, voxel_size, K, R, t, W, H):

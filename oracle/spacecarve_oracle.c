@@ -253,6 +253,14 @@ int oracle_average_view(float *values, const int32_t *shape, const float *volinf
     return run_view(1, values, shape, volinfo, K, R, t, mask, W, H, begin, end, nthreads, 0, 1, shape ? shape[0] : 0);
 }
 
+/* The same launch over a rank's planes only, as oracle_carve_view_planes: values holds nplanes planes, local plane p
+ * being plane first + p * stride of the grid, coordinates from the WHOLE grid's index (backprojection.c:43, 46-48). */
+int oracle_average_view_planes(float *values, const int32_t *shape, const float *volinfo, const float *K,
+                               const float *R, const float *t, const float *mask, int W, int H, int64_t first,
+                               int64_t stride, int64_t nplanes, int nthreads) {
+    return run_view(1, values, shape, volinfo, K, R, t, mask, W, H, -1, -1, nthreads, first, stride, nplanes);
+}
+
 /*
  * Projection of explicit voxel indices, for edge-case tests: writes u, v (INT_MIN-style
  * raw casts included) and ok[n] = 1 when the reference would touch mask[v][u].

@@ -179,10 +179,59 @@ def rank_digests(nthreads=None, only_missing=False):
     json.dump(digests, open(path, "w"), indent=1, sort_keys=True)
 
 
+def average_digests(nthreads=None):
+    """The `average` kernel (backprojection.c:36-55) at the sizes bench.py times it and cfg 4 shards it: SHA-256 of the
+    ORACLE's float32 C-order volume, the masks converted as cl.py:205-208 does (``averaging_table``) and summed in view
+    order.  `python tests/golden/make_golden.py average` computes only the keys that are not there yet (a few minutes
+    on 8 cores)."""
+    from plant3dvision_amd.cl import averaging_table
+    from plant3dvision_amd.sharded import rank_planes
+    from tests.helpers import grey_masks, table_views
+    nthreads = nthreads or min(32, os.cpu_count() or 8)
+    path = os.path.join(OUT, "synthetic_digests.json")
+    digests = json.load(open(path))
+
+    def put(key, form, values):
+        digests[key] = {"sha256_float32": sha256(values), "form": form}
+        print(key, digests[key], flush=True)
+        json.dump(digests, open(path, "w"), indent=1, sort_keys=True)
+
+    key = "average_plant_128_12_u8_binary_log"
+    if key not in digests:
+        shape, origin, vs, views = scenes.make_scene(128, 12, "plant")
+        put(key, "uint8 binary masks, log", oracle_c.average(shape, origin, vs, table_views(views, averaging_table(True)),
+                                                            nthreads=nthreads))
+    shape, origin, vs, views = scenes.make_scene(512, 72, "plant")
+    grey = None
+    for form, log in (("u8_binary", False), ("u8_binary", True), ("u8_grey", False)):
+        key = f"average_plant_512_72_{form}" + ("_log" if log else "")
+        if key in digests:
+            continue
+        if form == "u8_grey" and grey is None:
+            grey = grey_masks((len(views), *views[0][3].shape))
+        masks = grey if form == "u8_grey" else None
+        vals = oracle_c.average(shape, origin, vs, table_views(views, averaging_table(log), masks), nthreads=nthreads)
+        put(key, "uint8 %s masks%s (bench.py average_forms)" % (form[3:], ", log" if log else ""), vals)
+        del vals
+    del grey, views
+    shape, origin, vs, views = scenes.make_scene(1024, 72, "plant")
+    for partition in ("cyclic", "slab"):
+        key = f"average_plant_1024_72_{partition}_rank3of8_u8_binary_log"
+        if key in digests:
+            continue
+        pl = rank_planes(shape[0], 8, 3, partition)
+        vals = oracle_c.average_planes(shape, origin, vs, table_views(views, averaging_table(True)), pl.start, pl.step,
+                                       len(pl), nthreads=nthreads)
+        put(key, f"uint8 binary masks, log; the planes of rank 3 of 8 ({partition})", vals)
+        del vals
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "big":
         big_digests()
     elif len(sys.argv) > 1 and sys.argv[1] == "ranks":
         rank_digests(only_missing=True)
+    elif len(sys.argv) > 1 and sys.argv[1] == "average":
+        average_digests()
     else:
         main()

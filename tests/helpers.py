@@ -269,3 +269,16 @@ def scene(n, n_views, kind="plant", **kw):
     for _, _, _, m in views:
         m.setflags(write=False)
     return shape, origin, vs, views
+
+
+def grey_masks(shape):
+    """The grey bytes bench.py's ``average_forms`` times beside the binary masks: ``default_rng(4321)`` over the
+    whole ``[V, H, W]`` stack."""
+    return np.random.default_rng(4321).integers(0, 256, shape, dtype=np.uint8)
+
+
+def table_views(views, table, masks=None):
+    """``(K, R, t, table[mask])`` view after view, the float32 mask made only when the oracle reaches it (the float
+    stack of 72 pictures of 1440 x 1080 is 448 MB); ``masks[q]`` replaces the scene's own mask of view q."""
+    for q, (K, R, t, m) in enumerate(views):
+        yield K, R, t, table[m if masks is None else masks[q]]

@@ -6,7 +6,8 @@
   plane-cyclic and slab partitions -- every voxel of a rank's 128 planes against the oracle over those planes
   (coordinates from the GLOBAL plane index) + the committed digests + properties;
 * cfg 5 (Masks2D feeding a 512^3 volume): 72 stand-in predictions of 896 x 896 -> per-label masks on
-  the device -> 512^3 averaging and carving volumes -- properties + a voxel sample;
+  the device -> 512^3 averaging and carving volumes -- the averaging volumes of every label (the config's
+  log = false) and of one label with log, whole grid, against the oracle; the rest on a voxel sample;
 * the bench's extra scenes (dense, solid, noise) at 512^3: the whole grid against the oracle, fused == per view.
 """
 import json
@@ -20,10 +21,10 @@ from plant3dvision_amd import _native as nat
 from plant3dvision_amd import masks2d, scenes
 from plant3dvision_amd.cl import EPS, averaging_table
 from plant3dvision_amd.sharded import rank_planes
-from tests.helpers import histogram3, scene, sha256
+from tests.helpers import histogram3, scene, sha256, table_views
 
 pytestmark = pytest.mark.gpu
-THREADS = min(32, os.cpu_count() or 8)
+THREADS = min(16, os.cpu_count() or 8)  # a GPU host grants 16 CPUs; os.cpu_count() counts the whole machine
 GOLD = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "synthetic_digests.json")))
 
 
@@ -190,8 +191,11 @@ def test_cfg3_other_scenes_whole_grid_vs_oracle(gpu_device, kind):
 def test_cfg5_masks2d_896_feeding_512_cubed(gpu_device):
     """ml_pipe_real.toml's shape of work: 72 predictions of 896 x 896 (a seeded stand-in for the
     unvendored romiseg network) -> per-label uint8 masks on the device -> 512^3 volumes, averaging
-    (log, as the config) and carving, no host round trip and NO synchronisation between the torch ops
-    that make the masks and the engine that reads them."""
+    (log = true; and log = false, as ml_pipe_real.toml:44 sets it) and carving, no host round trip and NO
+    synchronisation between the torch ops that make the masks and the engine that reads them.  Three labels
+    of 896-pixel rows take the shared launch of every label (sc_average_labels): with log = false each
+    label's whole volume against the oracle, with log = true one label's whole volume against the oracle's
+    exp / clip (tasks/cl.py:172-174), the others on a voxel sample."""
     import torch
     labels = ["background", "flower", "stem"]
     shape, origin, vs, views = scenes.make_scene(512, 72, "empty", width=896, height=896, fx=371.2 * 2, fy=371.2 * 2,
@@ -222,6 +226,21 @@ def test_cfg5_masks2d_896_feeding_512_cubed(gpu_device):
         want[want > 1] = 1.0  # tasks/cl.py:172-174
         got = vols[name][ijk[:, 0], ijk[:, 1], ijk[:, 2]]
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), name
+    # one label's whole volume: np.exp of the oracle's sum, then vol[vol > 1] = 1 (tasks/cl.py:172-174)
+    want = oracle_c.average(shape, origin, vs, table_views(views, table, host["stem"]), nthreads=THREADS)
+    with np.errstate(over="ignore"):
+        np.exp(want, out=want)
+    want[want > 1] = 1.0
+    assert np.array_equal(vols["stem"].view(np.uint32), want.view(np.uint32)), "stem, log, whole grid"
+    del vols, want
+    # the config's own mode (ml_pipe_real.toml:44, log = false): every label's whole volume against the oracle
+    vols = masks2d.voxels_from_masks(masks, cams, shape, origin, vs, type="averaging", log=False)
+    plain = averaging_table(False)
+    for name in labels:
+        want = oracle_c.average(shape, origin, vs, table_views(views, plain, host[name]), nthreads=THREADS)
+        assert np.array_equal(vols[name].view(np.uint32), want.view(np.uint32)), (name, "no log, whole grid")
+        del want
+        vols[name] = None
     del vols
     # the same volumes by the schedules the engine offers (bitwise: the sum keeps the view order)
     K, R, t = _poses(views)

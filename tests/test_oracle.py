@@ -268,6 +268,41 @@ def test_oracle_over_a_ranks_planes_equals_the_whole_grid_oracle(first, stride, 
         oracle_c.carve_planes(shape, origin, vs, views, first, stride, count + 40)
 
 
+@pytest.mark.parametrize("first,stride,count", [(0, 1, 37), (1, 3, 12), (2, 4, 9), (5, 1, 11), (36, 1, 1)])
+def test_average_oracle_over_a_ranks_planes_equals_the_whole_grid_oracle(first, stride, count):
+    """The same for the average (oracle_average_view_planes: the checker of the averaging tests of a rank's planes),
+    grey masks so that every voxel's float sum depends on where its coordinates come from; a sum continued over the
+    same planes is the same planes of the whole grid's continued sum."""
+    from plant3dvision_amd import scenes
+    shape, origin, vs, views = scenes.make_scene((37, 20, 50), 7, "plant")
+    rng = np.random.default_rng(5)
+    fviews = [(K, R, t, img_as_float32(rng.integers(0, 256, m.shape, dtype=np.uint8))) for K, R, t, m in views]
+    full = oracle_c.average(shape, origin, vs, fviews, default_value=0.5, nthreads=3)
+    assert (full != 0.5).mean() > 0.5
+    got = oracle_c.average_planes(shape, origin, vs, fviews, first, stride, count, default_value=0.5, nthreads=4)
+    sl = slice(first, first + (count - 1) * stride + 1, stride)
+    assert np.array_equal(got.view(np.uint32), full[sl].view(np.uint32))
+    again = oracle_c.average_planes(shape, origin, vs, fviews[::-1], first, stride, count, nthreads=2, values=got)
+    vol = oracle_c.OracleVolume(shape, origin, vs, "averaging", 0.5)
+    for K, R, t, m in fviews + fviews[::-1]:
+        vol.process_view(K, R, t, m, nthreads=3)
+    assert np.array_equal(again.view(np.uint32), vol.values[sl].view(np.uint32))
+    with pytest.raises(RuntimeError):
+        oracle_c.average_planes(shape, origin, vs, fviews, first, stride, count + 40)
+
+
+def test_synthetic_golden_cfg1_average_digest():
+    """The average at cfg 1's size (128^3 x 12, uint8 binary masks through the log table): SHA-256 of the float32
+    C-order grid (tests/golden/make_golden.py average)."""
+    from plant3dvision_amd.cl import averaging_table
+    from tests.helpers import table_views
+    dig = json.load(open(os.path.join(GOLDEN, "synthetic_digests.json")))
+    shape, origin, vs, views = scene(128, 12, "plant")
+    vals = oracle_c.average(shape, origin, vs, table_views(views, averaging_table(True)), nthreads=8)
+    assert vals.dtype == np.float32 and (vals == 0).mean() < 0.9 and (vals < -23 * 6).any()
+    assert sha256(vals) == dig["average_plant_128_12_u8_binary_log"]["sha256_float32"]
+
+
 def test_committed_rank_digests_of_cfg4_cover_the_whole_grid():
     """tests/golden/synthetic_digests.json holds the oracle's digest of EVERY rank of 8 of the 1024^3 x 72 grid in both
     partitions; the ranks' histograms add up to the same whole grid either way (a checksum of checksums: no plane is
