@@ -400,9 +400,9 @@ class ShardedBackprojection:
         return self._engine.get_values()
 
     # -- assembling the grid ----------------------------------------------------------------
-    def _slab_tensor(self):
+    def _slab_tensor(self, on_device=True):
         import torch
-        if self._on_gpu:
+        if self._on_gpu and on_device:
             ptr = self._engine.values_device_ptr()
             self._engine.synchronize()
             typestr = "<i4" if self.dtype == np.int32 else "<f4"
@@ -416,6 +416,84 @@ class ShardedBackprojection:
 
     def _is_even(self):
         return self.shape[0] % self.world_size == 0
+
+    @property
+    def _alone(self):
+        """A group of one that does not rehearse the collectives: this rank's buffer is the whole grid."""
+        return self.world_size == 1 and not self.force_collective
+
+    def _three_state(self, wire):
+        """Carve labels that a default value of -1, 0 or 1 keeps in three states, on an engine with the host method
+        ``wire`` (``"get_values_packed"`` / ``"get_values_sparse"``): what the 2-bit and sparse wires carry."""
+        return self.dtype == np.int32 and float(self.default_value) in (-1.0, 0.0, 1.0) and hasattr(self._engine, wire)
+
+    def _wire_bytes(self, bits=None, cap=None, on_device=True):
+        """This rank's labels packed for the wire -- ``bits`` per label, or the sparse form with ``cap`` payload slots --
+        as a uint8 tensor, and torch's stream the engine was ordered before (None: host bytes)."""
+        import torch
+        if self._on_gpu and on_device:
+            # the batch's kernels first, THEN the wait for the previous collective, then the pack
+            self._engine.flush()
+            self._settle()
+            ptr, nbytes = self._engine.values_packed(bits) if cap is None else self._engine.values_sparse(cap)
+            # packed on the engine's stream; the collective and the unpack run on torch's: ordered on the device,
+            # nothing waits on the host
+            tstream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+            self._engine.order_before(tstream)
+            return torch.as_tensor(_DeviceBuffer(ptr, nbytes, "|u1"), device=f"cuda:{self.device}"), tstream
+        host = self._engine.get_values_packed(bits) if cap is None else self._engine.get_values_sparse(cap)
+        return torch.from_numpy(np.ascontiguousarray(host).view(np.uint8)), None
+
+    @staticmethod
+    def _pad(local, n):
+        """``local`` as the ``n`` elements every rank sends (the rank with the most planes sets ``n``): zeros after a
+        rank with one plane fewer; a packed tail longer than the stride is cut."""
+        if local.numel() == n:
+            return local
+        import torch
+        send = torch.zeros(n, dtype=local.dtype, device=local.device)
+        send[: min(local.numel(), n)] = local[:n]
+        return send
+
+    def _all_gather_into(self, send, recv=None):
+        """Every rank's ``send`` rank-major in ``recv`` (a new buffer unless ``recv`` has the dtype, the device and
+        the size), or ``send`` itself when ``_alone``.  gloo takes device tensors through the host."""
+        import torch
+        import torch.distributed as dist
+        if self._alone:
+            return send
+        n = send.numel() * self.world_size
+        if recv is None or getattr(recv, "dtype", None) != send.dtype or recv.numel() < n or recv.device != send.device:
+            recv = torch.empty(n, dtype=send.dtype, device=send.device)
+        recv = recv[:n]
+        staged = dist.get_backend() == "gloo" and recv.is_cuda  # rehearsal on one box: through the host
+        if staged and self.world_size == 1:  # (gloo takes 50 ms to gather a group of one: a poll that waits for nobody)
+            return recv.copy_(send.cpu())
+        into = torch.empty(recv.shape, dtype=recv.dtype) if staged else recv
+        dist.all_gather_into_tensor(into, send.cpu() if staged else send)
+        if staged:
+            recv.copy_(into)
+        return recv
+
+    def _gather_to(self, send, dst):
+        """Every rank's ``send`` rank-major in a new buffer on rank ``dst``; None on the other ranks."""
+        import torch
+        import torch.distributed as dist
+        recv = None
+        if self.rank == dst:
+            recv = torch.empty(send.numel() * self.world_size, dtype=send.dtype, device=send.device)
+        dist.gather(send, list(recv.view(self.world_size, -1).unbind(0)) if recv is not None else None, dst=dst)
+        return recv
+
+    def _hand_back(self, tstream, overlap=False):
+        """The engine's next pack must not overwrite what the collective on torch's stream ``tstream`` still reads: it
+        waits for it from now on, or (``overlap``) only right before that pack (``_settle``)."""
+        if tstream is None:
+            return
+        if overlap:
+            self._lazy_wait = tstream
+        else:
+            self._engine.order_after(tstream)
 
     def _land(self, recv, out=None):
         """Global-order grid from the all-gather's receive buffer ``[W][P][ny*nz]`` (P = the
@@ -457,65 +535,27 @@ class ShardedBackprojection:
         waits right before its next pack instead (``_settle``), so the carve of the next batch runs beside this
         batch's collective.  The caller hands alternating ``recv`` buffers if it still reads the previous grid."""
         import torch
-        import torch.distributed as dist
         if self.dtype != np.int32:
             raise ValueError("packed labels are carve labels")
         W = self.world_size
-        rank_bytes = self.packed_rank_bytes(bits)
-        tstream = None
-        if self._on_gpu:
-            # the batch's kernels first, THEN the wait for the previous collective, then the pack
-            self._engine.flush()
-            self._settle()
-            ptr, nbytes = self._engine.values_packed(bits)
-            # packed on the engine's stream; the collective and the unpack run on torch's: ordered on the device,
-            # nothing waits on the host
-            tstream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-            self._engine.order_before(tstream)
-            local = torch.as_tensor(_DeviceBuffer(ptr, nbytes, "|u1"), device=f"cuda:{self.device}")
-        else:
-            local = torch.from_numpy(np.ascontiguousarray(self._engine.get_values_packed(bits)).view(np.uint8))
-        n_out = int(np.prod(self.shape))
-        out_dtype = torch.int32 if widen else torch.int8
-        if unpack and (out is None or out.dtype != out_dtype or out.numel() < n_out):
-            out = torch.empty(n_out, dtype=out_dtype, device=local.device)
-        single = W == 1 and not self.force_collective
-        if single:
-            recv = local
-            rank_bytes = int(local.numel())
-        else:
-            if recv is None or recv.dtype != torch.uint8 or recv.numel() < rank_bytes * W:
-                recv = torch.empty(rank_bytes * W, dtype=torch.uint8, device=local.device)
-            recv = recv[: rank_bytes * W]
-            send = local
-            if local.numel() != rank_bytes:  # a rank with one plane fewer, or a tail shorter than the padding
-                send = torch.zeros(rank_bytes, dtype=torch.uint8, device=local.device)
-                send[: min(local.numel(), rank_bytes)] = local[:rank_bytes]
-            if dist.get_backend() == "gloo" and recv.is_cuda:  # rehearsal on one box: through the host
-                if W == 1:  # (gloo takes 50 ms to gather a group of one: a poll that waits for nobody)
-                    hrecv = send.cpu()
-                else:
-                    hrecv = torch.empty(recv.shape, dtype=recv.dtype)
-                    dist.all_gather_into_tensor(hrecv, send.cpu())
-                recv.copy_(hrecv)
-            else:
-                dist.all_gather_into_tensor(recv, send)
+        local, tstream = self._wire_bytes(bits=bits)
+        rank_bytes = int(local.numel()) if self._alone else self.packed_rank_bytes(bits)
+        recv = self._all_gather_into(self._pad(local, rank_bytes), recv)
         if not unpack:
             # the packed planes as they are (a PackedGrid): vol2pcd reads them directly.  A single rank's buffer is
             # the engine's own and is overwritten by its next pack: copied, it is 1/16 of the grid
-            if single and recv.is_cuda:
+            if self._alone and recv.is_cuda:
                 recv = recv.clone()
-            if tstream is not None:
-                if overlap:
-                    self._lazy_wait = tstream  # the engine waits before its next pack, not here
-                else:
-                    self._engine.order_after(tstream)
+            self._hand_back(tstream, overlap)
             return PackedGrid(recv, rank_bytes, W, self.partition, self.shape, bits, self.device)
+        n_out = int(np.prod(self.shape))
+        out_dtype = torch.int32 if widen else torch.int8
+        if out is None or out.dtype != out_dtype or out.numel() < n_out:
+            out = torch.empty(n_out, dtype=out_dtype, device=local.device)
         if recv.is_cuda:
             nat.unpack_labels(self.device, torch.cuda.current_stream(recv.device).cuda_stream, recv.data_ptr(), rank_bytes, W,
                               self.partition, self.shape, bits, out.data_ptr(), 4 if widen else 1)
-            if tstream is not None:  # the engine's next pack must not overwrite what the collective still reads
-                self._engine.order_after(tstream)
+            self._hand_back(tstream)
         else:
             if self._unpack_fn is None:
                 raise RuntimeError("host tensors: no HIP unpack (the product path keeps the labels on the device)")
@@ -578,48 +618,15 @@ class ShardedBackprojection:
             return grid.unpack(widen=widen, out=out) if unpack else grid
 
     def _all_gather_sparse_torch(self, cap, stride, recv, overlap):
-        import torch
-        import torch.distributed as dist
-        W = self.world_size
-        tstream = None
-        if self._on_gpu:
-            self._engine.flush()
-            self._settle()
-            ptr, nbytes = self._engine.values_sparse(cap)
-            tstream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-            self._engine.order_before(tstream)
-            local = torch.as_tensor(_DeviceBuffer(ptr, nbytes, "|u1"), device=f"cuda:{self.device}")
-        else:
-            local = torch.from_numpy(np.ascontiguousarray(self._engine.get_values_sparse(cap)).view(np.uint8))
-        single = W == 1 and not self.force_collective
-        send = local
-        if local.numel() != stride:  # a rank with one plane fewer
-            send = torch.zeros(stride, dtype=torch.uint8, device=local.device)
-            send[: local.numel()] = local
-        if single:
-            recv = send.clone() if send.is_cuda else send
-        else:
-            if recv is None or not hasattr(recv, "dtype") or recv.dtype != torch.uint8 or recv.numel() < stride * W \
-                    or recv.device != local.device:
-                recv = torch.empty(stride * W, dtype=torch.uint8, device=local.device)
-            recv = recv[: stride * W]
-            if dist.get_backend() == "gloo" and recv.is_cuda:  # rehearsal on one box: through the host
-                if W == 1:  # (gloo takes 50 ms to gather a group of one: a poll that waits for nobody)
-                    hrecv = send.cpu()
-                else:
-                    hrecv = torch.empty(recv.shape, dtype=recv.dtype)
-                    dist.all_gather_into_tensor(hrecv, send.cpu())
-                recv.copy_(hrecv)
-            else:
-                dist.all_gather_into_tensor(recv, send)
-        if tstream is not None:
-            # two send buffers alternate inside the engine: the next pack does not touch the one this collective reads,
-            # the one after it does -- the engine waits then (lazily), or now
-            if overlap:
-                self._lazy_wait = tstream
-            else:
-                self._engine.order_after(tstream)
-        return SparseGrid(recv, stride, W, self.shape, self.device, cap, on_gpu=bool(recv.is_cuda), engine=self._engine)
+        local, tstream = self._wire_bytes(cap=cap)
+        recv = self._all_gather_into(self._pad(local, stride), recv)
+        if self._alone and recv.is_cuda:
+            recv = recv.clone()  # (the engine's own buffer, overwritten by its next pack)
+        # two send buffers alternate inside the engine: the next pack does not touch the one this collective reads,
+        # the one after it does -- the engine waits then (lazily), or now
+        self._hand_back(tstream, overlap)
+        return SparseGrid(recv, stride, self.world_size, self.shape, self.device, cap, on_gpu=bool(recv.is_cuda),
+                          engine=self._engine)
 
     def all_gather(self, compress=False, widen=True, recv=None, out=None, unpack=True, overlap=False, check=True):
         """Full grid on every rank (torch tensor on the slab's device), by all-gather.
@@ -650,8 +657,6 @@ class ShardedBackprojection:
                 grid = self._all_gather_sparse(widen, recv, None, unpack=False, overlap=False, check=True)
                 return torch.from_numpy(grid.to_host().astype(np.int32 if widen else np.int8))
             return self._all_gather_sparse(widen, recv, out, unpack, overlap, check and not overlap)
-        import torch
-        import torch.distributed as dist
         if compress in ("2bit", "1bit"):
             if not unpack and not self._on_gpu:
                 # (a PackedGrid is a device object -- unpack() and vol2pcd read it with HIP kernels)
@@ -659,6 +664,11 @@ class ShardedBackprojection:
             return self._all_gather_packed(2 if compress == "2bit" else 1, widen, recv, out, unpack, overlap)
         if not unpack:
             raise ValueError("unpack=False is for the packed forms (compress='2bit' / '1bit')")
+        return self._all_gather_dense(compress, widen, recv, out)
+
+    def _all_gather_dense(self, compress, widen, recv, out):
+        """The planes in the engine's dtype over the wire, or carve labels as int8 (``compress``)."""
+        import torch
         self._settle()
         local = self._slab_tensor()
         if compress:
@@ -667,27 +677,12 @@ class ShardedBackprojection:
             if not -128 <= int(self.default_value) <= 127:
                 raise ValueError("default_value does not fit int8")
             local = local.to(torch.int8)
-        if self.world_size == 1 and not self.force_collective:
+        if self._alone:
             full = local.reshape(self.shape)
-            return full.to(torch.int32) if compress and widen else full
-        pad = self._planes_max() * self.shape[1] * self.shape[2]
-        if recv is None:
-            recv = torch.empty(pad * self.world_size, dtype=local.dtype, device=local.device)
-        send = local
-        if local.numel() != pad:  # a rank with one plane fewer
-            send = torch.zeros(pad, dtype=local.dtype, device=local.device)
-            send[: local.numel()] = local
-        staged = dist.get_backend() == "gloo" and recv.is_cuda  # rehearsal on one box: through the host
-        if staged:
-            hrecv = torch.empty(recv.shape, dtype=recv.dtype)
-            dist.all_gather_into_tensor(hrecv, send.cpu())
-            recv.copy_(hrecv)
         else:
-            dist.all_gather_into_tensor(recv, send)
-        full = self._land(recv, out)
-        if compress and widen:
-            full = full.to(torch.int32)
-        return full
+            send = self._pad(local, self._planes_max() * self.shape[1] * self.shape[2])
+            full = self._land(self._all_gather_into(send, recv), out)
+        return full.to(torch.int32) if compress and widen else full
 
     def all_reduce(self):
         """Full grid on every rank by summing zero-padded full-size buffers (the north
@@ -700,7 +695,7 @@ class ShardedBackprojection:
                            device=local.device)
         pl = self.planes
         full[pl.start:pl.stop:pl.step] = local.reshape(len(pl), *self.shape[1:])
-        if self.world_size > 1 or self.force_collective:
+        if not self._alone:
             if dist.get_backend() == "gloo" and full.is_cuda:
                 h = full.cpu()
                 dist.all_reduce(h, op=dist.ReduceOp.SUM)
@@ -713,33 +708,25 @@ class ShardedBackprojection:
         """Full grid as a NumPy array of the reference's dtype on rank ``dst`` (None elsewhere) --
         what ``get_values`` (cl.py:229-232) hands a ``Voxels`` run.
 
-        RCCL: the slabs travel to ``dst``'s GPU over xGMI (``dist.gather`` of tensors; carve labels
-        as int8 unless ``compress=False``), are put in global order there by the same strided copy
-        as ``all_gather``, and cross PCIe once.  gloo (CPU rehearsal and tests): each rank copies
-        its slab to the host and the host tensors are gathered.
-        Carve labels of a default value of -1 / 0 / 1 take the 2-bit wire instead (``_gather_to_host_2bit``);
+        Carve labels of a default value of -1 / 0 / 1 take the sparse wire of ``all_gather`` by default when there are
+        collectives to run: every rank ends with every rank's (small) buffer, ``dst`` copies it over PCIe once and the
+        host pool widens it and puts it in global order.  compress="2bit": the 2-bit wire (``_gather_to_host_2bit``).
+        Otherwise the planes travel as int8 unless ``compress=False`` (``_gather_to_host_dense``).
         ``out``: an int32 array of the grid's size to widen into on ``dst`` -- one whose pages have been touched
         takes 512^3 labels in ~4 ms, a fresh ``np.empty`` ~30 (first-touch page faults, not the transfer)."""
-        if compress is None and (self.world_size > 1 or self.force_collective) and self.dtype == np.int32 \
-                and float(self.default_value) in (-1.0, 0.0, 1.0) and hasattr(self._engine, "get_values_sparse"):
+        if compress is None and not self._alone and self._three_state("get_values_sparse"):
             compress = "sparse"  # (round 6: the default wire of a sharded run's labels)
         if compress == "sparse":
-            # (round 6) codes + mixed bricks only over the collective (every rank ends with every rank's buffer: they
-            # are small), ONE PCIe copy on ``dst``, widened and put in global order by the host pool
-            if not (self.dtype == np.int32 and float(self.default_value) in (-1.0, 0.0, 1.0)
-                    and hasattr(self._engine, "get_values_sparse")):
+            if not self._three_state("get_values_sparse"):
                 raise ValueError("the sparse wire carries carve labels of a default_value of -1, 0 or 1")
             self._settle()
             grid = self._all_gather_sparse(True, None, None, unpack=False, overlap=False, check=True)
             return grid.to_host(out=out) if self.rank == dst else None
-        import torch
-        import torch.distributed as dist
         self._settle()
-        two_bit = (self.dtype == np.int32 and float(self.default_value) in (-1.0, 0.0, 1.0)
-                   and compress in (None, "2bit") and hasattr(self._engine, "get_values_packed"))
+        two_bit = compress in (None, "2bit") and self._three_state("get_values_packed")
         if compress == "2bit" and not two_bit:
             raise ValueError("the 2-bit wire carries carve labels of a default_value of -1, 0 or 1")
-        if self.world_size == 1 and not self.force_collective:
+        if self._alone:
             if two_bit and self._on_gpu and int(np.prod(self.shape)) >= (1 << 24):
                 if out is None or out.dtype != np.int32 or out.size != int(np.prod(self.shape)) or not out.flags["C_CONTIGUOUS"]:
                     out = np.empty(self.shape, dtype=np.int32)
@@ -748,23 +735,21 @@ class ShardedBackprojection:
             return np.ascontiguousarray(self.get_local()).reshape(self.shape)
         if two_bit:
             return self._gather_to_host_2bit(dst, out)
+        return self._gather_to_host_dense(dst, compress)
+
+    def _gather_to_host_dense(self, dst, compress):
+        """The planes to ``dst``'s GPU (RCCL: tensors over xGMI; gloo: through the hosts), as int8 when ``compress`` (by
+        default for carve labels that fit), put in global order there by the strided copy of ``all_gather``, and one
+        PCIe copy."""
+        import torch
+        import torch.distributed as dist
         if compress is None:
             compress = self.dtype == np.int32 and -128 <= int(self.default_value) <= 127
-        pad = self._planes_max() * self.shape[1] * self.shape[2]
-        on_device = self._on_gpu and dist.get_backend() != "gloo"
-        local = self._slab_tensor() if on_device else torch.from_numpy(
-            np.ascontiguousarray(self.get_local()).reshape(-1))
+        local = self._slab_tensor(on_device=dist.get_backend() != "gloo")
         if compress:
             local = local.to(torch.int8)
-        send = local
-        if local.numel() != pad:
-            send = torch.zeros(pad, dtype=local.dtype, device=local.device)
-            send[: local.numel()] = local
-        recv = None
-        if self.rank == dst:
-            recv = torch.empty(pad * self.world_size, dtype=send.dtype, device=send.device)
-        dist.gather(send, list(recv.view(self.world_size, pad).unbind(0)) if recv is not None else None, dst=dst)
-        if self.rank != dst:
+        recv = self._gather_to(self._pad(local, self._planes_max() * self.shape[1] * self.shape[2]), dst)
+        if recv is None:
             return None
         full = self._land(recv).cpu().numpy()
         return full.astype(self.dtype) if full.dtype != self.dtype else full
@@ -774,37 +759,16 @@ class ShardedBackprojection:
         (``sc_values_packed``), gathered to ``dst``'s GPU (RCCL; gloo: through the hosts), ONE PCIe copy of 1/16 of
         the grid's bytes, and the host pool widens and interleaves the planes into the int32 grid of cl.py:229-232
         (``sc_widen_labels2_ranks``)."""
-        import torch
         import torch.distributed as dist
-        W = self.world_size
         rank_bytes = self.packed_rank_bytes(2)
-        on_device = self._on_gpu and dist.get_backend() != "gloo"
-        if self._on_gpu:
-            ptr, nbytes = self._engine.values_packed(2)
-            if on_device:
-                tstream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-                self._engine.order_before(tstream)
-                local = torch.as_tensor(_DeviceBuffer(ptr, nbytes, "|u1"), device=f"cuda:{self.device}")
-            else:
-                local = torch.from_numpy(np.ascontiguousarray(self._engine.get_values_packed(2)).view(np.uint8))
-        else:
-            local = torch.from_numpy(np.ascontiguousarray(self._engine.get_values_packed(2)).view(np.uint8))
-        send = local
-        if local.numel() != rank_bytes:
-            send = torch.zeros(rank_bytes, dtype=torch.uint8, device=local.device)
-            send[: min(local.numel(), rank_bytes)] = local[:rank_bytes]
-        recv = None
-        if self.rank == dst:
-            recv = torch.empty(rank_bytes * W, dtype=torch.uint8, device=send.device)
-        dist.gather(send, list(recv.view(W, rank_bytes).unbind(0)) if recv is not None else None, dst=dst)
-        if on_device:
-            self._engine.order_after(tstream)  # the engine's next pack waits for the collective's read
-        if self.rank != dst:
+        local, tstream = self._wire_bytes(bits=2, on_device=dist.get_backend() != "gloo")
+        recv = self._gather_to(self._pad(local, rank_bytes), dst)
+        self._hand_back(tstream)  # the engine's next pack waits for the collective's read
+        if recv is None:
             return None
-        host = recv.cpu().numpy() if recv.is_cuda else recv.numpy()
         if out is not None and (out.dtype != np.int32 or out.size != int(np.prod(self.shape)) or not out.flags["C_CONTIGUOUS"]):
             out = None
-        return nat.widen_labels2_ranks(host, rank_bytes, W, self.partition, self.shape, out=out)
+        return nat.widen_labels2_ranks(recv.cpu().numpy(), rank_bytes, self.world_size, self.partition, self.shape, out=out)
 
     def close(self):
         if self._engine is not None:

@@ -94,6 +94,9 @@ def _worker(rank, world, port, shape, mode, q, partition="cyclic"):
             res["ags"] = ps.numpy()
             res["agsn"] = sb.all_gather(compress="sparse", widen=False).numpy()
             res["hosts"] = sb.gather_to_host(dst=0, compress="sparse")
+            # the dense wires to one rank's host: 2 bits per label, and int8
+            res["host2"] = sb.gather_to_host(dst=0, compress="2bit")
+            res["host8"] = sb.gather_to_host(dst=0, compress=True)
             # a capacity too small for some rank: every rank sees the same headers and gathers again with more slots
             sb._sparse_cap = 16
             res["ags_small_cap"] = sb.all_gather(compress="sparse").numpy()
@@ -150,10 +153,11 @@ def test_gloo_sharded_equals_single(world, shape, mode, partition):
             assert np.array_equal(res["ags"], want) and res["agsn"].dtype == np.int8 and np.array_equal(res["agsn"], want)
             assert np.array_equal(res["ags_small_cap"], want) and res["cap_after"] >= 16
             assert np.array_equal(res["ags_twin"], want)
-            if res["rank"] == 0:
-                assert res["hosts"].dtype == np.int32 and np.array_equal(res["hosts"], want)
-            else:
-                assert res["hosts"] is None
+            for key in ("hosts", "host2", "host8"):
+                if res["rank"] == 0:
+                    assert res[key].dtype == np.int32 and np.array_equal(res[key], want), key
+                else:
+                    assert res[key] is None, key
             if res["rank"] == world - 1:
                 assert res["host32"].dtype == np.int32 and np.array_equal(res["host32"], want)
             else:
@@ -226,7 +230,8 @@ def _gpu_worker(rank, world, port, shape, partition, q):
         assert len(ref.points) > 0
         q.put({"rank": rank, "ag": full.cpu().numpy(), "ag8n": narrow.cpu().numpy(),
                "ag2n": p2.cpu().numpy(), "ag2": p2w.cpu().numpy(), "ag1": p1.cpu().numpy(),
-               "ar": sb.all_reduce().cpu().numpy(), "host": sb.gather_to_host(dst=0)})
+               "ar": sb.all_reduce().cpu().numpy(), "host": sb.gather_to_host(dst=0),
+               "host2": sb.gather_to_host(dst=0, compress="2bit")})
         sb.close()
     finally:
         dist.barrier()
@@ -255,10 +260,11 @@ def test_two_ranks_over_hip_engines_sharing_the_gpu(gpu_device, partition, shape
         assert res["ag8n"].dtype == np.int8 and np.array_equal(res["ag8n"], want)
         assert np.array_equal(res["ag2n"], want) and res["ag2"].dtype == np.int32 and np.array_equal(res["ag2"], want)
         assert np.array_equal(res["ag1"], (want == 1).astype(np.int8))
-        if res["rank"] == 0:
-            assert res["host"].dtype == np.int32 and np.array_equal(res["host"], want)
-        else:
-            assert res["host"] is None
+        for key in ("host", "host2"):
+            if res["rank"] == 0:
+                assert res[key].dtype == np.int32 and np.array_equal(res[key], want), key
+            else:
+                assert res[key] is None, key
 
 
 @pytest.mark.gpu
@@ -322,8 +328,10 @@ def test_collectives_through_rccl_with_a_process_group_of_one(gpu_device):
             p1 = sb.all_gather(compress="1bit", widen=False)
             assert np.array_equal(p1.cpu().numpy(), (want == 1).astype(np.int8))
             assert np.array_equal(sb.all_reduce().cpu().numpy(), want)
-            host = sb.gather_to_host(dst=0)  # the 2-bit wire + sc_widen_labels2_ranks
+            host = sb.gather_to_host(dst=0)  # the sparse wire + sc_widen_sparse_ranks
             assert host.dtype == np.int32 and np.array_equal(host, want)
+            host2 = sb.gather_to_host(dst=0, compress="2bit")  # the 2-bit wire + sc_widen_labels2_ranks
+            assert host2.dtype == np.int32 and np.array_equal(host2, want)
             host8 = sb.gather_to_host(dst=0, compress=True)  # the int8 route of rounds 2-3
             assert host8.dtype == np.int32 and np.array_equal(host8, want)
             from plant3dvision_amd import proc3d
