@@ -482,6 +482,44 @@ int sc_label_points(const double *points, int64_t P, int L, int V, const double 
                     double *scores_out, int32_t *labels_out);
 const char *sc_label_points_last_error(void);
 
+/*
+ * The geometric pipeline's mask producer: plant3dvision/tasks/proc2d.py::Masks.f (:224-249) over
+ * plant3dvision/proc2d.py (:69-220) on the GPU.  rgb: uint8 [V][H][W][3] (R, G, B); per picture, independently:
+ * imin / imax over all its bytes, x' = (x - imin) / (imax - imin) (min(x, 1) for a constant picture), then
+ * linear  f = (c0 r' + c1 g') + c2 b'  or excess_green  s = ((r' + g') + b') + 1e-9, f = ((2 (g'/s)) - (r'/s)) - (b'/s),
+ * all in IEEE binary64 without contraction; mask = f > threshold; `nsteps` (0..32) 3x3 dilation steps, one after the
+ * other, out[p] = OR over the footprint's offsets o of in[p - o], outside the picture is background (the expanded
+ * series of masks2d.disk_series(n)); masks_out: uint8 [V][H][W] of 0 / 255.  coefs are read for both filters and
+ * used by the linear one.  Restates skimage's rescale_intensity from its source: parity unpinned.
+ *
+ * Device pointers on both sides (rgb_on_device, out_on_device != 0): the work is enqueued on hip_stream (NULL = the
+ * legacy default stream) and the call returns without waiting, so sc_order_after(engine, hip_stream) +
+ * sc_process_views_device(..., SC_MASK_U8) consumes the masks without a host wait.  A host pointer on either side
+ * is staged by the library and the call returns when masks_out is complete.  ranges_out (host, [V][2] = imin, imax;
+ * may be NULL) is a diagnostic and makes the call wait.
+ * The work buffers (1 bit per pixel, 2 KiB per picture) are the library's, one set per device, kept between calls
+ * and given back by sc_masks_release.  Every call is ordered on the device behind the previous call of that device
+ * with an event, whatever the two streams: a call never writes into buffers an earlier one may still be reading.
+ * Arguments are judged before any device call: V, H, W >= 1, 3 H W < 2^31, 0 <= nsteps <= 32, step ids 0..5,
+ * filter 0..1, finite coefficients and threshold, non-NULL rgb / coefs / masks_out.
+ */
+#define SC_FILTER_LINEAR 0
+#define SC_FILTER_EXCESS_GREEN 1
+/* one 3x3 dilation step each, the footprints of masks2d._FOOTPRINTS */
+#define SC_FOOT_T0 0
+#define SC_FOOT_T90 1
+#define SC_FOOT_T180 2
+#define SC_FOOT_T270 3
+#define SC_FOOT_DIAMOND 4
+#define SC_FOOT_SQUARE 5
+int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, int filter, const double coefs[3],
+                      double threshold, const uint8_t *steps, int nsteps, int device, void *hip_stream,
+                      void *masks_out, int out_on_device, int32_t *ranges_out /* [V][2] imin, imax; may be NULL */);
+const char *sc_masks_last_error(void);
+/* Gives back the work buffers sc_masks_from_rgb keeps (after waiting for the work that uses them).  The caller's
+ * current HIP device is left as it was. */
+void sc_masks_release(void);
+
 /* Page-locked host memory for the read-back of sc_get_values (no reference counterpart: the
  * reference's values_h is a pageable NumPy array, cl.py:173).  A 512 MiB volume reads back in
  * ~10 ms into such a buffer against ~50 ms into pageable memory, but allocating it takes ~0.1 s

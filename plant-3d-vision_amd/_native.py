@@ -46,6 +46,8 @@ SC_OPT_BULK_ADAPT = SC_OPT_BULK_FLOOR  # deprecated name of key 35 (0 still mean
 SC_OPT_UNIT_CULL, SC_OPT_LIST_CAP, SC_OPT_HOST_PACK, SC_OPT_HOST_THREADS, SC_OPT_LDS_TILES, SC_OPT_BULK_LIVE, SC_OPT_SAFE_KERNELS = 37, 38, 39, 40, 41, 42, 43
 SC_OPT_DENSE_EXTRA = 44
 SC_OPT_SPEC_SHARE, SC_OPT_SPEC_BLOCKS, SC_OPT_LATE_ROAD = 45, 46, 47
+SC_FILTER_LINEAR, SC_FILTER_EXCESS_GREEN = 0, 1
+SC_FOOT = {"t0": 0, "t90": 1, "t180": 2, "t270": 3, "diamond": 4, "square": 5}  # SC_FOOT_*: names of masks2d._FOOTPRINTS
 
 # name -> (restype, [argtypes]); 'p' pointer, 'i' int, 'q' int64, 'f' float, 's' const char*
 _SIGNATURES = {
@@ -124,6 +126,9 @@ _SIGNATURES = {
     "sc_free_host": ("v", ["p"]),
     "sc_label_points": ("i", ["p", "q", "i", "i", "p", "p", "p", "p", "i", "i", "i", "i", "p", "p"]),
     "sc_label_points_last_error": ("s", []),
+    "sc_masks_from_rgb": ("i", ["p", "i", "i", "i", "i", "i", "p", "d", "p", "i", "i", "p", "p", "i", "p"]),
+    "sc_masks_last_error": ("s", []),
+    "sc_masks_release": ("v", []),
     "sc_create_sharded": ("i", ["p", "q", "q", "q", "p", "f", "i", "f", "p", "i", "i"]),
     "sc_group_destroy": ("v", ["p"]),
     "sc_group_size": ("i", ["p"]),

@@ -1,0 +1,81 @@
+"""The ``Masks`` task logic of the reference (``plant3dvision/tasks/proc2d.py:146-249``) around the device mask
+producer (``proc2d.masks_from_images``).
+
+As with ``tasks/cl.py::voxels_run``, the task's *logic* -- read every picture, filter, threshold, dilate, the
+output metadata -- is a plain function, ``masks_run``, without luigi / plantdb.  The reference runs ``Masks.f`` file
+by file; here pictures of equal size go to the device as one batch (every picture still has its own range).
+INTEGRATION.md has the lines a maintainer of the reference puts into ``Masks.run``.
+"""
+import logging
+
+import numpy as np
+
+logger = logging.getLogger(__name__)
+
+#: parameter defaults of the reference task (tasks/proc2d.py:207-211)
+MASKS_DEFAULTS = dict(type="linear", parameters=[0, 1, 0], threshold=0.3, dilation=0)
+
+
+def _plain_query(query):
+    """The ``query`` dictionary as the reference stores it in the metadata (its ``jsonify``, utils.py:38-64):
+    NumPy arrays and numbers as plain Python ones, an empty sequence as ``'None'``."""
+    out = {}
+    for key, val in dict(query).items():
+        if isinstance(val, np.ndarray):
+            val = val.tolist()
+        if hasattr(val, "__iter__"):
+            if len(val) == 0:
+                out[key] = "None"
+            elif isinstance(val, (list, tuple)) and isinstance(val[0], (float, np.floating)):
+                out[key] = [float(x) for x in val]
+            elif isinstance(val, (list, tuple)) and isinstance(val[0], np.integer):
+                out[key] = [int(x) for x in val]
+            else:
+                out[key] = val
+        elif isinstance(val, (float, np.floating)):
+            out[key] = float(val)
+        elif isinstance(val, np.integer):
+            out[key] = int(val)
+        else:
+            out[key] = val
+    return out
+
+
+def masks_metadata(type, parameters, threshold, dilation, query=None, upstream_task="Undistorted"):
+    """The metadata ``Masks.f`` sets on every mask file (tasks/proc2d.py:242-248)."""
+    md = {"upstream_task": str(upstream_task), "filter": str(type), "threshold": threshold, "dilation": dilation}
+    if type == "linear":
+        md["linear_coeff"] = list(parameters)
+    if query is not None and dict(query) != {}:
+        md["query"] = _plain_query(query)
+    return {"Masks": md}
+
+
+def masks_run(image_files, type="linear", parameters=(0, 1, 0), threshold=0.3, dilation=0, query=None,
+              upstream_task="Undistorted", masks_fn=None):
+    """The ``Masks.f`` loop without luigi / plantdb (tasks/proc2d.py:224-249).
+
+    image_files : list of file-like objects (``.id``; pixels via ``cl.read_image``), uint8 RGB pictures.
+    masks_fn : ``masks_from_images`` by default; an argument only, the CPU tests pass a function of theirs.
+
+    Returns ``[(id, mask, metadata), ...]`` in input order: ``mask`` the uint8 0 / 255 picture the reference
+    writes (:237-240), ``metadata`` what it sets on the file (:242-248).
+    """
+    if type not in ("linear", "excess_green"):
+        raise Exception(f"Unknown masking type '{type}'!")  # tasks/proc2d.py:222
+    if masks_fn is None:  # the product: the HIP kernels
+        from ..proc2d import masks_from_images as masks_fn
+    from ..cl import read_image
+    logger.info(f"Processing a list of {len(image_files)} image files...")
+    pictures = [np.asarray(read_image(fi)) for fi in image_files]
+    groups = {}  # pictures of one size make one batch, in input order
+    for q, img in enumerate(pictures):
+        groups.setdefault(img.shape, []).append(q)
+    masks = [None] * len(pictures)
+    for shape, members in groups.items():
+        batch = np.stack([pictures[q] for q in members])
+        out = masks_fn(batch, type=type, parameters=list(parameters), threshold=threshold, dilation=dilation)
+        for k, q in enumerate(members):
+            masks[q] = out[k]
+    md = masks_metadata(type, parameters, threshold, dilation, query, upstream_task)
+    return [(fi.id, masks[q], {"Masks": dict(md["Masks"])}) for q, fi in enumerate(image_files)]
