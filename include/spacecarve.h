@@ -520,6 +520,34 @@ const char *sc_masks_last_error(void);
  * current HIP device is left as it was. */
 void sc_masks_release(void);
 
+/*
+ * The clustering of OrganSegmentation (plant3dvision/tasks/proc3d.py:419-521): what open3d's
+ * cluster_dbscan(eps, min_points) computes for one cloud, on the GPU.  points: float64 [P][3]; labels_out: int32 [P],
+ * cluster ids from 0, noise -1; nclusters_out (host, may be NULL): the number of clusters.  The rules, order-free:
+ *   d2(i, j) = ((dx dx) + (dy dy)) + (dz dz) in IEEE binary64 without contraction; j is a neighbour of i iff
+ *   d2(i, j) < eps * eps (strict, the product rounded once, i its own neighbour); i is core iff it has at least
+ *   min_points neighbours (0 behaves as 1); clusters are the connected components of the core points, numbered by the
+ *   rank of their smallest point index; a non-core point with core neighbours takes the smallest id among them;
+ *   every other point is noise.
+ * Restates open3d's sequential loop, which cannot be run here: parity unpinned.
+ *
+ * points_on_device / labels_on_device != 0: device pointers on `device`, read and written on hip_stream (NULL = the
+ * legacy default stream).  The call waits once for its first kernel (which looks for non-finite coordinates) and,
+ * when nclusters_out or a host pointer is given, for its last; with device pointers and nclusters_out == NULL it
+ * returns with the remaining work enqueued.  The work buffers (about 100 bytes per point) are the library's, one set
+ * per device, kept between calls, ordered across streams as sc_masks_from_rgb's are, given back by sc_dbscan_release.
+ * Judged before any device call (SC_ERR_INVALID): NULL points / labels_out, P < 0 or P >= 2^31, eps not finite or
+ * <= 0 (or eps * eps not a normal number), min_points < 0, a non-finite coordinate in host points -- a documented
+ * deviation from open3d, which goes on computing.  In device points the first kernel finds it: SC_ERR_INVALID as
+ * well, labels_out untouched.  P == 0 is SC_OK with 0 clusters and no device call.
+ */
+int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps, int64_t min_points, int device,
+              int32_t *labels_out, int labels_on_device, int32_t *nclusters_out, void *hip_stream);
+const char *sc_dbscan_last_error(void);
+/* Gives back the work buffers sc_dbscan keeps (after waiting for the work that uses them).  The caller's current
+ * HIP device is left as it was. */
+void sc_dbscan_release(void);
+
 /* Page-locked host memory for the read-back of sc_get_values (no reference counterpart: the
  * reference's values_h is a pageable NumPy array, cl.py:173).  A 512 MiB volume reads back in
  * ~10 ms into such a buffer against ~50 ms into pageable memory, but allocating it takes ~0.1 s

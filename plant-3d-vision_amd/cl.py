@@ -590,5 +590,6 @@ class Backprojection(object):
             self._engine = None
             try:  # the consumer's cached device buffers go with the volume they were sized for
                 nat.backend().call("sc_vol2pcd_release")
+                nat.backend().call("sc_dbscan_release")
             except Exception:
                 pass

@@ -1,0 +1,436 @@
+// dbscan.hip -- the clustering of OrganSegmentation on the GPU.
+//
+// Replaces open3d's `cluster_dbscan(eps, min_points)` as plant3dvision/tasks/proc3d.py::OrganSegmentation.run
+// (:419-521) calls it, for one cloud of P float64 points.  PARITY UNPINNED: open3d is not available,
+// this restates what its sequential loop computes in an order-free form:
+//   1. d2(i, j) = ((dx dx) + (dy dy)) + (dz dz) in IEEE binary64 without contraction (-ffp-contract=off);
+//   2. j is a neighbour of i iff d2(i, j) < eps * eps (strict; the product rounded once; i is its own neighbour);
+//   3. i is core iff it has at least min_points neighbours;
+//   4. clusters = connected components of the core points under 2; id = rank of the component's smallest index;
+//   5. a non-core point with core neighbours takes the smallest id among them;  6. every other point is -1.
+//
+// No neighbour list is stored: every pass finds its candidates again in a uniform grid of cells (points sorted by a
+// hash of their cell, a counting sort) and decides each pair with rules 1 and 2 alone.  Launches per call: finite,
+// histogram, [scan], scatter, core, link, flatten, border, [scan], labels.  The link launch is the only one in
+// which blocks exchange data (the parent array): every access to it there is a relaxed agent-scope atomic.
+// Stand-alone unit: nothing shared with the carve's engine.
+
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+
+#include "spacecarve.h"
+
+namespace {
+
+constexpr int kB = 256;
+
+thread_local char g_derr[256];
+int fail_d(int code, const char *msg) {
+    strncpy(g_derr, msg, sizeof g_derr - 1);
+    g_derr[sizeof g_derr - 1] = 0;
+    return code;
+}
+
+// ---- the cell grid ---------------------------------------------------------------------------------------------
+// Cell of a coordinate: c = floor(clamp(q, -2^40, 2^40)) with q = fl(fl(x - a) / edge), a = the coordinate of point
+// 0 (the anchor; any finite number would do) and edge = fl(eps * kEdgeFactor), kEdgeFactor = 1 + 2^-8.
+//
+// Why the 27 cells around a point's own hold every neighbour.  Let d2(i, j) < eps2 = fl(eps * eps) as computed.
+// Rounded sums of non-negative terms never fall below a term, so fl(dx dx) < eps2 for dx = fl(xi - xj); eps2 is a
+// normal number (checked by the entry; a product that underflowed is below it anyway), hence |dx| < eps (1 + 2^-52),
+// and |xi - xj| <= |dx| (1 + 2^-52) < eps (1 + 2^-50).  In exact arithmetic the two quotients r = (x - a) / edge
+// then differ by less than (1 + 2^-50) / ((1 + 2^-8)(1 - 2^-53)) < 1 - 2^-9.  q carries two roundings:
+// |q - r| <= |r| 2^-52 (a quotient that underflows is off by less than 2^-1074), at most 2^-11 while |r| <= 2^41.
+// So if both |q| are below 2^41 they differ by less than 1 - 2^-9 + 2^-10 < 1, their floors by at most 1, and the
+// clamp, being monotone, never separates what was adjacent.  If one |q| is 2^41 or more, the other is beyond
+// 2^41 - 2 > 2^40 on the same side and both cells are that side's clamp.  (x - a may overflow to an infinity: the
+// clamp again; it is never NaN for finite x.)  The clamp costs time only: what lies further than 2^40 cells from
+// point 0 shares one layer of cells per axis and side.
+//
+// Cells are 3 x 41 bits and a sign: points are binned by a 64-bit hash of them, reduced to a power-of-two table, and
+// carry the low 32 bits of their cell.  A bucket may hold several cells: a candidate is looked at only if the low
+// 32 bits of its cell are those of the cell asked for.  The 27 cells asked for differ from one another by at most 2
+// per axis, so no two of them share their low bits: a point of the 27 cells is visited exactly once, a stray point
+// that collides in hash and low bits at most once, and only rule 2 decides what a visited pair is.
+constexpr double kEdgeFactor = 1.0 + 1.0 / 256.0;
+constexpr double kCellClamp = 1099511627776.0;  // 2^40
+constexpr int64_t kCellMax = (int64_t)1 << 40;
+
+struct Grid {
+    double ax, ay, az, edge, eps2;
+    uint32_t mask;  // buckets - 1
+};
+
+__device__ __forceinline__ int64_t cell_of(double x, double a, double edge) {
+    const double q = (x - a) / edge;
+    return (int64_t)floor(fmax(fmin(q, kCellClamp), -kCellClamp));
+}
+
+__device__ __forceinline__ uint32_t bucket_of(int64_t cx, int64_t cy, int64_t cz, uint32_t mask) {
+    unsigned long long h = (unsigned long long)cx * 0x9E3779B97F4A7C15ull ^ (unsigned long long)cy * 0xC2B2AE3D27D4EB4Full ^
+                           (unsigned long long)cz * 0x165667B19E3779F9ull;
+    h ^= h >> 32;
+    h *= 0xD6E8FEB86659FD93ull;
+    h ^= h >> 32;
+    return (uint32_t)h & mask;
+}
+
+__device__ __forceinline__ double dist2(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    return ((dx * dx) + (dy * dy)) + (dz * dz);
+}
+
+// Calls f(t, original index of t) for every sorted slot t whose point is a neighbour (rules 1, 2) of the point at
+// (x, y, z), itself included; f returns true to stop.
+template <class F>
+__device__ __forceinline__ void for_each_neighbour(const Grid &g, const uint32_t *__restrict__ start,
+                                                   const uint4 *__restrict__ scell, const double *__restrict__ spts,
+                                                   double x, double y, double z, F f) {
+    const int64_t cx = cell_of(x, g.ax, g.edge), cy = cell_of(y, g.ay, g.edge), cz = cell_of(z, g.az, g.edge);
+    for (int dzc = -1; dzc <= 1; ++dzc)
+        for (int dyc = -1; dyc <= 1; ++dyc)
+            for (int dxc = -1; dxc <= 1; ++dxc) {
+                const int64_t tx = cx + dxc, ty = cy + dyc, tz = cz + dzc;
+                if (tx < -kCellMax || ty < -kCellMax || tz < -kCellMax || tx > kCellMax || ty > kCellMax || tz > kCellMax) continue;
+                const uint32_t b = bucket_of(tx, ty, tz, g.mask);
+                const uint32_t t0 = start[b], t1 = start[b + 1];
+                for (uint32_t t = t0; t < t1; ++t) {
+                    const uint4 c = scell[t];
+                    if (c.x != (uint32_t)tx || c.y != (uint32_t)ty || c.z != (uint32_t)tz) continue;
+                    const double d2 = dist2(x, y, z, spts[3 * (size_t)t], spts[3 * (size_t)t + 1], spts[3 * (size_t)t + 2]);
+                    if (d2 < g.eps2)
+                        if (f(t, (int)c.w)) return;
+                }
+            }
+}
+
+// ---- finite: whether every coordinate is finite (device points have no other judge) -----------------------------
+// flag: zeroed before the launch; one add per block that saw a NaN or an infinity.
+__global__ __launch_bounds__(kB) void dbscan_finite_kernel(const double *__restrict__ pts, int64_t n3, unsigned int *flag) {
+    __shared__ int sbad;
+    if (threadIdx.x == 0) sbad = 0;
+    __syncthreads();
+    int bad = 0;
+    for (int64_t k = (int64_t)blockIdx.x * kB + threadIdx.x; k < n3; k += (int64_t)gridDim.x * kB)
+        if (!(fabs(pts[k]) <= DBL_MAX)) bad = 1;
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&sbad, 1);
+    __syncthreads();
+    if (threadIdx.x == 0 && sbad) atomicAdd(flag, 1u);
+}
+
+// ---- counting sort by bucket -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(kB) void dbscan_hist_kernel(const double *__restrict__ pts, int P, Grid g, uint32_t *__restrict__ count) {
+    const int i = (int)(blockIdx.x * kB + threadIdx.x);
+    if (i >= P) return;
+    const int64_t cx = cell_of(pts[3 * (size_t)i], g.ax, g.edge), cy = cell_of(pts[3 * (size_t)i + 1], g.ay, g.edge),
+                  cz = cell_of(pts[3 * (size_t)i + 2], g.az, g.edge);
+    atomicAdd(&count[bucket_of(cx, cy, cz, g.mask)], 1u);
+}
+
+// cursor = a copy of start; afterwards cursor[b] == start[b + 1].  The order inside a bucket is whatever the atomics
+// give; no result depends on it.  Also sets every point's state by original index.
+__global__ __launch_bounds__(kB) void dbscan_scatter_kernel(const double *__restrict__ pts, int P, Grid g, uint32_t *__restrict__ cursor,
+                                                            uint4 *__restrict__ scell, double *__restrict__ spts,
+                                                            int *__restrict__ parent, int *__restrict__ rootof, int *__restrict__ isroot) {
+    const int i = (int)(blockIdx.x * kB + threadIdx.x);
+    if (i >= P) return;
+    const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    const int64_t cx = cell_of(x, g.ax, g.edge), cy = cell_of(y, g.ay, g.edge), cz = cell_of(z, g.az, g.edge);
+    const uint32_t t = atomicAdd(&cursor[bucket_of(cx, cy, cz, g.mask)], 1u);
+    scell[t] = make_uint4((uint32_t)cx, (uint32_t)cy, (uint32_t)cz, (uint32_t)i);  // the cell's low bits
+    spts[3 * (size_t)t] = x;
+    spts[3 * (size_t)t + 1] = y;
+    spts[3 * (size_t)t + 2] = z;
+    parent[i] = i;
+    rootof[i] = -1;
+    isroot[i] = 0;
+}
+
+// ---- core flags (rule 3) ---------------------------------------------------------------------------------------
+// One thread per sorted slot.  The count stops at min_points: only whether it is reached matters.
+__global__ __launch_bounds__(kB) void dbscan_core_kernel(int P, Grid g, int64_t minp, const uint32_t *__restrict__ start,
+                                                         const uint4 *__restrict__ scell, const double *__restrict__ spts,
+                                                         uint8_t *__restrict__ core) {
+    const int s = (int)(blockIdx.x * kB + threadIdx.x);
+    if (s >= P) return;
+    int64_t n = 0;
+    for_each_neighbour(g, start, scell, spts, spts[3 * (size_t)s], spts[3 * (size_t)s + 1], spts[3 * (size_t)s + 2],
+                       [&](uint32_t, int) { return ++n >= minp; });
+    core[s] = n >= minp ? 1 : 0;
+}
+
+// ---- link (rule 4) ---------------------------------------------------------------------------------------------
+// parent[] is indexed by ORIGINAL index and only ever holds a smaller-or-equal index of the same component: a root
+// (parent[a] == a) is hung under a smaller root with a compare-and-swap, so when the launch ends each component's
+// root is its smallest index whatever the order of the atomics was.  Blocks on different XCDs share parent[] inside
+// this launch and their L2s are not coherent: EVERY access here is a relaxed agent-scope atomic, none a plain load.
+#define DB_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+__device__ __forceinline__ int find_root(int *parent, int a) {
+    for (;;) {
+        const int p = __hip_atomic_load(&parent[a], DB_RLX);
+        if (p == a) return a;
+        const int gp = __hip_atomic_load(&parent[p], DB_RLX);
+        if (gp != p) (void)__hip_atomic_fetch_min(&parent[a], gp, DB_RLX);  // path halving: a non-root only moves up
+        a = p;
+    }
+}
+
+__device__ __forceinline__ void unite(int *parent, int a, int b) {
+    for (;;) {
+        a = find_root(parent, a);
+        b = find_root(parent, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }  // a > b: hang a under b
+        int expect = a;
+        if (__hip_atomic_compare_exchange_strong(&parent[a], &expect, b, __ATOMIC_RELAXED, DB_RLX)) return;
+    }
+}
+
+__global__ __launch_bounds__(kB) void dbscan_link_kernel(int P, Grid g, const uint32_t *__restrict__ start, const uint4 *__restrict__ scell,
+                                                         const double *__restrict__ spts, const uint8_t *__restrict__ core, int *parent) {
+    const int s = (int)(blockIdx.x * kB + threadIdx.x);
+    if (s >= P || !core[s]) return;
+    const int i = (int)scell[s].w;
+    for_each_neighbour(g, start, scell, spts, spts[3 * (size_t)s], spts[3 * (size_t)s + 1], spts[3 * (size_t)s + 2],
+                       [&](uint32_t t, int j) {
+                           if (j < i && core[t]) unite(parent, i, j);  // each pair once, from its larger index
+                           return false;
+                       });
+}
+
+// ---- flatten, border (rule 5), labels --------------------------------------------------------------------------
+// parent[] is final here (a kernel boundary lies behind the link launch) and is only read: plain loads.
+__global__ __launch_bounds__(kB) void dbscan_flatten_kernel(int P, const uint4 *__restrict__ scell, const uint8_t *__restrict__ core,
+                                                            const int *__restrict__ parent, int *__restrict__ rootof, int *__restrict__ isroot) {
+    const int s = (int)(blockIdx.x * kB + threadIdx.x);
+    if (s >= P || !core[s]) return;
+    const int i = (int)scell[s].w;
+    int r = i;
+    while (parent[r] != r) r = parent[r];
+    rootof[i] = r;
+    if (r == i) isroot[i] = 1;
+}
+
+// A non-core point reads rootof[] of core points only (written by the launch before) and writes its own.  Ids rise
+// with the roots' indices (rule 4), so the smallest root is the smallest id.
+__global__ __launch_bounds__(kB) void dbscan_border_kernel(int P, Grid g, const uint32_t *__restrict__ start, const uint4 *__restrict__ scell,
+                                                           const double *__restrict__ spts, const uint8_t *__restrict__ core, int *rootof) {
+    const int s = (int)(blockIdx.x * kB + threadIdx.x);
+    if (s >= P || core[s]) return;
+    int best = 0x7fffffff;
+    for_each_neighbour(g, start, scell, spts, spts[3 * (size_t)s], spts[3 * (size_t)s + 1], spts[3 * (size_t)s + 2],
+                       [&](uint32_t t, int j) {
+                           if (core[t]) best = min(best, rootof[j]);
+                           return false;
+                       });
+    if (best != 0x7fffffff) rootof[(int)scell[s].w] = best;
+}
+
+// rank = exclusive sum of isroot: the number of roots with a smaller index, i.e. the cluster id of rule 4
+__global__ __launch_bounds__(kB) void dbscan_labels_kernel(int P, const int *__restrict__ rootof, const int *__restrict__ isroot,
+                                                           const int *__restrict__ rank, int32_t *__restrict__ labels,
+                                                           int32_t *__restrict__ nclusters) {
+    const int i = (int)(blockIdx.x * kB + threadIdx.x);
+    if (i >= P) return;
+    const int r = rootof[i];
+    labels[i] = r < 0 ? -1 : rank[r];
+    if (i == P - 1) *nclusters = rank[i] + isroot[i];
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------
+// Work buffers are kept per device and grow as needed (the model of masks_rgb.hip): calls are serialised by the
+// slot's mutex while they enqueue, and each waits on the device, through the slot's event, for the call before it.
+struct Slot {
+    std::mutex mu;
+    char *base = nullptr;
+    size_t cap = 0;
+    hipEvent_t last = nullptr;
+    bool checked = false;
+};
+Slot g_slots[64];
+
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+#define D_TRY(expr)                                                                \
+    do {                                                                           \
+        hipError_t _e = (expr);                                                    \
+        if (_e != hipSuccess) { rc = fail_d(_e == hipErrorOutOfMemory ? SC_ERR_NOMEM : SC_ERR_DEVICE, hipGetErrorString(_e)); goto done; } \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+
+const char *sc_dbscan_last_error(void) { return g_derr; }
+
+int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps, int64_t min_points, int device,
+              int32_t *labels_out, int labels_on_device, int32_t *nclusters_out, void *hip_stream) {
+    // every argument is judged before the first device call
+    if (!points || !labels_out) return fail_d(SC_ERR_INVALID, "null argument (points, labels_out)");
+    if (P < 0 || P >= ((int64_t)1 << 31)) return fail_d(SC_ERR_INVALID, "P must be 0 .. 2^31 - 1");
+    if (!std::isfinite(eps) || !(eps > 0.0)) return fail_d(SC_ERR_INVALID, "eps must be finite and positive");
+    if (!(eps * eps >= DBL_MIN) || !std::isfinite(eps * eps))
+        return fail_d(SC_ERR_INVALID, "eps * eps must be a normal number (eps out of range)");
+    if (min_points < 0) return fail_d(SC_ERR_INVALID, "min_points must not be negative");
+    if (device < 0 || device >= 64) return fail_d(SC_ERR_INVALID, "device ordinal out of range");
+    if (!points_on_device)
+        for (int64_t k = 0; k < 3 * P; ++k)
+            if (!std::isfinite(points[k])) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "non-finite coordinate in point %lld", (long long)(k / 3));
+                return fail_d(SC_ERR_INVALID, msg);
+            }
+    if (P == 0) {
+        if (nclusters_out) *nclusters_out = 0;
+        return SC_OK;
+    }
+
+    const int n = (int)P;
+    uint32_t nb = 64;  // buckets: a power of two, at least P (at most 2^30)
+    while (nb < (uint32_t)std::min<int64_t>(P, (int64_t)1 << 30)) nb <<= 1;
+    const uint32_t blocks = (uint32_t)((P + kB - 1) / kB);
+    const int64_t minp = std::max<int64_t>(min_points, 1);  // a point is its own neighbour: 0 behaves as 1
+
+    Slot &sl = g_slots[device];
+    std::lock_guard<std::mutex> lock(sl.mu);
+    int rc = SC_OK;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    size_t tmp1 = 0, tmp2 = 0;
+    double anchor[3] = {0, 0, 0};
+    unsigned int bad = 0;
+    int32_t ncl = 0;
+    Grid g;
+
+    // layout of the work buffer
+    size_t o = 0;
+    const size_t o_hdr = o;    o += 256;                                  // the non-finite flag, nclusters
+    const size_t o_count = o;  o += al256(((size_t)nb + 1) * 4);
+    const size_t o_start = o;  o += al256(((size_t)nb + 1) * 4);
+    const size_t o_cursor = o; o += al256(((size_t)nb + 1) * 4);
+    const size_t o_scell = o;  o += al256((size_t)P * 16);
+    const size_t o_spts = o;   o += al256((size_t)P * 24);
+    const size_t o_core = o;   o += al256((size_t)P);
+    const size_t o_parent = o; o += al256((size_t)P * 4);
+    const size_t o_rootof = o; o += al256((size_t)P * 4);
+    const size_t o_isroot = o; o += al256((size_t)P * 4);
+    const size_t o_rank = o;   o += al256((size_t)P * 4);
+    const size_t o_pts = o;    o += points_on_device ? 0 : al256((size_t)P * 24);
+    const size_t o_lab = o;    o += labels_on_device ? 0 : al256((size_t)P * 4);
+    const size_t o_tmp = o;
+
+    D_TRY(hipSetDevice(device));
+    if (!sl.checked) {
+        hipDeviceProp_t prop;
+        D_TRY(hipGetDeviceProperties(&prop, device));
+        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+            return fail_d(SC_ERR_DEVICE, msg);
+        }
+        D_TRY(hipEventCreateWithFlags(&sl.last, hipEventDisableTiming));
+        D_TRY(hipEventRecord(sl.last, stream));
+        sl.checked = true;
+    }
+    // the scans' temporary storage (a size query: no device work)
+    D_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(nb + 1), stream));
+    D_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (const int *)nullptr, (int *)nullptr, n, stream));
+    {
+        const size_t tmp = std::max(tmp1, tmp2), need = o_tmp + al256(tmp);
+        if (sl.cap < need) {
+            D_TRY(hipEventSynchronize(sl.last));  // nobody reads the old buffers any more
+            if (sl.base) (void)hipFree(sl.base);
+            sl.base = nullptr;
+            sl.cap = 0;
+            D_TRY(hipMalloc(reinterpret_cast<void **>(&sl.base), need));
+            sl.cap = need;
+        }
+    }
+    {
+        char *const w = sl.base;
+        unsigned int *flag = reinterpret_cast<unsigned int *>(w + o_hdr);
+        uint32_t *count = reinterpret_cast<uint32_t *>(w + o_count), *start = reinterpret_cast<uint32_t *>(w + o_start),
+                 *cursor = reinterpret_cast<uint32_t *>(w + o_cursor);
+        uint4 *scell = reinterpret_cast<uint4 *>(w + o_scell);
+        double *spts = reinterpret_cast<double *>(w + o_spts);
+        uint8_t *core = reinterpret_cast<uint8_t *>(w + o_core);
+        int *parent = reinterpret_cast<int *>(w + o_parent), *rootof = reinterpret_cast<int *>(w + o_rootof),
+            *isroot = reinterpret_cast<int *>(w + o_isroot), *rank = reinterpret_cast<int *>(w + o_rank);
+        int32_t *ncl_d = reinterpret_cast<int32_t *>(w + o_hdr + 64);
+        const double *pts_d = points_on_device ? points : reinterpret_cast<const double *>(w + o_pts);
+        int32_t *lab_d = labels_on_device ? labels_out : reinterpret_cast<int32_t *>(w + o_lab);
+        void *tmp_d = w + o_tmp;
+
+        D_TRY(hipStreamWaitEvent(stream, sl.last, 0));  // behind the previous call, whatever its stream was
+        if (!points_on_device)
+            D_TRY(hipMemcpyAsync(w + o_pts, points, (size_t)P * 24, hipMemcpyHostToDevice, stream));
+        D_TRY(hipMemsetAsync(flag, 0, 128, stream));
+        hipLaunchKernelGGL(dbscan_finite_kernel, dim3(std::min<uint32_t>(blocks, 1024u)), dim3(kB), 0, stream, pts_d, 3 * P, flag);
+        D_TRY(hipGetLastError());
+        D_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, stream));
+        D_TRY(hipMemcpyAsync(anchor, pts_d, 24, hipMemcpyDeviceToHost, stream));
+        D_TRY(hipEventRecord(sl.last, stream));
+        D_TRY(hipStreamSynchronize(stream));
+        if (bad != 0u) {  // device points: the first kernel is the judge
+            rc = fail_d(SC_ERR_INVALID, "non-finite coordinate in the device points");
+            goto done;
+        }
+        g.ax = anchor[0];
+        g.ay = anchor[1];
+        g.az = anchor[2];
+        g.edge = eps * kEdgeFactor;
+        g.eps2 = eps * eps;
+        g.mask = nb - 1;
+
+        D_TRY(hipMemsetAsync(count, 0, ((size_t)nb + 1) * 4, stream));
+        hipLaunchKernelGGL(dbscan_hist_kernel, dim3(blocks), dim3(kB), 0, stream, pts_d, n, g, count);
+        D_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp1, count, start, (int)(nb + 1), stream));
+        D_TRY(hipMemcpyAsync(cursor, start, (size_t)nb * 4, hipMemcpyDeviceToDevice, stream));
+        hipLaunchKernelGGL(dbscan_scatter_kernel, dim3(blocks), dim3(kB), 0, stream, pts_d, n, g, cursor, scell, spts, parent, rootof,
+                           isroot);
+        hipLaunchKernelGGL(dbscan_core_kernel, dim3(blocks), dim3(kB), 0, stream, n, g, minp, start, scell, spts, core);
+        hipLaunchKernelGGL(dbscan_link_kernel, dim3(blocks), dim3(kB), 0, stream, n, g, start, scell, spts, core, parent);
+        hipLaunchKernelGGL(dbscan_flatten_kernel, dim3(blocks), dim3(kB), 0, stream, n, scell, core, parent, rootof, isroot);
+        hipLaunchKernelGGL(dbscan_border_kernel, dim3(blocks), dim3(kB), 0, stream, n, g, start, scell, spts, core, rootof);
+        D_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp2, isroot, rank, n, stream));
+        hipLaunchKernelGGL(dbscan_labels_kernel, dim3(blocks), dim3(kB), 0, stream, n, rootof, isroot, rank, lab_d, ncl_d);
+        D_TRY(hipGetLastError());
+        if (!labels_on_device) D_TRY(hipMemcpyAsync(labels_out, lab_d, (size_t)P * 4, hipMemcpyDeviceToHost, stream));
+        if (nclusters_out) D_TRY(hipMemcpyAsync(&ncl, ncl_d, 4, hipMemcpyDeviceToHost, stream));
+        D_TRY(hipEventRecord(sl.last, stream));
+        if (!labels_on_device || nclusters_out) {
+            D_TRY(hipStreamSynchronize(stream));
+            if (nclusters_out) *nclusters_out = ncl;
+        }
+    }
+
+done:
+    if (rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);  // nothing of ours still reads host memory
+    return rc;
+}
+
+void sc_dbscan_release(void) {
+    int current = -1;
+    const bool restore = hipGetDevice(&current) == hipSuccess;  // the caller's current device stays what it was
+    for (int d = 0; d < 64; ++d) {
+        Slot &sl = g_slots[d];
+        std::lock_guard<std::mutex> lock(sl.mu);
+        if (sl.base && hipSetDevice(d) == hipSuccess) {
+            if (sl.last) (void)hipEventSynchronize(sl.last);
+            (void)hipFree(sl.base);
+            sl.base = nullptr;
+            sl.cap = 0;
+        }
+    }
+    if (restore) (void)hipSetDevice(current);
+}
+
+}  // extern "C"

@@ -40,9 +40,11 @@ def gaussian_weights(sigma=1.0, truncate=4.0):
 
 def release_device_buffers():
     """Give back the device work buffers ``vol2pcd`` keeps between calls (``sc_vol2pcd_release``; it keeps them
-    only while they are at most 1 GiB).  ``Backprojection.close`` calls this too."""
+    only while they are at most 1 GiB) and those of ``cluster_dbscan`` (``sc_dbscan_release``).
+    ``Backprojection.close`` calls both too."""
     from . import _native as nat
     nat.backend().call("sc_vol2pcd_release")
+    nat.backend().call("sc_dbscan_release")
 
 
 def set_scratch_limit(nbytes):
@@ -199,3 +201,59 @@ def label_points(points, cameras, masks, device=0):
             raise ValueError(f"sc_label_points: {msg}")
         raise nat.SpaceCarveError(f"sc_label_points: {msg} (code {rc})")
     return labels, scores
+
+
+def cluster_dbscan(points, eps, min_points, device=0):
+    """open3d's ``PointCloud.cluster_dbscan(eps, min_points)`` -- what ``OrganSegmentation.run`` calls per label
+    (``tasks/proc3d.py:507-508``) -- on the GPU (``sc_dbscan``, ``csrc/dbscan.hip``).
+
+    points : array-like ``[P, 3]``, a :class:`PointCloud` or anything with ``.points`` -> ``np.int32 [P]``; or a
+        contiguous float64 CUDA torch tensor ``[P, 3]``, read in place on torch's current stream -> a CUDA int32 tensor
+        on the same device.
+    Labels: cluster ids from 0 in the order of each cluster's smallest point index, ``-1`` for noise.
+
+    PARITY UNPINNED: open3d is not available here.  The rules restate its sequential loop in an
+    order-free form: ``d2 = ((dx dx) + (dy dy)) + (dz dz)`` in float64, neighbours iff ``d2 < eps * eps`` (strict: a
+    pair at exactly ``eps`` is not; a point is its own neighbour), core iff at least ``min_points`` neighbours,
+    clusters = connected components of the core points, a border point joins the smallest id among its core
+    neighbours.  Deviation: non-finite coordinates (and ``eps`` that is not finite and positive) raise ``ValueError``.
+    """
+    from . import _native as nat
+
+    b = nat.backend()
+
+    def check(rc):
+        if rc == nat.SC_OK:
+            return
+        msg = f"sc_dbscan: {b.string(b.call('sc_dbscan_last_error'))} (code {rc})"
+        if rc == nat.SC_ERR_INVALID:
+            raise ValueError(msg)
+        if rc == nat.SC_ERR_NOMEM:
+            raise MemoryError(msg)
+        raise nat.SpaceCarveError(msg)
+
+    if not isinstance(points, np.ndarray) and hasattr(points, "points"):
+        points = points.points
+    if not isinstance(points, np.ndarray) and hasattr(points, "data_ptr"):  # torch tensor on the device
+        import torch
+        if (points.dtype != torch.float64 or not points.is_cuda or not points.is_contiguous() or points.dim() != 2
+                or points.shape[1] != 3):
+            raise ValueError("device points must be a contiguous float64 CUDA tensor [P, 3]")
+        dev = points.device.index
+        P = int(points.shape[0])
+        out = torch.empty((P,), dtype=torch.int32, device=points.device)
+        if P:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            check(b.call("sc_dbscan", points.data_ptr(), 1, P, float(eps), int(min_points), int(dev), out.data_ptr(), 1, 0,
+                         int(stream)))
+        return out
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        if pts.size:
+            raise ValueError("points must be [P, 3]")
+        pts = pts.reshape(0, 3)
+    P = pts.shape[0]
+    labels = np.full(max(P, 1), -1, dtype=np.int32)
+    keep = pts if P else np.zeros((1, 3))  # a valid address for an empty cloud
+    check(b.call("sc_dbscan", nat.addr(keep), 0, P, float(eps), int(min_points), int(device), nat.addr(labels), 0, 0, 0))
+    return labels[:P]
