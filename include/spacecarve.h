@@ -398,6 +398,10 @@ int sc_fused_counts(sc_engine *e, int64_t out[4]);
  * (SC_OPT_BULK_MIN); out[6]: their work items (0 when the batch had fewer units than SC_OPT_BULK_FLOOR: their
  * voxels took the ordinary lists); out[7]: 0 (round 3: batches the host kept the bulk list off). */
 int sc_fused_counts_ex(sc_engine *e, int64_t out[8]);
+/* What the last flushed batch packed of its masks, in 32x32 tiles (SC_OPT_PACK_REACH; all 0 for a batch that was not
+ * packed at its flush): out[0] tiles packed ahead of the flags kernel, out[1] the tiles of those views' pictures,
+ * out[2] tiles packed beside the dense stage (waits for the stream), out[3] the tiles of those views' pictures. */
+int sc_pack_counts(sc_engine *e, int64_t out[4]);
 
 /* Self-test: runs the kernels' shared-reciprocal division and the compiler's IEEE division on
  * `count` pseudo-random operand triples (mode 0: raw bit patterns, 1: projection-like

@@ -99,5 +99,9 @@
                                      ahead; a unit some view finds empty is carved whole, not projected -- unless
                                      the tile level settled less than half of the bricks (masks without structure:
                                      nothing for the cells to find); 2: asked whatever the tiles settled; 0: never */
+#define SC_OPT_PACK_REACH 48       /* 1 (default): a batch of device-resident masks that is packed at its flush
+                                     (SC_OPT_PACK_RIDE) packs, of every view, only the 32x32 tiles a voxel of the engine
+                                     can reach -- the image of the grid's box, worked out on the host from the pose alone;
+                                     the rest of the packed arena is never looked at.  0: whole pictures              */
 
 #endif /* SPACECARVE_TUNING_H */

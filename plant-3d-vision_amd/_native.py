@@ -46,6 +46,7 @@ SC_OPT_BULK_ADAPT = SC_OPT_BULK_FLOOR  # deprecated name of key 35 (0 still mean
 SC_OPT_UNIT_CULL, SC_OPT_LIST_CAP, SC_OPT_HOST_PACK, SC_OPT_HOST_THREADS, SC_OPT_LDS_TILES, SC_OPT_BULK_LIVE, SC_OPT_SAFE_KERNELS = 37, 38, 39, 40, 41, 42, 43
 SC_OPT_DENSE_EXTRA = 44
 SC_OPT_SPEC_SHARE, SC_OPT_SPEC_BLOCKS, SC_OPT_LATE_ROAD = 45, 46, 47
+SC_OPT_PACK_REACH = 48
 SC_FILTER_LINEAR, SC_FILTER_EXCESS_GREEN = 0, 1
 SC_FOOT = {"t0": 0, "t90": 1, "t180": 2, "t270": 3, "diamond": 4, "square": 5}  # SC_FOOT_*: names of masks2d._FOOTPRINTS
 
@@ -114,6 +115,7 @@ _SIGNATURES = {
     "sc_reset_kernel_stats": ("i", ["p"]),
     "sc_fused_counts": ("i", ["p", "p"]),
     "sc_fused_counts_ex": ("i", ["p", "p"]),
+    "sc_pack_counts": ("i", ["p", "p"]),
     "sc_span_begin": ("i", ["p"]),
     "sc_span_end": ("i", ["p", "p"]),
     "sc_selftest_division": ("i", ["p", "q", "I", "i", "p", "p"]),
@@ -945,6 +947,13 @@ class Engine:
         return {"live_bricks": int(out[0]), "alive_after_dense_stage": int(out[1]),
                 "alive_after_first_list_stage": int(out[2]), "list_overflow": int(out[3]), "late_bricks": int(out[4]),
                 "bulk_units": int(out[5]), "unit_items": int(out[6])}
+
+    def pack_counts(self):
+        """(tiles packed ahead, tiles of the views packed ahead, tiles packed by riders, tiles of the riders' views)
+        of the last flushed batch (``sc_pack_counts``; 32x32-pixel tiles)."""
+        out = np.zeros(4, dtype=np.int64)
+        self._call("sc_pack_counts", addr(out))
+        return tuple(int(x) for x in out)
 
     def selftest_division(self, count, seed=1, mode=1):
         """(mismatches, fast_pairs) of the shared-reciprocal division vs hipcc's IEEE division."""

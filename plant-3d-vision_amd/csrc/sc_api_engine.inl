@@ -250,6 +250,9 @@ int sc_set_option(sc_engine *e, int key, int64_t value) {
         case SC_OPT_PACK_RIDE:
             e->pack_ride = value ? 1 : 0;
             return SC_OK;
+        case SC_OPT_PACK_REACH:
+            e->pack_reach = value ? 1 : 0;
+            return SC_OK;
         case SC_OPT_FLAG_VIEWS:
             if (value < 0) return fail(SC_ERR_INVALID, "flag_views must be >= 0");
             e->flag_views = value;

@@ -355,6 +355,20 @@ int sc_fused_counts_ex(sc_engine *e, int64_t out[8]) {
     return SC_OK;
 }
 
+int sc_pack_counts(sc_engine *e, int64_t out[4]) {
+    if (!e || !out) return fail(SC_ERR_INVALID, "bad argument");
+    for (int q = 0; q < 4; ++q) out[q] = e->pack_cnt[q];
+    if (!e->pack_cnt_riders || !e->ctl) return SC_OK;
+    int rc = use_device(e);
+    if (rc) return rc;
+    HIP_TRY(schost::wait_stream(e->stream));
+    ListCounter host[kRiderCounters];
+    HIP_TRY(hipMemcpy(host, e->ctl->rider_tiles, sizeof host, hipMemcpyDeviceToHost));
+    out[2] = 0;
+    for (int s = 0; s < kRiderCounters; ++s) out[2] += host[s].n;
+    return SC_OK;
+}
+
 int sc_fused_counts(sc_engine *e, int64_t out[4]) {
     if (!e || !out) return fail(SC_ERR_INVALID, "bad argument");
     out[0] = out[1] = out[2] = out[3] = 0;

@@ -388,11 +388,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
         // (this stage waits on gathers and arithmetic, the packing on HBM reads).  One short block per
         // panel: persistent riders measured the same or slower.
         const uint32_t b = blockIdx.x - nwalkers;
-        if (pack_rows == 0) pack_band_block(ride, b);
-        else if (pack_rows == 1) pack16_block<1>(ride, b);
-        else if (pack_rows == 2) pack16_block<2>(ride, b);
-        else if (pack_rows == 8) pack16_block<8>(ride, b);
-        else pack16_block<4>(ride, b);
+        const int rs = pack_rows == 0 ? pack_band_slot(ride, b)
+                                      : (pack_rows == 1 ? pack16_slot<1>(ride, b)
+                                                        : (pack_rows == 2 ? pack16_slot<2>(ride, b) : (pack_rows == 8 ? pack16_slot<8>(ride, b) : pack16_slot<4>(ride, b))));
+        if (rs >= ride.nslots) return;  // block-uniform
+        const TileRect rc = job_rect(ride, rs + ride.slot0);
+        uint32_t packed;
+        if (pack_rows == 0) packed = pack_band_block(ride, b, rc);
+        else if (pack_rows == 1) packed = pack16_block<1>(ride, b, rc);
+        else if (pack_rows == 2) packed = pack16_block<2>(ride, b, rc);
+        else if (pack_rows == 8) packed = pack16_block<8>(ride, b, rc);
+        else packed = pack16_block<4>(ride, b, rc);
+        if (packed != 0u && threadIdx.x == 0) (void)atomicAdd(&ctl->rider_tiles[b & (uint32_t)(kRiderCounters - 1)].n, packed);  // sc_pack_counts
         return;
     }
     // Walkers are WAVEFRONTS: each takes the next live brick of its XCD's runs (runs of kXcdRun consecutive entries --

@@ -50,6 +50,9 @@ struct sc_engine {
     size_t verdf_cap = 0;
     int64_t pack_rows = 0;     // 0: the band form of the 16-byte pack kernel; 1, 2, 4, 8: the panel form, tile rows per block
     int64_t view_brick = 1;    // a single-view carve launch goes through the brick kernels too (0: streaming kernel)
+    int64_t pack_reach = 1;    // a batch packed at its flush packs only the tiles its voxels can reach (0: whole pictures)
+    int64_t pack_cnt[4] = {0, 0, 0, 0};  // sc_pack_counts of the last flushed batch ([2] on the device when riders packed)
+    bool pack_cnt_riders = false;
     uint8_t *dead = nullptr;   // per brick: an earlier launch found it empty, every voxel is -1 (until the next clear)
     bool dead_clean = false;   // `dead` describes the labels (false after a clear: the next flags kernel rewrites it)
     int64_t pack_ride = 1;     // a device batch is packed at flush, in view order: the first views ahead of

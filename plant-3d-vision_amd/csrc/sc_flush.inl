@@ -43,12 +43,67 @@ struct Ride {
     bool ordered;  // the pending views are in the order they will be applied already
 };
 
+// The REACH RECTANGLE of a view (ViewDesc::reserved): the 32x32 tiles of its picture that a voxel of this engine --
+// planes i0 + k istride, every column, every voxel -- or a verdict about a brick or a unit of it can look at.  Readers
+// take whole bricks, those that stick out of the grid at its far y / z faces included, so the box is the engine's
+// planes x whole bricks.  Under a certified view with every corner well in front of the camera the image of that
+// convex box is the hull of its eight corners' images (DESIGN_APPENDIX.md 4b), worked out here in double precision
+// from the kernels' own float coordinates.  A reader's widened pixel box (rect_box) lies within twice its slack of
+// the exact image, and the slack grows with the box: the hull is widened by the slack mu of the WHOLE box plus one
+// whole tile, which covers 2 mu as long as mu <= 32 -- beyond that, for an uncertified view, a corner not in front or
+// anything not finite, the rectangle is the whole picture (0).  An image that misses the picture: the empty rectangle.
+uint64_t reach_rect(const sc_engine *e, const ViewDesc &d) {
+    const int64_t tiles_x = (d.W + kTile - 1) / kTile, tiles_y = (d.H + kTile - 1) / kTile;
+    if (d.safe == 0 || tiles_x > 0xffff || tiles_y > 0xffff) return 0;
+    const int64_t last[3] = {e->i0 + (e->planes - 1) * e->istride, (e->ny + kBrickY - 1) / kBrickY * kBrickY - 1,
+                             (e->nz + kBrickZ - 1) / kBrickZ * kBrickZ - 1};
+    const int64_t first[3] = {e->i0, 0, 0};
+    double c[3][2];  // the box's extremes per axis, as the kernels compute a coordinate: origin + (float)index * voxel_size
+    for (int a = 0; a < 3; ++a) {
+        c[a][0] = (double)(e->origin[a] + (float)first[a] * e->vs);
+        c[a][1] = (double)(e->origin[a] + (float)last[a] * e->vs);
+    }
+    double err[3], pzmin = INFINITY, umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY, qxm = 0.0, qym = 0.0;
+    for (int r = 0; r < 3; ++r) {  // rows of R: x, y, depth
+        err[r] = std::fabs((double)d.t[r]);
+        for (int a = 0; a < 3; ++a) err[r] += std::fabs((double)d.R[3 * r + a]) * std::max(std::fabs(c[a][0]), std::fabs(c[a][1]));
+        err[r] *= 0x1p-19;
+    }
+    for (int q = 0; q < 8; ++q) {
+        const double X[3] = {c[0][q & 1], c[1][(q >> 1) & 1], c[2][(q >> 2) & 1]};
+        double p[3];
+        for (int r = 0; r < 3; ++r) p[r] = (double)d.R[3 * r] * X[0] + (double)d.R[3 * r + 1] * X[1] + (double)d.R[3 * r + 2] * X[2] + (double)d.t[r];
+        if (!(p[2] > 8.0 * err[2]) || !(p[2] > 0x1p-10)) return 0;  // (also NaN)
+        const double qx = p[0] / p[2], qy = p[1] / p[2];
+        const double u = qx * (double)d.K[0] + (double)d.K[2], v = qy * (double)d.K[1] + (double)d.K[3];
+        if (!std::isfinite(u) || !std::isfinite(v)) return 0;
+        pzmin = std::min(pzmin, p[2]);
+        umin = std::min(umin, u); umax = std::max(umax, u);
+        vmin = std::min(vmin, v); vmax = std::max(vmax, v);
+        qxm = std::max(qxm, std::fabs(qx)); qym = std::max(qym, std::fabs(qy));
+    }
+    // rect_box's slack (sc_verdicts.h), with the box's extremes
+    const double inv = 2.0 / pzmin;
+    const double mu = 2.0 + std::fabs((double)d.K[0]) * (err[0] + qxm * err[2]) * inv +
+                      (std::fabs((double)d.K[0]) * qxm + std::fabs((double)d.K[2]) + std::max(std::fabs(umin), std::fabs(umax))) * 0x1p-20;
+    const double mv = 2.0 + std::fabs((double)d.K[1]) * (err[1] + qym * err[2]) * inv +
+                      (std::fabs((double)d.K[1]) * qym + std::fabs((double)d.K[3]) + std::max(std::fabs(vmin), std::fabs(vmax))) * 0x1p-20;
+    if (!(mu <= 32.0 && mv <= 32.0)) return 0;
+    const double ulo = umin - mu - 32.0, uhi = umax + mu + 32.0, vlo = vmin - mv - 32.0, vhi = vmax + mv + 32.0;
+    if (uhi < 0.0 || vhi < 0.0 || ulo > (double)d.W - 1.0 || vlo > (double)d.H - 1.0) return 1ull | (1ull << 16) | (1ull << 32) | (1ull << 48);  // empty
+    const uint64_t tx0 = (uint64_t)std::floor(std::max(ulo, 0.0) / 32.0), tx1 = (uint64_t)std::floor(std::min(uhi, (double)d.W - 1.0) / 32.0) + 1;
+    const uint64_t ty0 = (uint64_t)std::floor(std::max(vlo, 0.0) / 32.0), ty1 = (uint64_t)std::floor(std::min(vhi, (double)d.H - 1.0) / 32.0) + 1;
+    return tx0 | (tx1 << 16) | (ty0 << 32) | (ty1 << 48);
+}
+
 // A device batch whose packing was deferred is packed here, in the order its views will be applied: the views the
 // flags kernel, the dense stage and the first survivor stage need go ahead, the others ride beside the dense stage
 // (brick form).  Any other shape of launch packs the whole batch first, in the order given.
 int pack_deferred(sc_engine *e, size_t nv, Ride *r) {
     memset(r, 0, sizeof *r);
     r->packed_ahead = (int)nv;
+    for (int q = 0; q < 4; ++q) e->pack_cnt[q] = 0;  // sc_pack_counts speaks of the last flushed batch
+    e->pack_cnt_riders = false;
     if (!e->deferred.on) return SC_OK;
     const bool whole = nv == e->pending.size() && nv == (size_t)e->deferred.V && e->mode == SC_MODE_CARVE && nv > 1;
     if (!whole) return materialize_deferred(e);
@@ -71,6 +126,23 @@ int pack_deferred(sc_engine *e, size_t nv, Ride *r) {
     if (e->pack_ride && fp.brick && fp.compact) ahead = std::min<int>((int)nv, std::max(fp.flag_views, fp.s1));
     pj.slot0 = 0;
     pj.nslots = ahead;
+    // every view's reach rectangle: in its descriptor, and in the job for the packers (ahead and riders alike)
+    pj.reach_on = e->pack_reach ? 1 : 0;
+    const int64_t view_tiles = (int64_t)pj.tiles_x * pj.tiles_y;
+    for (size_t q = 0; q < nv; ++q) {
+        ViewDesc &d = e->pending[q];
+        // (a slot the job has no room for is packed whole, and its descriptor says so: field and arena agree)
+        d.reserved = (e->pack_reach && q < (size_t)kReachViews) ? reach_rect(e, d) : 0;
+        if (q < (size_t)kReachViews)
+            for (int w = 0; w < 4; ++w) pj.reach[q][w] = (uint16_t)(d.reserved >> (16 * w));
+        if ((int)q < ahead) {
+            const TileRect rc = rect_unpack(d.reserved, pj.tiles_x, pj.tiles_y);
+            e->pack_cnt[0] += (int64_t)std::max(0, rc.tx1 - rc.tx0) * std::max(0, rc.ty1 - rc.ty0);
+            e->pack_cnt[1] += view_tiles;
+        } else {
+            e->pack_cnt[3] += view_tiles;
+        }
+    }
     LaunchTimer ltp{e, SC_KERNEL_PACK};
     rc = ltp.begin();
     if (rc) return rc;
@@ -86,6 +158,7 @@ int pack_deferred(sc_engine *e, size_t nv, Ride *r) {
         if (rb > 0x3fffffffLL) return fail(SC_ERR_INVALID, "mask batch too large");
         r->blocks = (uint32_t)rb;
         r->packed_ahead = ahead;
+        e->pack_cnt_riders = true;  // pack_cnt[2] is on the device (ListCtl::rider_tiles)
     }
     return SC_OK;
 }

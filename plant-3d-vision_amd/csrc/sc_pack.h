@@ -37,6 +37,7 @@ __device__ __forceinline__ uint32_t nonzero_bits16(uint4 q) {
 // the raw view order[s] (the views of a fused carve are packed in the order they will be applied,
 // so that the first few can be packed ahead and the rest beside the dense stage).
 constexpr int kPackOrderMax = 256;
+constexpr int kReachViews = 128;  // slots whose reach rectangle the job carries; later ones take the whole picture
 struct PackJob {
     const uint8_t *raw;
     int64_t row_stride, view_stride;
@@ -49,10 +50,44 @@ struct PackJob {
     uint32_t *cmask;    // per tile: the 4x4 map of its 8x8-pixel cells, [slot][tiles_y][tiles_x] (see ViewDesc)
     int32_t slot0, nslots;
     uint16_t order[kPackOrderMax];
+    int32_t reach_on;   // SC_OPT_PACK_REACH: 0 packs whole pictures
+    uint16_t reach[kReachViews][4];  // tx0, tx1, ty0, ty1 of slot s < kReachViews (ViewDesc::reserved).  In the kernel
+                                     // arguments, for the riders too: a rider that fetched its rectangle from memory
+                                     // (its descriptor, or anything else) cost the dense kernel 15 vector registers --
+                                     // 74 -> 89, a wavefront per SIMD less for the walkers (DESIGN_APPENDIX.md 14)
 };
 
+// (the job is a kernel argument, of the pack kernels and of the dense kernel beside its others: 4 KB is the limit)
+static_assert(sizeof(PackJob) <= 2048, "PackJob must leave the kernels that take it room for their other arguments");
+
+// Tiles [tx0, tx1) x [ty0, ty1) of a picture: what a packer writes of it.  Outside, the arena keeps what an earlier
+// batch left there, and no kernel looks.
+struct TileRect { int tx0, tx1, ty0, ty1; };
+__host__ __device__ __forceinline__ TileRect rect_unpack(uint64_t r, int tiles_x, int tiles_y) {
+    TileRect t{(int)(r & 0xffffu), (int)((r >> 16) & 0xffffu), (int)((r >> 32) & 0xffffu), (int)(r >> 48)};
+    if (t.tx1 == 0) t = TileRect{0, tiles_x, 0, tiles_y};
+    t.tx1 = t.tx1 < tiles_x ? t.tx1 : tiles_x;  // (the packers index the arena by these)
+    t.ty1 = t.ty1 < tiles_y ? t.ty1 : tiles_y;
+    return t;
+}
+// ... of slot `slot` (absolute) of a job
+__device__ __forceinline__ TileRect job_rect(const PackJob &pj, int slot) {
+    if (pj.reach_on == 0 || slot >= kReachViews) return TileRect{0, pj.tiles_x, 0, pj.tiles_y};
+    const uint64_t r = (uint64_t)pj.reach[slot][0] | ((uint64_t)pj.reach[slot][1] << 16) | ((uint64_t)pj.reach[slot][2] << 32) |
+                       ((uint64_t)pj.reach[slot][3] << 48);
+    return rect_unpack(r, pj.tiles_x, pj.tiles_y);
+}
+
+// slot (relative to slot0) of block b; >= nslots: none
+template <int ROWS>
+__device__ __forceinline__ int pack16_slot(const PackJob &pj, uint32_t b) {
+    const uint32_t txb = (uint32_t)(pj.tiles_x + 3) >> 2, tyb = (uint32_t)((pj.tiles_y + ROWS - 1) / ROWS);
+    return (int)(b / (txb * tyb));
+}
+
+// Returns the tiles it packed: those of its panel inside `rc` (nothing else is read or written).
 template <int ROWS>  // tile rows per block: that many 16-byte loads in flight per lane
-__device__ __forceinline__ void pack16_block(const PackJob &pj, uint32_t b) {
+__device__ __forceinline__ uint32_t pack16_block(const PackJob &pj, uint32_t b, const TileRect &rc) {
     __shared__ uint32_t cm_s[ROWS * 4];  // per tile of the block: cells with some foreground | cells with some background << 16
     const int W = pj.W, H = pj.H, tiles_x = pj.tiles_x, tiles_y = pj.tiles_y;
     const uint32_t flip = pj.flip;
@@ -63,7 +98,8 @@ __device__ __forceinline__ void pack16_block(const PackJob &pj, uint32_t b) {
     uint32_t r = b / (uint32_t)txb;
     int by = (int)(r % (uint32_t)tyb);
     int slot = (int)(r / (uint32_t)tyb);
-    if (slot >= pj.nslots) return;  // block-uniform
+    if (slot >= pj.nslots) return 0u;  // block-uniform
+    if (bx * 4 >= rc.tx1 || bx * 4 + 4 <= rc.tx0 || by * ROWS >= rc.ty1 || by * ROWS + ROWS <= rc.ty0) return 0u;  // block-uniform
     slot += pj.slot0;
     const int64_t view = pj.use_order ? (int64_t)pj.order[slot] : (int64_t)slot;
     const uint8_t *raw = pj.raw + view * pj.view_stride;
@@ -73,12 +109,13 @@ __device__ __forceinline__ void pack16_block(const PackJob &pj, uint32_t b) {
     int c = lane & 7;                  // 16-pixel chunk inside the panel
     int u0 = bx * 128 + c * 16;
     int tx = bx * 4 + (c >> 1);
+    const bool in_x = tx >= rc.tx0 && tx < rc.tx1;  // (tx1 <= tiles_x)
     uint4 q[ROWS];
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) {
         int v = (by * ROWS + k) * 32 + row;
         q[k] = make_uint4(flip, flip, flip, flip);  // padding stays background after the flip
-        if (v < H && u0 < W)  // W % 16 == 0: a 16-pixel run is inside the row or outside it
+        if (v < H && u0 < W && in_x && by * ROWS + k >= rc.ty0 && by * ROWS + k < rc.ty1)  // W % 16 == 0: a 16-pixel run is inside the row or outside it
             q[k] = *reinterpret_cast<const uint4 *>(raw + (int64_t)v * pj.row_stride + u0);
     }
     __syncthreads();
@@ -88,7 +125,7 @@ __device__ __forceinline__ void pack16_block(const PackJob &pj, uint32_t b) {
         uint32_t half = nonzero_bits16(make_uint4(q[k].x ^ flip, q[k].y ^ flip, q[k].z ^ flip, q[k].w ^ flip));
         uint32_t other = __shfl_xor(half, 1);
         uint32_t word = half | (other << 16);
-        if ((c & 1) == 0 && tx < tiles_x && ty < tiles_y)
+        if ((c & 1) == 0 && in_x && ty >= rc.ty0 && ty < rc.ty1)  // (ty1 <= tiles_y)
             pj.out[(int64_t)slot * pj.out_view_words + ((int64_t)tx * tiles_y + ty) * 32 + row] = word;  // strip tx, tile ty of it
         // 8x8-pixel cells: this wavefront holds rows 8w .. 8w + 7 of the tile (cell row w), lane 8r + c the
         // pixels 16c .. 16c + 15 of row r -- two cells' worth.  Four ballots; bit c + 8r of each belongs to
@@ -108,18 +145,19 @@ __device__ __forceinline__ void pack16_block(const PackJob &pj, uint32_t b) {
     // written here, nothing for the host to clear
     if (threadIdx.x < ROWS * 4) {
         int ty = by * ROWS + (int)(threadIdx.x >> 2), txo = bx * 4 + (int)(threadIdx.x & 3);
-        if (ty < tiles_y && txo < tiles_x) {
+        if (ty >= rc.ty0 && ty < rc.ty1 && txo >= rc.tx0 && txo < rc.tx1) {
             const uint32_t cm = cm_s[threadIdx.x];
             const int64_t tile = (int64_t)slot * tiles_x * tiles_y + (int64_t)ty * tiles_x + txo;
             pj.occ[tile] = ((cm & 0xffffu) ? 1 : 0) | ((cm >> 16) ? 0 : 2);
             if (pj.cmask != nullptr) pj.cmask[tile] = cm;
         }
     }
+    return (uint32_t)((min(bx * 4 + 4, rc.tx1) - max(bx * 4, rc.tx0)) * (min(by * ROWS + ROWS, rc.ty1) - max(by * ROWS, rc.ty0)));
 }
 
 template <int ROWS>
 __global__ __launch_bounds__(kBlock) void pack16_kernel(PackJob pj) {
-    pack16_block<ROWS>(pj, blockIdx.x);
+    (void)pack16_block<ROWS>(pj, blockIdx.x, job_rect(pj, pack16_slot<ROWS>(pj, blockIdx.x) + pj.slot0));
 }
 
 // The same ingest in BAND form (SC_OPT_PACK_ROWS 0, the default for pictures up to kBandTiles tiles wide): a
@@ -134,14 +172,20 @@ __global__ __launch_bounds__(kBlock) void pack16_kernel(PackJob pj) {
 constexpr int kBandTiles = 64;   // widest picture of the band form: 2048 pixels
 constexpr int kBandPhase = 6;    // 16-byte loads in flight per lane (3, 4, 6, 12: the same within a microsecond)
 
-__device__ __forceinline__ void pack_band_block(const PackJob &pj, uint32_t b) {
+// A band outside `rc` is not packed, one inside only over the rectangle's columns: tasks, LDS image, tile stores and
+// cell maps all start at the rectangle's first tile column.  Returns the tiles it packed.
+__device__ __forceinline__ int pack_band_slot(const PackJob &pj, uint32_t b) { return (int)(b / (uint32_t)pj.tiles_y); }
+
+__device__ __forceinline__ uint32_t pack_band_block(const PackJob &pj, uint32_t b, const TileRect &rc) {
     __shared__ alignas(16) uint32_t band_s[kBandTiles * 32];  // the band's tile words, as they lie in the packed arena
     const int W = pj.W, H = pj.H, tiles_x = pj.tiles_x, tiles_y = pj.tiles_y;
     const uint32_t flip = pj.flip;
     const uint32_t tid = threadIdx.x;
     const int ty = (int)(b % (uint32_t)tiles_y);
     int slot = (int)(b / (uint32_t)tiles_y);
-    if (slot >= pj.nslots) return;  // block-uniform
+    if (slot >= pj.nslots) return 0u;  // block-uniform
+    if (ty < rc.ty0 || ty >= rc.ty1 || rc.tx0 >= rc.tx1) return 0u;  // block-uniform
+    const uint32_t tx0 = (uint32_t)rc.tx0, ntx = (uint32_t)(rc.tx1 - rc.tx0);  // tx1 <= tiles_x
     slot += pj.slot0;
     const int64_t view = pj.use_order ? (int64_t)pj.order[slot] : (int64_t)slot;
     // the band's first byte (block-uniform: a scalar base) and 32-bit offsets from it: 32 rows of a picture are below
@@ -151,10 +195,10 @@ __device__ __forceinline__ void pack_band_block(const PackJob &pj, uint32_t b) {
 #else
     typedef const uint4 *gq_t;
 #endif
-    const char *raw = reinterpret_cast<const char *>(pj.raw) + view * pj.view_stride + (int64_t)ty * 32 * pj.row_stride;
+    const char *raw = reinterpret_cast<const char *>(pj.raw) + view * pj.view_stride + (int64_t)ty * 32 * pj.row_stride + tx0 * 32u;
     const uint32_t stride = (uint32_t)pj.row_stride;
-    const uint32_t cpr = (uint32_t)(W >> 4);       // 16-pixel chunks per row (W % 16 == 0)
-    const uint32_t cprp = 2u * (uint32_t)tiles_x;  // ... rounded up to an even number
+    const uint32_t cpr = (uint32_t)(W >> 4) - 2u * tx0;  // 16-pixel chunks per row from the rectangle's first column (W % 16 == 0)
+    const uint32_t cprp = 2u * ntx;                      // ... of the rectangle (an even number; may reach past the row's end)
     const uint32_t ntasks = 32u * cprp;
     const uint32_t rows_here = (uint32_t)min(32, H - ty * 32);
     // task q = tid + 256 i: row q / cprp, chunk q % cprp, stepped without a division
@@ -182,15 +226,15 @@ __device__ __forceinline__ void pack_band_block(const PackJob &pj, uint32_t b) {
     }
     __syncthreads();
     // the band's tiles: tile tx of it is tile ty of strip tx in the packed arena (8 pieces of 16 bytes each)
-    uint4 *out = reinterpret_cast<uint4 *>(pj.out + (int64_t)slot * pj.out_view_words + (int64_t)ty * 32);
+    uint4 *out = reinterpret_cast<uint4 *>(pj.out + (int64_t)slot * pj.out_view_words + ((int64_t)tx0 * tiles_y + ty) * 32);
     const uint4 *src = reinterpret_cast<const uint4 *>(band_s);
     const uint32_t strip4 = (uint32_t)pj.tiles_y * 8u;  // a strip in 16-byte pieces
-    for (uint32_t i = tid; i < (uint32_t)tiles_x * 8u; i += kBlock) out[(size_t)(i >> 3) * strip4 + (i & 7u)] = src[i];
+    for (uint32_t i = tid; i < ntx * 8u; i += kBlock) out[(size_t)(i >> 3) * strip4 + (i & 7u)] = src[i];
     // The 8x8-pixel cells from the finished words (round 5; until then every task worked out its two cells' flags and
     // sent them to LDS atomics: a third of the packer's instructions): thread 4 t + cy takes cell row cy of tile t --
     // the OR and the AND of its eight words, a byte of them per cell -- and the four threads of a tile join their
     // nibbles.  Padding is background (zero bits): a tile over the picture's edge is never FULL.
-    for (uint32_t t4 = tid; t4 < (uint32_t)tiles_x * 4u; t4 += kBlock) {  // (kBandTiles * 4 == kBlock: one turn)
+    for (uint32_t t4 = tid; t4 < ntx * 4u; t4 += kBlock) {  // (kBandTiles * 4 == kBlock: one turn)
         const uint32_t t = t4 >> 2, cy = t4 & 3u;
         const uint4 a = src[t * 8u + cy * 2u], bq = src[t * 8u + cy * 2u + 1u];
         const uint32_t any = (a.x | a.y) | (a.z | a.w) | (bq.x | bq.y) | (bq.z | bq.w);
@@ -205,14 +249,17 @@ __device__ __forceinline__ void pack_band_block(const PackJob &pj, uint32_t b) {
         cm |= __shfl_xor(cm, 1);
         cm |= __shfl_xor(cm, 2);
         if (cy == 0u) {
-            const int64_t tile = (int64_t)slot * tiles_x * tiles_y + (int64_t)ty * tiles_x + t;
+            const int64_t tile = (int64_t)slot * tiles_x * tiles_y + (int64_t)ty * tiles_x + tx0 + t;
             pj.occ[tile] = ((cm & 0xffffu) ? 1 : 0) | ((cm >> 16) ? 0 : 2);
             if (pj.cmask != nullptr) pj.cmask[tile] = cm;
         }
     }
+    return ntx;
 }
 
-__global__ __launch_bounds__(kBlock) void pack_band_kernel(PackJob pj) { pack_band_block(pj, blockIdx.x); }
+__global__ __launch_bounds__(kBlock) void pack_band_kernel(PackJob pj) {
+    (void)pack_band_block(pj, blockIdx.x, job_rect(pj, pack_band_slot(pj, blockIdx.x) + pj.slot0));
+}
 
 // Masks that arrive from the HOST cross PCIe as bits already (hostpack.h: `pixel != 0` after the optional invert, on
 // host threads, row-major, one word per 32 pixels, 0 beyond the picture).  What is left for the device is a pass over

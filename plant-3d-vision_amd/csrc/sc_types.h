@@ -18,7 +18,12 @@ struct ViewDesc {   // 128 bytes, read with scalar loads (the view index is wave
     const uint32_t *cmask;  // carve, 16-byte pack form: per 32x32 tile the 4x4 map of its 8x8-pixel CELLS -- bits 0..15
                             // "cell holds some foreground", bits 16..31 "cell holds some background" (cell (cx, cy) of
                             // the tile at bit cy * 4 + cx; padding counts as background); null: no cell level
-    uint64_t reserved;
+    uint64_t reserved;   // carve, a batch packed at its flush: the REACH RECTANGLE of the view in 32x32 tiles, four
+                         // uint16 -- tx0 | tx1 << 16 | ty0 << 32 | ty1 << 48, tiles [tx0, tx1) x [ty0, ty1) -- outside of
+                         // which no voxel of the engine can land (reach_rect, sc_flush.inl) and the packed arena holds
+                         // whatever an earlier batch left; tx1 == 0: the whole picture -- also for a view the
+                         // pack job has no room for (PackJob::reach, from where the packers take it: no kernel
+                         // reads it here), which is packed whole.
 };
 static_assert(sizeof(ViewDesc) == 128, "ViewDesc layout");
 // Descriptor `i` (wave-uniform) by SCALAR loads, whatever the compiler knows about the pointer: through the constant
@@ -91,6 +96,7 @@ struct alignas(128) ListCounter {
 __device__ __forceinline__ uint32_t list_count(const ListCounter &c, uint32_t cap) {
     return min(min(c.n, cap), c.cut ? ~c.cut : 0xffffffffu);
 }
+constexpr int kRiderCounters = 8;  // lines the riders' tile count is spread over (ListCtl::rider_tiles)
 struct ListCtl {
     ListCounter count[5][kSub];  // entries appended per sub-list, one set per list stage; set 3: bulk units, set 4:
                                  // their work items
@@ -112,6 +118,8 @@ struct ListCtl {
                                  // atomics on one line serialise at 11 ns each: one counter for all of them (a 64-bit
                                  // add that reserved the live list's places as well) made the flags kernel 25 -> 35 us
                                  // there
+    ListCounter rider_tiles[kRiderCounters];  // 32x32 tiles the riders of the batch packed (sc_pack_counts): one
+                                 // non-returning add per rider block that packs, block b on counter b % 8
 };
 
 // Bricks whose -1 fill is left to the final list stage (see carve_list_kernel).

@@ -24,9 +24,11 @@ KNOBS = {  # (round 6: the sixteen settled tuning keys are retired -- accepted, 
     "SC_OPT_VIEW_BRICK": [0, 1], "SC_OPT_BULK_MIN": [0, 1, 64, 128, 256], "SC_OPT_BULK_FLOOR": [0, 1, 16, 2048, 1 << 30],
     "SC_OPT_UNIT_CULL": [0, 1, 2, 2], "SC_OPT_HOST_PACK": [0, 1, 1], "SC_OPT_BULK_LIVE": [0, 0, 2, 16],
     "SC_OPT_SAFE_KERNELS": [0, 1, 1], "SC_OPT_LATE_ROAD": [0, 1, 1], "SC_OPT_LIST_CAP": [0, 0, 0, 2, 16, 300],
+    "SC_OPT_PACK_REACH": [0, 1, 1],
 }
 
 ranked = 0
+reused = 0
 
 
 def ranks_assembly(sh, origin, vs, views, dv, opts, device_masks, world, part, cap, want, stack, K, R, t):
@@ -90,7 +92,7 @@ def main():
     only = {int(x) for x in os.environ.get("FUZZ_ONLY", "").split(",") if x.strip()}
     bad = 0
     certified_views = uncertified_views = averaged = 0
-    global ranked
+    global ranked, reused
     for c in range(cases):
         shape = (int(rng.integers(2, 24)), int(rng.integers(2, 70)), int(rng.integers(2, 200)))
         kind = str(rng.choice(["plant", "noise", "solid", "empty", "dense"]))
@@ -123,6 +125,12 @@ def main():
         ranks_w = int(rng.integers(2, 9)) if rng.random() < 0.3 else 0
         ranks_part = str(rng.choice(["cyclic", "slab"]))
         ranks_cap = int(rng.choice([16, 64, 4096, 1 << 20]))
+        # the engine of a device batch first carves ANOTHER scene of the same grid and picture size (other masks, a ring
+        # at another distance), then is cleared: the packed arena holds that scene's tiles wherever this one's reach
+        # rectangles (SC_OPT_PACK_REACH) leave it alone
+        reuse = rng.random() < 0.3
+        poison_kind = str(rng.choice(["solid", "noise", "plant"]))
+        poison_rf = float(rng.choice([0.3, 0.8, 1.5, 3.0]))
         ok = True
         if run_it:
             print(f"case {c}: shape {sh} {kind} views {nviews} dv {dv} kw {kw} opts {opts}", flush=True)
@@ -130,11 +138,24 @@ def main():
             stack = np.ascontiguousarray(np.stack([m for _, _, _, m in views]))
             K = np.stack([v[0] for v in views]); R = np.stack([v[1] for v in views]); t = np.stack([v[2] for v in views])
 
+            poison = None
+            if reuse and device_masks:
+                _, _, _, pviews = scenes.make_scene(shape, nviews, poison_kind, **dict(kw, radius_factor=poison_rf))
+                poison = (np.ascontiguousarray(np.stack([m for _, _, _, m in pviews])), np.stack([v[0] for v in pviews]),
+                          np.stack([v[1] for v in pviews]), np.stack([v[2] for v in pviews]))
+                reused += 1
+
             def carve_twice(o):
                 e = nat.Engine(sh, origin, vs, nat.SC_MODE_CARVE, default_value=dv)
                 for k, v in o.items():
                     e.set_option(getattr(nat, k), v)
-                ptr = e.dev_alloc(stack.nbytes); e.dev_upload(ptr, stack)
+                ptr = e.dev_alloc(stack.nbytes)
+                if poison is not None:
+                    e.dev_upload(ptr, poison[0])
+                    e.process_views_device(poison[1], poison[2], poison[3], ptr, *poison[0].shape, nat.SC_MASK_U8)
+                    e.synchronize()
+                    e.clear()
+                e.dev_upload(ptr, stack)
                 gots = []
                 for rnd in range(2):
                     if device_masks:
@@ -224,13 +245,14 @@ def main():
             ea.close()
             averaged += 1
         bad += 0 if ok else 1
-    print(f"{ranked} cases also as the ranks of an N > 1 run through the sparse wire")
+    print(f"{ranked} cases also as the ranks of an N > 1 run through the sparse wire; {reused} on an engine that had carved another scene")
     print(f"{cases} cases ({averaged} with the average kernel too), {bad} with mismatches; {certified_views} certified views, {uncertified_views} not")
     if len(sys.argv) > 3:
         import json
         json.dump({"tool": "tools/fuzz_carve.py", "cases": cases, "seed": int(sys.argv[2]), "cases_with_mismatches": bad,
                    "cases_with_the_average_kernel_too": averaged,
                    "cases_also_as_ranks_through_the_sparse_wire": ranked,
+                   "cases_on_an_engine_that_had_carved_another_scene": reused,
                    "views_on_the_certified_projection_path": certified_views, "views_on_the_general_path": uncertified_views,
                    "knobs": sorted(KNOBS), "scenes": ["plant", "noise", "solid", "empty", "dense"],
                    "checked": "HIP carve (host masks or device batch, fresh volume and a second batch on the stored one) "
