@@ -169,14 +169,9 @@ class SpaceCarveError(RuntimeError):
 
 
 def build(force=False):
-    """Compile ``csrc/spacecarve.hip`` for gfx950 into ``libspacecarve.so`` (in-tree)."""
-    csrc = os.path.join(_PKG_DIR, "csrc")
-    deps = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp")) or f == "Makefile"]
-    deps.append(HEADER_PATH)
-    if (not force and os.path.exists(LIB_PATH)
-            and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
-        return LIB_PATH
-    subprocess.check_call(["make", "-C", os.path.join(_PKG_DIR, "csrc"), "-s", "-B", "all"])
+    """Compile ``csrc/*.hip`` for gfx950 into ``libspacecarve.so`` (in-tree).  ``csrc/Makefile`` names what the library
+    depends on and so decides whether it is stale; ``force`` rebuilds it regardless."""
+    subprocess.check_call(["make", "-C", os.path.join(_PKG_DIR, "csrc"), "-s"] + (["-B"] if force else []) + ["all"])
     return LIB_PATH
 
 
@@ -298,10 +293,12 @@ def last_error():
     return b.string(b.call("sc_last_error"))
 
 
-def check(rc, what):
+def check(rc, what, last_error="sc_last_error"):
+    """Raise for a failed call ``what``; ``last_error`` names the error getter of the unit that returned ``rc``."""
     if rc == SC_OK:
         return
-    msg = f"{what}: {last_error()} (code {rc})"
+    b = backend()
+    msg = f"{what}: {b.string(b.call(last_error))} (code {rc})"
     if rc == SC_ERR_INVALID:
         raise ValueError(msg)
     if rc == SC_ERR_NOMEM:

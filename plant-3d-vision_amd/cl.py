@@ -21,6 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _native as nat
+from .proc3d import release_device_buffers
 
 logger = logging.getLogger(__name__)
 
@@ -589,7 +590,6 @@ class Backprojection(object):
             self._engine.close()
             self._engine = None
             try:  # the consumer's cached device buffers go with the volume they were sized for
-                nat.backend().call("sc_vol2pcd_release")
-                nat.backend().call("sc_dbscan_release")
+                release_device_buffers()
             except Exception:
                 pass

@@ -22,22 +22,14 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <mutex>
 
-#include "spacecarve.h"
+#include "sc_unit.h"
 
 namespace {
 
 constexpr int kB = 256;
 
-thread_local char g_derr[256];
-int fail_d(int code, const char *msg) {
-    strncpy(g_derr, msg, sizeof g_derr - 1);
-    g_derr[sizeof g_derr - 1] = 0;
-    return code;
-}
+thread_local UnitError g_err;
 
 // ---- the cell grid ---------------------------------------------------------------------------------------------
 // Cell of a coordinate: c = floor(clamp(q, -2^40, 2^40)) with q = fl(fl(x - a) / edge), a = the coordinate of point
@@ -247,47 +239,31 @@ __global__ __launch_bounds__(kB) void dbscan_labels_kernel(int P, const int *__r
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
-// Work buffers are kept per device and grow as needed (the model of masks_rgb.hip): calls are serialised by the
-// slot's mutex while they enqueue, and each waits on the device, through the slot's event, for the call before it.
-struct Slot {
-    std::mutex mu;
-    char *base = nullptr;
-    size_t cap = 0;
-    hipEvent_t last = nullptr;
-    bool checked = false;
-};
-Slot g_slots[64];
-
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-#define D_TRY(expr)                                                                \
-    do {                                                                           \
-        hipError_t _e = (expr);                                                    \
-        if (_e != hipSuccess) { rc = fail_d(_e == hipErrorOutOfMemory ? SC_ERR_NOMEM : SC_ERR_DEVICE, hipGetErrorString(_e)); goto done; } \
-    } while (0)
+// Work buffers are kept per device: the slot protocol of sc_unit.h.
+WorkSlot g_slots[kUnitDevices];
 
 }  // namespace
 
 extern "C" {
 
-const char *sc_dbscan_last_error(void) { return g_derr; }
+const char *sc_dbscan_last_error(void) { return g_err.msg; }
 
 int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps, int64_t min_points, int device,
               int32_t *labels_out, int labels_on_device, int32_t *nclusters_out, void *hip_stream) {
     // every argument is judged before the first device call
-    if (!points || !labels_out) return fail_d(SC_ERR_INVALID, "null argument (points, labels_out)");
-    if (P < 0 || P >= ((int64_t)1 << 31)) return fail_d(SC_ERR_INVALID, "P must be 0 .. 2^31 - 1");
-    if (!std::isfinite(eps) || !(eps > 0.0)) return fail_d(SC_ERR_INVALID, "eps must be finite and positive");
+    if (!points || !labels_out) return g_err.fail(SC_ERR_INVALID, "null argument (points, labels_out)");
+    if (P < 0 || P >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "P must be 0 .. 2^31 - 1");
+    if (!std::isfinite(eps) || !(eps > 0.0)) return g_err.fail(SC_ERR_INVALID, "eps must be finite and positive");
     if (!(eps * eps >= DBL_MIN) || !std::isfinite(eps * eps))
-        return fail_d(SC_ERR_INVALID, "eps * eps must be a normal number (eps out of range)");
-    if (min_points < 0) return fail_d(SC_ERR_INVALID, "min_points must not be negative");
-    if (device < 0 || device >= 64) return fail_d(SC_ERR_INVALID, "device ordinal out of range");
+        return g_err.fail(SC_ERR_INVALID, "eps * eps must be a normal number (eps out of range)");
+    if (min_points < 0) return g_err.fail(SC_ERR_INVALID, "min_points must not be negative");
+    if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
     if (!points_on_device)
         for (int64_t k = 0; k < 3 * P; ++k)
             if (!std::isfinite(points[k])) {
                 char msg[160];
                 snprintf(msg, sizeof msg, "non-finite coordinate in point %lld", (long long)(k / 3));
-                return fail_d(SC_ERR_INVALID, msg);
+                return g_err.fail(SC_ERR_INVALID, msg);
             }
     if (P == 0) {
         if (nclusters_out) *nclusters_out = 0;
@@ -300,7 +276,7 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
     const uint32_t blocks = (uint32_t)((P + kB - 1) / kB);
     const int64_t minp = std::max<int64_t>(min_points, 1);  // a point is its own neighbour: 0 behaves as 1
 
-    Slot &sl = g_slots[device];
+    WorkSlot &sl = g_slots[device];
     std::lock_guard<std::mutex> lock(sl.mu);
     int rc = SC_OK;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -311,49 +287,23 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
     Grid g;
 
     // layout of the work buffer
-    size_t o = 0;
-    const size_t o_hdr = o;    o += 256;                                  // the non-finite flag, nclusters
-    const size_t o_count = o;  o += al256(((size_t)nb + 1) * 4);
-    const size_t o_start = o;  o += al256(((size_t)nb + 1) * 4);
-    const size_t o_cursor = o; o += al256(((size_t)nb + 1) * 4);
-    const size_t o_scell = o;  o += al256((size_t)P * 16);
-    const size_t o_spts = o;   o += al256((size_t)P * 24);
-    const size_t o_core = o;   o += al256((size_t)P);
-    const size_t o_parent = o; o += al256((size_t)P * 4);
-    const size_t o_rootof = o; o += al256((size_t)P * 4);
-    const size_t o_isroot = o; o += al256((size_t)P * 4);
-    const size_t o_rank = o;   o += al256((size_t)P * 4);
-    const size_t o_pts = o;    o += points_on_device ? 0 : al256((size_t)P * 24);
-    const size_t o_lab = o;    o += labels_on_device ? 0 : al256((size_t)P * 4);
-    const size_t o_tmp = o;
+    Layout lay;
+    const size_t o_hdr = lay.take(256);  // the non-finite flag, nclusters
+    const size_t o_count = lay.take(((size_t)nb + 1) * 4), o_start = lay.take(((size_t)nb + 1) * 4),
+                 o_cursor = lay.take(((size_t)nb + 1) * 4);
+    const size_t o_scell = lay.take((size_t)P * 16), o_spts = lay.take((size_t)P * 24), o_core = lay.take((size_t)P);
+    const size_t o_parent = lay.take((size_t)P * 4), o_rootof = lay.take((size_t)P * 4), o_isroot = lay.take((size_t)P * 4),
+                 o_rank = lay.take((size_t)P * 4);
+    const size_t o_pts = lay.take(points_on_device ? 0 : (size_t)P * 24), o_lab = lay.take(labels_on_device ? 0 : (size_t)P * 4);
+    size_t o_tmp = 0;  // the scans' temporary storage: the last buffer, sized below
 
-    D_TRY(hipSetDevice(device));
-    if (!sl.checked) {
-        hipDeviceProp_t prop;
-        D_TRY(hipGetDeviceProperties(&prop, device));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-            return fail_d(SC_ERR_DEVICE, msg);
-        }
-        D_TRY(hipEventCreateWithFlags(&sl.last, hipEventDisableTiming));
-        D_TRY(hipEventRecord(sl.last, stream));
-        sl.checked = true;
-    }
+    UNIT_TRY(hipSetDevice(device));
+    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
     // the scans' temporary storage (a size query: no device work)
-    D_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(nb + 1), stream));
-    D_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (const int *)nullptr, (int *)nullptr, n, stream));
-    {
-        const size_t tmp = std::max(tmp1, tmp2), need = o_tmp + al256(tmp);
-        if (sl.cap < need) {
-            D_TRY(hipEventSynchronize(sl.last));  // nobody reads the old buffers any more
-            if (sl.base) (void)hipFree(sl.base);
-            sl.base = nullptr;
-            sl.cap = 0;
-            D_TRY(hipMalloc(reinterpret_cast<void **>(&sl.base), need));
-            sl.cap = need;
-        }
-    }
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(nb + 1), stream));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (const int *)nullptr, (int *)nullptr, n, stream));
+    o_tmp = lay.take(std::max(tmp1, tmp2));
+    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
     {
         char *const w = sl.base;
         unsigned int *flag = reinterpret_cast<unsigned int *>(w + o_hdr);
@@ -369,18 +319,18 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
         int32_t *lab_d = labels_on_device ? labels_out : reinterpret_cast<int32_t *>(w + o_lab);
         void *tmp_d = w + o_tmp;
 
-        D_TRY(hipStreamWaitEvent(stream, sl.last, 0));  // behind the previous call, whatever its stream was
+        UNIT_TRY(sl.wait(stream));
         if (!points_on_device)
-            D_TRY(hipMemcpyAsync(w + o_pts, points, (size_t)P * 24, hipMemcpyHostToDevice, stream));
-        D_TRY(hipMemsetAsync(flag, 0, 128, stream));
+            UNIT_TRY(hipMemcpyAsync(w + o_pts, points, (size_t)P * 24, hipMemcpyHostToDevice, stream));
+        UNIT_TRY(hipMemsetAsync(flag, 0, 128, stream));
         hipLaunchKernelGGL(dbscan_finite_kernel, dim3(std::min<uint32_t>(blocks, 1024u)), dim3(kB), 0, stream, pts_d, 3 * P, flag);
-        D_TRY(hipGetLastError());
-        D_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, stream));
-        D_TRY(hipMemcpyAsync(anchor, pts_d, 24, hipMemcpyDeviceToHost, stream));
-        D_TRY(hipEventRecord(sl.last, stream));
-        D_TRY(hipStreamSynchronize(stream));
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(hipMemcpyAsync(anchor, pts_d, 24, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(hipStreamSynchronize(stream));
         if (bad != 0u) {  // device points: the first kernel is the judge
-            rc = fail_d(SC_ERR_INVALID, "non-finite coordinate in the device points");
+            rc = g_err.fail(SC_ERR_INVALID, "non-finite coordinate in the device points");
             goto done;
         }
         g.ax = anchor[0];
@@ -390,24 +340,24 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
         g.eps2 = eps * eps;
         g.mask = nb - 1;
 
-        D_TRY(hipMemsetAsync(count, 0, ((size_t)nb + 1) * 4, stream));
+        UNIT_TRY(hipMemsetAsync(count, 0, ((size_t)nb + 1) * 4, stream));
         hipLaunchKernelGGL(dbscan_hist_kernel, dim3(blocks), dim3(kB), 0, stream, pts_d, n, g, count);
-        D_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp1, count, start, (int)(nb + 1), stream));
-        D_TRY(hipMemcpyAsync(cursor, start, (size_t)nb * 4, hipMemcpyDeviceToDevice, stream));
+        UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp1, count, start, (int)(nb + 1), stream));
+        UNIT_TRY(hipMemcpyAsync(cursor, start, (size_t)nb * 4, hipMemcpyDeviceToDevice, stream));
         hipLaunchKernelGGL(dbscan_scatter_kernel, dim3(blocks), dim3(kB), 0, stream, pts_d, n, g, cursor, scell, spts, parent, rootof,
                            isroot);
         hipLaunchKernelGGL(dbscan_core_kernel, dim3(blocks), dim3(kB), 0, stream, n, g, minp, start, scell, spts, core);
         hipLaunchKernelGGL(dbscan_link_kernel, dim3(blocks), dim3(kB), 0, stream, n, g, start, scell, spts, core, parent);
         hipLaunchKernelGGL(dbscan_flatten_kernel, dim3(blocks), dim3(kB), 0, stream, n, scell, core, parent, rootof, isroot);
         hipLaunchKernelGGL(dbscan_border_kernel, dim3(blocks), dim3(kB), 0, stream, n, g, start, scell, spts, core, rootof);
-        D_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp2, isroot, rank, n, stream));
+        UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp2, isroot, rank, n, stream));
         hipLaunchKernelGGL(dbscan_labels_kernel, dim3(blocks), dim3(kB), 0, stream, n, rootof, isroot, rank, lab_d, ncl_d);
-        D_TRY(hipGetLastError());
-        if (!labels_on_device) D_TRY(hipMemcpyAsync(labels_out, lab_d, (size_t)P * 4, hipMemcpyDeviceToHost, stream));
-        if (nclusters_out) D_TRY(hipMemcpyAsync(&ncl, ncl_d, 4, hipMemcpyDeviceToHost, stream));
-        D_TRY(hipEventRecord(sl.last, stream));
+        UNIT_TRY(hipGetLastError());
+        if (!labels_on_device) UNIT_TRY(hipMemcpyAsync(labels_out, lab_d, (size_t)P * 4, hipMemcpyDeviceToHost, stream));
+        if (nclusters_out) UNIT_TRY(hipMemcpyAsync(&ncl, ncl_d, 4, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(sl.record(stream));
         if (!labels_on_device || nclusters_out) {
-            D_TRY(hipStreamSynchronize(stream));
+            UNIT_TRY(hipStreamSynchronize(stream));
             if (nclusters_out) *nclusters_out = ncl;
         }
     }
@@ -417,20 +367,6 @@ done:
     return rc;
 }
 
-void sc_dbscan_release(void) {
-    int current = -1;
-    const bool restore = hipGetDevice(&current) == hipSuccess;  // the caller's current device stays what it was
-    for (int d = 0; d < 64; ++d) {
-        Slot &sl = g_slots[d];
-        std::lock_guard<std::mutex> lock(sl.mu);
-        if (sl.base && hipSetDevice(d) == hipSuccess) {
-            if (sl.last) (void)hipEventSynchronize(sl.last);
-            (void)hipFree(sl.base);
-            sl.base = nullptr;
-            sl.cap = 0;
-        }
-    }
-    if (restore) (void)hipSetDevice(current);
-}
+void sc_dbscan_release(void) { release_slots(g_slots); }
 
 }  // extern "C"

@@ -9,22 +9,15 @@
 // here each dot product is evaluated left to right without FMA.
 #include <hip/hip_runtime.h>
 
-
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 
-#include "spacecarve.h"
+#include "sc_unit.h"
 
 namespace {
 
 constexpr int kB = 256;
-thread_local char g_lerr[256];
-int fail_l(int code, const char *msg) {
-    strncpy(g_lerr, msg, sizeof g_lerr - 1);
-    g_lerr[sizeof g_lerr - 1] = 0;
-    return code;
-}
+thread_local UnitError g_err;
 
 __global__ __launch_bounds__(kB) void label_points_kernel(const double *__restrict__ pts, int64_t P,
                                                           int L, int V, const double *__restrict__ K,
@@ -67,49 +60,44 @@ __global__ __launch_bounds__(kB) void label_points_kernel(const double *__restri
 
 extern "C" {
 
-const char *sc_label_points_last_error(void) { return g_lerr; }
+const char *sc_label_points_last_error(void) { return g_err.msg; }
 
 int sc_label_points(const double *points, int64_t P, int L, int V, const double *K, const double *R,
                     const double *t, const void *masks, int masks_on_device, int H, int W, int device,
                     double *scores_out, int32_t *labels_out) {
     if (!points || !K || !R || !t || !masks || !scores_out || !labels_out)
-        return fail_l(SC_ERR_INVALID, "null argument");
-    if (P < 0 || L <= 0 || V < 0 || H <= 0 || W <= 0) return fail_l(SC_ERR_INVALID, "bad sizes");
+        return g_err.fail(SC_ERR_INVALID, "null argument");
+    if (P < 0 || L <= 0 || V < 0 || H <= 0 || W <= 0) return g_err.fail(SC_ERR_INVALID, "bad sizes");
     if (P == 0) return SC_OK;
     int rc = SC_OK;
     double *pts_d = nullptr, *K_d = nullptr, *R_d = nullptr, *t_d = nullptr, *sc_d = nullptr;
     int32_t *lab_d = nullptr;
     void *m_d = nullptr;
     const size_t mbytes = (size_t)L * V * H * W;
-#define L_TRY(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess) { rc = fail_l(_e == hipErrorOutOfMemory ? SC_ERR_NOMEM : SC_ERR_DEVICE, hipGetErrorString(_e)); goto done; } \
-    } while (0)
-    L_TRY(hipSetDevice(device));
-    L_TRY(hipMalloc(&pts_d, (size_t)P * 24));
-    L_TRY(hipMalloc(&K_d, (size_t)(V ? V : 1) * 32));
-    L_TRY(hipMalloc(&R_d, (size_t)(V ? V : 1) * 72));
-    L_TRY(hipMalloc(&t_d, (size_t)(V ? V : 1) * 24));
-    L_TRY(hipMalloc(&sc_d, (size_t)L * P * 8));
-    L_TRY(hipMalloc(&lab_d, (size_t)P * 4));
-    L_TRY(hipMemcpy(pts_d, points, (size_t)P * 24, hipMemcpyHostToDevice));
+    UNIT_TRY(hipSetDevice(device));
+    UNIT_TRY(hipMalloc(&pts_d, (size_t)P * 24));
+    UNIT_TRY(hipMalloc(&K_d, (size_t)(V ? V : 1) * 32));
+    UNIT_TRY(hipMalloc(&R_d, (size_t)(V ? V : 1) * 72));
+    UNIT_TRY(hipMalloc(&t_d, (size_t)(V ? V : 1) * 24));
+    UNIT_TRY(hipMalloc(&sc_d, (size_t)L * P * 8));
+    UNIT_TRY(hipMalloc(&lab_d, (size_t)P * 4));
+    UNIT_TRY(hipMemcpy(pts_d, points, (size_t)P * 24, hipMemcpyHostToDevice));
     if (V) {
-        L_TRY(hipMemcpy(K_d, K, (size_t)V * 32, hipMemcpyHostToDevice));
-        L_TRY(hipMemcpy(R_d, R, (size_t)V * 72, hipMemcpyHostToDevice));
-        L_TRY(hipMemcpy(t_d, t, (size_t)V * 24, hipMemcpyHostToDevice));
+        UNIT_TRY(hipMemcpy(K_d, K, (size_t)V * 32, hipMemcpyHostToDevice));
+        UNIT_TRY(hipMemcpy(R_d, R, (size_t)V * 72, hipMemcpyHostToDevice));
+        UNIT_TRY(hipMemcpy(t_d, t, (size_t)V * 24, hipMemcpyHostToDevice));
     }
     if (masks_on_device) {
         m_d = const_cast<void *>(masks);
     } else {
-        L_TRY(hipMalloc(&m_d, mbytes ? mbytes : 1));
-        if (mbytes) L_TRY(hipMemcpy(m_d, masks, mbytes, hipMemcpyHostToDevice));
+        UNIT_TRY(hipMalloc(&m_d, mbytes ? mbytes : 1));
+        if (mbytes) UNIT_TRY(hipMemcpy(m_d, masks, mbytes, hipMemcpyHostToDevice));
     }
     hipLaunchKernelGGL(label_points_kernel, dim3((uint32_t)((P + kB - 1) / kB)), dim3(kB), 0, nullptr, pts_d, P,
                        L, V, K_d, R_d, t_d, static_cast<const uint8_t *>(m_d), H, W, sc_d, lab_d);
-    L_TRY(hipGetLastError());
-    L_TRY(hipMemcpy(scores_out, sc_d, (size_t)L * P * 8, hipMemcpyDeviceToHost));
-    L_TRY(hipMemcpy(labels_out, lab_d, (size_t)P * 4, hipMemcpyDeviceToHost));
+    UNIT_TRY(hipGetLastError());
+    UNIT_TRY(hipMemcpy(scores_out, sc_d, (size_t)L * P * 8, hipMemcpyDeviceToHost));
+    UNIT_TRY(hipMemcpy(labels_out, lab_d, (size_t)P * 4, hipMemcpyDeviceToHost));
 done:
     (void)hipDeviceSynchronize();
     if (!masks_on_device && m_d) (void)hipFree(m_d);
@@ -117,7 +105,6 @@ done:
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     return rc;
-#undef L_TRY
 }
 
 }  // extern "C"

@@ -22,23 +22,15 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <mutex>
 
-#include "spacecarve.h"
+#include "sc_unit.h"
 
 namespace {
 
 constexpr int kB = 256;
 constexpr int kMaxSteps = 32;
 
-thread_local char g_merr[256];
-int fail_m(int code, const char *msg) {
-    strncpy(g_merr, msg, sizeof g_merr - 1);
-    g_merr[sizeof g_merr - 1] = 0;
-    return code;
-}
+thread_local UnitError g_err;
 
 // ---- range: least and greatest byte of each picture ------------------------------------------------------------
 // work[v] = {255 - imin, imax}, zeroed before the launch: both are integer atomic maxima, one pair per block.
@@ -239,19 +231,8 @@ __global__ __launch_bounds__(kB) void masks_dilate_kernel(const unsigned long lo
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
-// Work buffers (bits, tables, ranges) are kept per device and grow as needed.  Calls are serialised by the slot's
-// mutex while they ENQUEUE; a call waits (on the device, through the slot's event) for the previous call's work
-// before it touches the buffers, so calls on different streams of one device never overlap in them.
-struct Slot {
-    std::mutex mu;
-    char *base = nullptr;
-    size_t cap = 0;
-    hipEvent_t last = nullptr;  // recorded behind the latest call's kernels
-    bool checked = false;       // the device is a gfx950
-};
-Slot g_slots[64];
-
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// Work buffers (bits, tables, ranges) are kept per device: the slot protocol of sc_unit.h.
+WorkSlot g_slots[kUnitDevices];
 
 // footprints of masks2d._FOOTPRINTS as 9-bit sets, bit (dy + 1) * 3 + (dx + 1)
 constexpr uint16_t fbit(int dy, int dx) { return (uint16_t)(1u << ((dy + 1) * 3 + (dx + 1))); }
@@ -264,40 +245,34 @@ const uint16_t kFoot[6] = {
     (uint16_t)0x1ff,                                                                  // square
 };
 
-#define M_TRY(expr)                                                                \
-    do {                                                                           \
-        hipError_t _e = (expr);                                                    \
-        if (_e != hipSuccess) { rc = fail_m(_e == hipErrorOutOfMemory ? SC_ERR_NOMEM : SC_ERR_DEVICE, hipGetErrorString(_e)); goto done; } \
-    } while (0)
-
 }  // namespace
 
 extern "C" {
 
-const char *sc_masks_last_error(void) { return g_merr; }
+const char *sc_masks_last_error(void) { return g_err.msg; }
 
 int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, int filter, const double coefs[3],
                       double threshold, const uint8_t *steps, int nsteps, int device, void *hip_stream,
                       void *masks_out, int out_on_device, int32_t *ranges_out) {
     // every argument is judged before the first device call
-    if (!rgb || !masks_out || !coefs) return fail_m(SC_ERR_INVALID, "null argument (rgb, coefs, masks_out)");
-    if (V < 1 || H < 1 || W < 1) return fail_m(SC_ERR_INVALID, "V, H and W must be at least 1");
-    if ((int64_t)3 * H * W >= ((int64_t)1 << 31)) return fail_m(SC_ERR_INVALID, "picture too large: 3 * H * W must be below 2^31");
+    if (!rgb || !masks_out || !coefs) return g_err.fail(SC_ERR_INVALID, "null argument (rgb, coefs, masks_out)");
+    if (V < 1 || H < 1 || W < 1) return g_err.fail(SC_ERR_INVALID, "V, H and W must be at least 1");
+    if ((int64_t)3 * H * W >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "picture too large: 3 * H * W must be below 2^31");
     if (filter != SC_FILTER_LINEAR && filter != SC_FILTER_EXCESS_GREEN)
-        return fail_m(SC_ERR_INVALID, "filter: 0 linear, 1 excess_green");
+        return g_err.fail(SC_ERR_INVALID, "filter: 0 linear, 1 excess_green");
     if (!std::isfinite(coefs[0]) || !std::isfinite(coefs[1]) || !std::isfinite(coefs[2]))
-        return fail_m(SC_ERR_INVALID, "coefficients must be finite");
-    if (!std::isfinite(threshold)) return fail_m(SC_ERR_INVALID, "threshold must be finite");
-    if (nsteps < 0 || nsteps > kMaxSteps) return fail_m(SC_ERR_INVALID, "nsteps must be 0..32");
-    if (nsteps > 0 && !steps) return fail_m(SC_ERR_INVALID, "null argument (steps)");
+        return g_err.fail(SC_ERR_INVALID, "coefficients must be finite");
+    if (!std::isfinite(threshold)) return g_err.fail(SC_ERR_INVALID, "threshold must be finite");
+    if (nsteps < 0 || nsteps > kMaxSteps) return g_err.fail(SC_ERR_INVALID, "nsteps must be 0..32");
+    if (nsteps > 0 && !steps) return g_err.fail(SC_ERR_INVALID, "null argument (steps)");
     Steps st;
     memset(&st, 0, sizeof st);
     st.n = nsteps;
     for (int k = 0; k < nsteps; ++k) {
-        if (steps[k] > SC_FOOT_SQUARE) return fail_m(SC_ERR_INVALID, "step ids are 0..5 (SC_FOOT_*)");
+        if (steps[k] > SC_FOOT_SQUARE) return g_err.fail(SC_ERR_INVALID, "step ids are 0..5 (SC_FOOT_*)");
         st.foot[k] = kFoot[steps[k]];
     }
-    if (device < 0 || device >= 64) return fail_m(SC_ERR_INVALID, "device ordinal out of range");
+    if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
     const int64_t npix = (int64_t)H * W, nbytes = 3 * npix;
     const int Wd = (W + 63) / 64;
     const int segs_per_row = (W + kB - 1) / kB;
@@ -306,42 +281,25 @@ int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, i
     const int64_t rblocks = std::min<int64_t>(kRangeBlocks, (nbytes / 16 + kB * 4 - 1) / (kB * 4) + 1);
     const int tiles_x = (Wd + kTW - 1) / kTW, tiles_y = (H + kTR - 1) / kTR;
     if (fblocks * V > 0x7fffffffLL || (int64_t)tiles_x * tiles_y * V > 0x7fffffffLL)
-        return fail_m(SC_ERR_INVALID, "batch too large for one launch: split it");
+        return g_err.fail(SC_ERR_INVALID, "batch too large for one launch: split it");
 
-    Slot &sl = g_slots[device];
+    WorkSlot &sl = g_slots[device];
     std::lock_guard<std::mutex> lock(sl.mu);
     int rc = SC_OK;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     uint8_t *rgb_d = nullptr, *out_d = nullptr;  // staging of host pointers (this call's own)
-    const size_t o_work = 0, o_rng = al256((size_t)V * 8), o_tab = o_rng + al256((size_t)V * 8),
-                 o_bits = o_tab + al256((size_t)V * 2048), need = o_bits + al256((size_t)V * H * Wd * 8);
+    Layout lay;
+    const size_t o_work = lay.take((size_t)V * 8), o_rng = lay.take((size_t)V * 8), o_tab = lay.take((size_t)V * 2048),
+                 o_bits = lay.take((size_t)V * H * Wd * 8);
     uint32_t *work;
     int32_t *ranges;
     double *table;
     unsigned long long *bits;
     FilterArgs fa{coefs[0], coefs[1], coefs[2], threshold, filter};
 
-    M_TRY(hipSetDevice(device));
-    if (!sl.checked) {
-        hipDeviceProp_t prop;
-        M_TRY(hipGetDeviceProperties(&prop, device));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-            return fail_m(SC_ERR_DEVICE, msg);
-        }
-        M_TRY(hipEventCreateWithFlags(&sl.last, hipEventDisableTiming));
-        M_TRY(hipEventRecord(sl.last, stream));
-        sl.checked = true;
-    }
-    if (sl.cap < need) {
-        M_TRY(hipEventSynchronize(sl.last));  // nobody reads the old buffers any more
-        if (sl.base) (void)hipFree(sl.base);
-        sl.base = nullptr;
-        sl.cap = 0;
-        M_TRY(hipMalloc(reinterpret_cast<void **>(&sl.base), need));
-        sl.cap = need;
-    }
+    UNIT_TRY(hipSetDevice(device));
+    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
+    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
     work = reinterpret_cast<uint32_t *>(sl.base + o_work);
     ranges = reinterpret_cast<int32_t *>(sl.base + o_rng);
     table = reinterpret_cast<double *>(sl.base + o_tab);
@@ -349,16 +307,16 @@ int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, i
     if (rgb_on_device) {
         rgb_d = static_cast<uint8_t *>(const_cast<void *>(rgb));
     } else {
-        M_TRY(hipMalloc(reinterpret_cast<void **>(&rgb_d), (size_t)V * nbytes));
-        M_TRY(hipMemcpyAsync(rgb_d, rgb, (size_t)V * nbytes, hipMemcpyHostToDevice, stream));
+        UNIT_TRY(hipMalloc(reinterpret_cast<void **>(&rgb_d), (size_t)V * nbytes));
+        UNIT_TRY(hipMemcpyAsync(rgb_d, rgb, (size_t)V * nbytes, hipMemcpyHostToDevice, stream));
     }
     if (out_on_device) {
         out_d = static_cast<uint8_t *>(masks_out);
     } else {
-        M_TRY(hipMalloc(reinterpret_cast<void **>(&out_d), (size_t)V * npix));
+        UNIT_TRY(hipMalloc(reinterpret_cast<void **>(&out_d), (size_t)V * npix));
     }
-    M_TRY(hipStreamWaitEvent(stream, sl.last, 0));  // behind the previous call, whatever its stream was
-    M_TRY(hipMemsetAsync(work, 0, (size_t)V * 8, stream));
+    UNIT_TRY(sl.wait(stream));
+    UNIT_TRY(hipMemsetAsync(work, 0, (size_t)V * 8, stream));
     hipLaunchKernelGGL(masks_range_kernel, dim3((uint32_t)(rblocks * V)), dim3(kB), 0, stream, rgb_d, nbytes, (int)rblocks, work);
     hipLaunchKernelGGL(masks_table_kernel, dim3((uint32_t)V), dim3(kB), 0, stream, work, table, ranges);
     if (filter == SC_FILTER_LINEAR)
@@ -369,11 +327,11 @@ int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, i
                            (int64_t)V * nbytes, H, W, Wd, segs_per_row, nseg, (int)fblocks, table, fa, bits);
     hipLaunchKernelGGL(masks_dilate_kernel, dim3((uint32_t)((int64_t)tiles_x * tiles_y * V)), dim3(kB), 0, stream, bits, H, W, Wd,
                        tiles_x, tiles_y, st, out_d);
-    M_TRY(hipGetLastError());
-    if (ranges_out) M_TRY(hipMemcpyAsync(ranges_out, ranges, (size_t)V * 8, hipMemcpyDeviceToHost, stream));
-    if (!out_on_device) M_TRY(hipMemcpyAsync(masks_out, out_d, (size_t)V * npix, hipMemcpyDeviceToHost, stream));
-    M_TRY(hipEventRecord(sl.last, stream));
-    if (ranges_out || !out_on_device || !rgb_on_device) M_TRY(hipStreamSynchronize(stream));
+    UNIT_TRY(hipGetLastError());
+    if (ranges_out) UNIT_TRY(hipMemcpyAsync(ranges_out, ranges, (size_t)V * 8, hipMemcpyDeviceToHost, stream));
+    if (!out_on_device) UNIT_TRY(hipMemcpyAsync(masks_out, out_d, (size_t)V * npix, hipMemcpyDeviceToHost, stream));
+    UNIT_TRY(sl.record(stream));
+    if (ranges_out || !out_on_device || !rgb_on_device) UNIT_TRY(hipStreamSynchronize(stream));
 
 done:
     if (!rgb_on_device || !out_on_device) {
@@ -384,20 +342,6 @@ done:
     return rc;
 }
 
-void sc_masks_release(void) {
-    int current = -1;
-    const bool restore = hipGetDevice(&current) == hipSuccess;  // the caller's current device stays what it was
-    for (int d = 0; d < 64; ++d) {
-        Slot &sl = g_slots[d];
-        std::lock_guard<std::mutex> lock(sl.mu);
-        if (sl.base && hipSetDevice(d) == hipSuccess) {
-            if (sl.last) (void)hipEventSynchronize(sl.last);
-            (void)hipFree(sl.base);
-            sl.base = nullptr;
-            sl.cap = 0;
-        }
-    }
-    if (restore) (void)hipSetDevice(current);
-}
+void sc_masks_release(void) { release_slots(g_slots); }
 
 }  // extern "C"

@@ -22,16 +22,13 @@
 
 #include <hip/hip_runtime.h>
 
-
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "spacecarve.h"
+#include "sc_unit.h"
 
 namespace {
 
@@ -39,7 +36,7 @@ constexpr int kB = 256;
 constexpr uint32_t kFar = 0xffffu;
 constexpr int kBlk = 8;  // activity is tracked per 8x8x8 block of voxels
 
-int fail_v(int code, const char *msg);  // defined below
+thread_local UnitError g_err;
 
 // The work buffers (49 bytes per voxel) are kept between calls while they are small (up to 1 GiB: volumes up
 // to ~280^3) -- allocating and freeing them was 2.8 of a call's 4.6 ms -- one per device, handed out to one
@@ -47,11 +44,11 @@ int fail_v(int code, const char *msg);  // defined below
 // sc_vol2pcd_release() gives them back.
 struct ScratchSlot { char *base = nullptr; size_t cap = 0; bool busy = false; };
 std::mutex g_scratch_mu;
-ScratchSlot g_scratch[64];
+ScratchSlot g_scratch[kUnitDevices];
 
 char *scratch_take(int device, size_t bytes, bool *cached) {
     *cached = false;
-    if (device >= 0 && device < 64) {
+    if (device >= 0 && device < kUnitDevices) {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
         ScratchSlot &sl = g_scratch[device];
         if (!sl.busy) {
@@ -598,26 +595,13 @@ __global__ __launch_bounds__(kB) void chunk_offsets_kernel(const uint32_t *__res
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = carry;
 }
 
-thread_local char g_verr[256];
-int fail_v(int code, const char *msg) {
-    strncpy(g_verr, msg, sizeof g_verr - 1);
-    g_verr[sizeof g_verr - 1] = 0;
-    return code;
-}
-
-#define V_TRY(expr)                                                                \
-    do {                                                                           \
-        hipError_t _e = (expr);                                                    \
-        if (_e != hipSuccess) { rc = fail_v(_e == hipErrorOutOfMemory ? SC_ERR_NOMEM : SC_ERR_DEVICE, hipGetErrorString(_e)); goto done; } \
-    } while (0)
-
 inline uint32_t blocks_for(int64_t n) { return (uint32_t)((n + kB - 1) / kB); }
 
 }  // namespace
 
 extern "C" {
 
-const char *sc_vol2pcd_last_error(void) { return g_verr; }
+const char *sc_vol2pcd_last_error(void) { return g_err.msg; }
 
 void sc_free_host(void *p) { free(p); }
 
@@ -626,17 +610,35 @@ static int reach_of(double level_set_value) {
     return (int)std::ceil(std::fabs(level_set_value) + 1.7321 + 5.0 * 1.7321 + 3.0);
 }
 
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// bytes of the work buffers for `planes` x-planes of ny x nz voxels (the layout below)
-static size_t scratch_bytes(int64_t planes, int64_t ny, int64_t nz) {
-    const int64_t n = planes * ny * nz;
-    const int64_t nbx = (planes + kBlk - 1) / kBlk, nby = (ny + kBlk - 1) / kBlk, nbz = (nz + kBlk - 1) / kBlk;
-    const int64_t nb = nbx * nby * nbz;
-    const int64_t nchunks = planes * ny * ((nz + 1023) / 1024);
-    return al256((size_t)n) + 2 * al256((size_t)nb) + 2 * al256((size_t)nb * 4) + al256((size_t)nbx * nby * 4) + al256(64) +
-           al256((size_t)planes * 8) + al256((size_t)nchunks * 4) + al256((size_t)nchunks * 8) + 6 * al256((size_t)n * 8);
-}
+// The work buffers for `planes` x-planes of ny x nz voxels, one allocation of `bytes`: the offsets of
+// occ | cls | active | block lists (active, halo, columns) | their lengths + shell total | plane sums | counts |
+// offsets | sd | A (g0, g1 then ga) | gb | gx | gy | gz
+struct ScratchLayout {
+    size_t occ, cls, act, la, lh, lc, ln, pl, cnt, off, sd, a, b, gx, gy, gz, bytes;
+    ScratchLayout(int64_t planes, int64_t ny, int64_t nz) {
+        const size_t n = (size_t)(planes * ny * nz);
+        const size_t nbxy = (size_t)(((planes + kBlk - 1) / kBlk) * ((ny + kBlk - 1) / kBlk)), nb = nbxy * (size_t)((nz + kBlk - 1) / kBlk);
+        const size_t nchunks = (size_t)(planes * ny * ((nz + kChunk - 1) / kChunk));
+        Layout lay;
+        occ = lay.take(n);
+        cls = lay.take(nb);
+        act = lay.take(nb);
+        la = lay.take(nb * 4);
+        lh = lay.take(nb * 4);
+        lc = lay.take(nbxy * 4);
+        ln = lay.take(64);
+        pl = lay.take((size_t)planes * 8);
+        cnt = lay.take(nchunks * 4);
+        off = lay.take(nchunks * 8);
+        sd = lay.take(n * 8);
+        a = lay.take(n * 8);
+        b = lay.take(n * 8);
+        gx = lay.take(n * 8);
+        gy = lay.take(n * 8);
+        gz = lay.take(n * 8);
+        bytes = lay.total;
+    }
+};
 
 // The pipeline on x-planes [0, nx) AT HAND -- the whole volume, or a slab of it with its halo: `volume` points at
 // plane `xoff` of the volume, and only the shell voxels of planes [cx0, cx1) at hand are put out.
@@ -666,18 +668,7 @@ static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t n
     uint64_t total = 0;
     uint32_t nlist[3] = {0, 0, 0};
     hipStream_t st = nullptr;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // one scratch allocation:
-    // occ | cls | active | block lists (active, halo) + their lengths + shell total | counts | offsets |
-    // sd | A (g0,g1 then ga) | gb | gx | gy | gz
-    const size_t o_occ = 0, o_cls = o_occ + al((size_t)n), o_act = o_cls + al((size_t)nb),
-                 o_la = o_act + al((size_t)nb), o_lh = o_la + al((size_t)nb * 4), o_lc = o_lh + al((size_t)nb * 4),
-                 o_ln = o_lc + al((size_t)nbx * nby * 4),
-                 o_pl = o_ln + al(64), o_cnt = o_pl + al((size_t)nx * 8), o_off = o_cnt + al((size_t)nchunks * 4),
-                 o_sd = o_off + al((size_t)nchunks * 8), o_a = o_sd + al((size_t)n * 8),
-                 o_b = o_a + al((size_t)n * 8), o_gx = o_b + al((size_t)n * 8),
-                 o_gy = o_gx + al((size_t)n * 8), o_gz = o_gy + al((size_t)n * 8),
-                 bytes = o_gz + al((size_t)n * 8);
+    const ScratchLayout at(nx, ny, nz);
     uint8_t *occ, *cls, *act;
     uint32_t *counts, *g0, *g1, *list_act, *list_halo, *list_cols, *list_n;
     uint64_t *offs_d, *total_d, *plane_d;
@@ -685,29 +676,29 @@ static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t n
     Vol v, vh;
     dim3 block(kB);
 
-    if (nb > 0xffffffffLL || nchunks > 0x7fffffffLL) return fail_v(SC_ERR_INVALID, "volume too large");
-    V_TRY(hipSetDevice(device));
-    scratch = scratch_take(device, bytes, &scratch_cached);
-    if (!scratch) { rc = fail_v(SC_ERR_NOMEM, "device allocation of the work buffers failed"); goto done; }
-    occ = reinterpret_cast<uint8_t *>(scratch + o_occ);
-    cls = reinterpret_cast<uint8_t *>(scratch + o_cls);
-    act = reinterpret_cast<uint8_t *>(scratch + o_act);
-    list_act = reinterpret_cast<uint32_t *>(scratch + o_la);
-    list_halo = reinterpret_cast<uint32_t *>(scratch + o_lh);
-    list_cols = reinterpret_cast<uint32_t *>(scratch + o_lc);
-    list_n = reinterpret_cast<uint32_t *>(scratch + o_ln);
-    total_d = reinterpret_cast<uint64_t *>(scratch + o_ln + 16);
-    plane_d = reinterpret_cast<uint64_t *>(scratch + o_pl);
-    counts = reinterpret_cast<uint32_t *>(scratch + o_cnt);
-    offs_d = reinterpret_cast<uint64_t *>(scratch + o_off);
-    sd = reinterpret_cast<double *>(scratch + o_sd);
-    ga = reinterpret_cast<double *>(scratch + o_a);
-    g0 = reinterpret_cast<uint32_t *>(scratch + o_a);
+    if (nb > 0xffffffffLL || nchunks > 0x7fffffffLL) return g_err.fail(SC_ERR_INVALID, "volume too large");
+    UNIT_TRY(hipSetDevice(device));
+    scratch = scratch_take(device, at.bytes, &scratch_cached);
+    if (!scratch) { rc = g_err.fail(SC_ERR_NOMEM, "device allocation of the work buffers failed"); goto done; }
+    occ = reinterpret_cast<uint8_t *>(scratch + at.occ);
+    cls = reinterpret_cast<uint8_t *>(scratch + at.cls);
+    act = reinterpret_cast<uint8_t *>(scratch + at.act);
+    list_act = reinterpret_cast<uint32_t *>(scratch + at.la);
+    list_halo = reinterpret_cast<uint32_t *>(scratch + at.lh);
+    list_cols = reinterpret_cast<uint32_t *>(scratch + at.lc);
+    list_n = reinterpret_cast<uint32_t *>(scratch + at.ln);
+    total_d = reinterpret_cast<uint64_t *>(scratch + at.ln + 16);
+    plane_d = reinterpret_cast<uint64_t *>(scratch + at.pl);
+    counts = reinterpret_cast<uint32_t *>(scratch + at.cnt);
+    offs_d = reinterpret_cast<uint64_t *>(scratch + at.off);
+    sd = reinterpret_cast<double *>(scratch + at.sd);
+    ga = reinterpret_cast<double *>(scratch + at.a);
+    g0 = reinterpret_cast<uint32_t *>(scratch + at.a);
     g1 = g0 + n;
-    gb = reinterpret_cast<double *>(scratch + o_b);
-    gx = reinterpret_cast<double *>(scratch + o_gx);
-    gy = reinterpret_cast<double *>(scratch + o_gy);
-    gz = reinterpret_cast<double *>(scratch + o_gz);
+    gb = reinterpret_cast<double *>(scratch + at.b);
+    gx = reinterpret_cast<double *>(scratch + at.gx);
+    gy = reinterpret_cast<double *>(scratch + at.gy);
+    gz = reinterpret_cast<double *>(scratch + at.gz);
     v = Vol{(int)nx, (int)ny, (int)nz, nby, nbz, act, list_act, list_cols, xoff, cx0, cx1};
     vh = Vol{(int)nx, (int)ny, (int)nz, nby, nbz, act, list_halo, list_cols, xoff, cx0, cx1};
     if (pk != nullptr) {
@@ -715,8 +706,8 @@ static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t n
     } else if (on_device) {
         vol_d = const_cast<void *>(volume);
     } else {
-        V_TRY(hipMalloc(&vol_d, (size_t)n * esz));
-        V_TRY(hipMemcpy(vol_d, volume, (size_t)n * esz, hipMemcpyHostToDevice));
+        UNIT_TRY(hipMalloc(&vol_d, (size_t)n * esz));
+        UNIT_TRY(hipMemcpy(vol_d, volume, (size_t)n * esz, hipMemcpyHostToDevice));
     }
     if (pk != nullptr) {
         if (pk->bits == 2) hipLaunchKernelGGL(occ_packed_kernel<2>, dim3(blocks_for((n + 15) / 16)), block, 0, st, *pk, occ, n, (uint64_t)ny * (uint64_t)nz, (uint32_t)xoff);
@@ -730,15 +721,15 @@ static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t n
     }
     hipLaunchKernelGGL(block_class_kernel, dim3(blocks_for(nb)), block, 0, st, occ, (int)nx, (int)ny, (int)nz, nbx, nby, nbz, cls);
     hipLaunchKernelGGL(block_active_kernel, dim3(blocks_for(nb)), block, 0, st, cls, nbx, nby, nbz, rb, act);
-    V_TRY(hipMemsetAsync(list_n, 0, 64, st));
+    UNIT_TRY(hipMemsetAsync(list_n, 0, 64, st));
     hipLaunchKernelGGL(block_lists_kernel, dim3(blocks_for(nb)), block, 0, st, act, nbx, nby, nbz, rb, list_act,
                        list_halo, list_n);
     hipLaunchKernelGGL(column_list_kernel, dim3(blocks_for((int64_t)nbx * nby)), block, 0, st, act, nbx * nby, nbz,
                        list_cols, list_n + 2);
-    V_TRY(hipMemsetAsync(counts, 0, (size_t)nchunks * 4, st));  // rows the shell kernels skip count nothing
-    V_TRY(hipGetLastError());
+    UNIT_TRY(hipMemsetAsync(counts, 0, (size_t)nchunks * 4, st));  // rows the shell kernels skip count nothing
+    UNIT_TRY(hipGetLastError());
     // the only host round trip before the result: how many blocks the per-voxel kernels walk
-    V_TRY(hipMemcpy(nlist, list_n, sizeof nlist, hipMemcpyDeviceToHost));
+    UNIT_TRY(hipMemcpy(nlist, list_n, sizeof nlist, hipMemcpyDeviceToHost));
     if (nlist[0] > 0) {
         const dim3 ga_(nlist[0]);
         // halo blocks hold (far, far) in both EDT buffers; other inactive voxels are never read
@@ -746,7 +737,7 @@ static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t n
         hipLaunchKernelGGL(edt_z_kernel, ga_, block, 0, st, occ, g0, v, R);
         hipLaunchKernelGGL(edt_y_kernel, ga_, block, 0, st, g0, g1, v, R);
         hipLaunchKernelGGL(edt_x_kernel, ga_, block, 0, st, g1, occ, sd, v, R);
-        V_TRY(hipGetLastError());
+        UNIT_TRY(hipGetLastError());
         // gradient along each axis, then gaussian_filter: axes 0, 1, 2 in turn (proc3d.py:525-531)
         hipLaunchKernelGGL(gradient_kernel<0>, ga_, block, 0, st, sd, ga, v);
         hipLaunchKernelGGL(gauss_kernel<0>, ga_, block, 0, st, ga, gb, v, gw);
@@ -760,26 +751,26 @@ static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t n
         hipLaunchKernelGGL(gauss_kernel<0>, ga_, block, 0, st, ga, gb, v, gw);
         hipLaunchKernelGGL(gauss_kernel<1>, ga_, block, 0, st, gb, ga, v, gw);
         hipLaunchKernelGGL(gauss_kernel<2>, ga_, block, 0, st, ga, gz, v, gw);
-        V_TRY(hipGetLastError());
+        UNIT_TRY(hipGetLastError());
         const dim3 rows(nlist[2] * 64u, nzseg);
         hipLaunchKernelGGL(shell_count_kernel, rows, block, 0, st, sd, v, lo, hi, counts);
         hipLaunchKernelGGL(plane_sums_kernel, dim3((uint32_t)nx), block, 0, st, counts, ny * (int64_t)nzseg, plane_d);
         hipLaunchKernelGGL(chunk_offsets_kernel, dim3((uint32_t)nx), block, 0, st, counts, ny * (int64_t)nzseg, plane_d,
                            offs_d, total_d);
-        V_TRY(hipGetLastError());
-        V_TRY(hipMemcpy(&total, total_d, sizeof total, hipMemcpyDeviceToHost));
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpy(&total, total_d, sizeof total, hipMemcpyDeviceToHost));
     }
     if (total > 0) {
-        V_TRY(hipMalloc(reinterpret_cast<void **>(&pts_d), (size_t)total * 48));
+        UNIT_TRY(hipMalloc(reinterpret_cast<void **>(&pts_d), (size_t)total * 48));
         nrm_d = pts_d + total * 3;
         hipLaunchKernelGGL(shell_points_kernel, dim3(nlist[2] * 64u, nzseg), block, 0, st, sd, gx, gy, gz, v, lo, hi, level_set_value,
                            origin[0], origin[1], origin[2], voxel_size, counts, offs_d, pts_d, nrm_d);
-        V_TRY(hipGetLastError());
+        UNIT_TRY(hipGetLastError());
         *points_out = static_cast<double *>(malloc((size_t)total * 24));
         *normals_out = static_cast<double *>(malloc((size_t)total * 24));
-        if (!*points_out || !*normals_out) { rc = fail_v(SC_ERR_NOMEM, "host allocation failed"); goto done; }
-        V_TRY(hipMemcpy(*points_out, pts_d, (size_t)total * 24, hipMemcpyDeviceToHost));
-        V_TRY(hipMemcpy(*normals_out, nrm_d, (size_t)total * 24, hipMemcpyDeviceToHost));
+        if (!*points_out || !*normals_out) { rc = g_err.fail(SC_ERR_NOMEM, "host allocation failed"); goto done; }
+        UNIT_TRY(hipMemcpy(*points_out, pts_d, (size_t)total * 24, hipMemcpyDeviceToHost));
+        UNIT_TRY(hipMemcpy(*normals_out, nrm_d, (size_t)total * 24, hipMemcpyDeviceToHost));
     }
     *count = (int64_t)total;
 
@@ -814,18 +805,18 @@ static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t 
                           const double gauss_w[5], int device, double **points_out, double **normals_out,
                           int64_t *count, const PackedIn *pk) {
     if ((!volume && !pk) || !origin || !gauss_w || !points_out || !normals_out || !count)
-        return fail_v(SC_ERR_INVALID, "null argument");
-    if (nx < 2 || ny < 2 || nz < 2) return fail_v(SC_ERR_INVALID, "np.gradient needs at least 2 voxels per axis");
-    if (nx > 65535 || ny > 65535) return fail_v(SC_ERR_INVALID, "x and y are limited to 65535 voxels");
-    if (dtype < 0 || dtype > 3) return fail_v(SC_ERR_INVALID, "volume dtype: 0 int32, 1 float32, 2 float64, 3 uint8");
-    if (!(std::fabs(level_set_value) < 200.0)) return fail_v(SC_ERR_INVALID, "level_set_value out of range");
+        return g_err.fail(SC_ERR_INVALID, "null argument");
+    if (nx < 2 || ny < 2 || nz < 2) return g_err.fail(SC_ERR_INVALID, "np.gradient needs at least 2 voxels per axis");
+    if (nx > 65535 || ny > 65535) return g_err.fail(SC_ERR_INVALID, "x and y are limited to 65535 voxels");
+    if (dtype < 0 || dtype > 3) return g_err.fail(SC_ERR_INVALID, "volume dtype: 0 int32, 1 float32, 2 float64, 3 uint8");
+    if (!(std::fabs(level_set_value) < 200.0)) return g_err.fail(SC_ERR_INVALID, "level_set_value out of range");
     *points_out = *normals_out = nullptr;
     *count = 0;
     const int64_t limit = g_scratch_limit;
     const int H = reach_of(level_set_value) + 8;
     int64_t planes = nx;
-    if (limit > 0 && scratch_bytes(nx, ny, nz) > (size_t)limit) {
-        const size_t per_plane = scratch_bytes(64, ny, nz) / 64 + 1;
+    if (limit > 0 && ScratchLayout(nx, ny, nz).bytes > (size_t)limit) {
+        const size_t per_plane = ScratchLayout(64, ny, nz).bytes / 64 + 1;
         planes = std::max<int64_t>((int64_t)((size_t)limit / per_plane), 2 * H + 8);  // at least 8 planes of its own per slab
     }
     if (planes >= nx)
@@ -850,7 +841,7 @@ static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t 
         double *P = static_cast<double *>(malloc((size_t)total * 24)), *N = static_cast<double *>(malloc((size_t)total * 24));
         if (!P || !N) {
             free(P); free(N);
-            rc = fail_v(SC_ERR_NOMEM, "host allocation failed");
+            rc = g_err.fail(SC_ERR_NOMEM, "host allocation failed");
         } else {
             int64_t at = 0;
             for (size_t k = 0; k < cs.size(); ++k) {
@@ -880,13 +871,13 @@ int sc_vol2pcd(const void *volume, int on_device, int dtype, int64_t nx, int64_t
 int sc_vol2pcd_packed(const void *recv_dev, int64_t rank_bytes, int world, int partition, int bits, int64_t nx,
                       int64_t ny, int64_t nz, const double origin[3], double voxel_size, double level_set_value,
                       const double gauss_w[5], int device, double **points_out, double **normals_out, int64_t *count) {
-    if (!recv_dev) return fail_v(SC_ERR_INVALID, "null argument");
-    if (bits != 1 && bits != 2) return fail_v(SC_ERR_INVALID, "bits must be 1 or 2");
-    if (partition != 0 && partition != 1) return fail_v(SC_ERR_INVALID, "partition: 0 plane-cyclic, 1 slabs");
-    if (world < 1 || nx < world || rank_bytes < 0 || (rank_bytes & 3)) return fail_v(SC_ERR_INVALID, "bad world / stride");
+    if (!recv_dev) return g_err.fail(SC_ERR_INVALID, "null argument");
+    if (bits != 1 && bits != 2) return g_err.fail(SC_ERR_INVALID, "bits must be 1 or 2");
+    if (partition != 0 && partition != 1) return g_err.fail(SC_ERR_INVALID, "partition: 0 plane-cyclic, 1 slabs");
+    if (world < 1 || nx < world || rank_bytes < 0 || (rank_bytes & 3)) return g_err.fail(SC_ERR_INVALID, "bad world / stride");
     const uint64_t pmax = (uint64_t)(nx + world - 1) / world;
     if ((uint64_t)rank_bytes * 8 < pmax * (uint64_t)ny * (uint64_t)nz * (uint64_t)bits)
-        return fail_v(SC_ERR_INVALID, "rank stride too small for its planes");
+        return g_err.fail(SC_ERR_INVALID, "rank stride too small for its planes");
     const PackedIn pk{static_cast<const uint32_t *>(recv_dev), (uint64_t)rank_bytes / 4, (uint32_t)world, (uint32_t)nx,
                       partition == 0 ? 1 : 0, bits};
     return vol2pcd_driver(nullptr, 1, 3, nx, ny, nz, origin, voxel_size, level_set_value, gauss_w, device, points_out,
@@ -895,17 +886,14 @@ int sc_vol2pcd_packed(const void *recv_dev, int64_t rank_bytes, int world, int p
 
 void sc_vol2pcd_release(void) {
     std::lock_guard<std::mutex> lock(g_scratch_mu);
-    int current = -1;
-    const bool restore = hipGetDevice(&current) == hipSuccess;  // the caller's current device stays what it was
-    for (int d = 0; d < 64; ++d) {
+    on_each_device([](int d) {
         ScratchSlot &sl = g_scratch[d];
         if (sl.base && !sl.busy && hipSetDevice(d) == hipSuccess) {
             (void)hipFree(sl.base);
             sl.base = nullptr;
             sl.cap = 0;
         }
-    }
-    if (restore) (void)hipSetDevice(current);
+    });
 }
 
 }  // extern "C"

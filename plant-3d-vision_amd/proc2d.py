@@ -26,18 +26,6 @@ def dilation_steps(n):
     return np.array(steps, dtype=np.uint8)
 
 
-def _check(rc, what):
-    if rc == nat.SC_OK:
-        return
-    b = nat.backend()
-    msg = f"{what}: {b.string(b.call('sc_masks_last_error'))} (code {rc})"
-    if rc == nat.SC_ERR_INVALID:
-        raise ValueError(msg)
-    if rc == nat.SC_ERR_NOMEM:
-        raise MemoryError(msg)
-    raise nat.SpaceCarveError(msg)
-
-
 def masks_from_images(images, type="linear", parameters=(0, 1, 0), threshold=0.3, dilation=0, device=0):
     """``Masks`` on a batch of pictures.
 
@@ -79,12 +67,13 @@ def masks_from_images(images, type="linear", parameters=(0, 1, 0), threshold=0.3
         stream = torch.cuda.current_stream(dev).cuda_stream
         if images.numel() == 0:
             raise ValueError("V, H and W must be at least 1")
-        _check(b.call("sc_masks_from_rgb", images.data_ptr(), 1, *args, int(dev), int(stream), out.data_ptr(), 1, 0),
-               "sc_masks_from_rgb")
+        nat.check(b.call("sc_masks_from_rgb", images.data_ptr(), 1, *args, int(dev), int(stream), out.data_ptr(), 1, 0),
+                  "sc_masks_from_rgb", "sc_masks_last_error")
         return out
     images = np.ascontiguousarray(images)
     out = np.empty((H, W) if single else (V, H, W), dtype=np.uint8)
     if images.size == 0:
         raise ValueError("V, H and W must be at least 1")
-    _check(b.call("sc_masks_from_rgb", nat.addr(images), 0, *args, int(device), 0, nat.addr(out), 0, 0), "sc_masks_from_rgb")
+    nat.check(b.call("sc_masks_from_rgb", nat.addr(images), 0, *args, int(device), 0, nat.addr(out), 0, 0),
+              "sc_masks_from_rgb", "sc_masks_last_error")
     return out

@@ -41,7 +41,7 @@ def gaussian_weights(sigma=1.0, truncate=4.0):
 def release_device_buffers():
     """Give back the device work buffers ``vol2pcd`` keeps between calls (``sc_vol2pcd_release``; it keeps them
     only while they are at most 1 GiB) and those of ``cluster_dbscan`` (``sc_dbscan_release``).
-    ``Backprojection.close`` calls both too."""
+    ``Backprojection.close`` calls this."""
     from . import _native as nat
     nat.backend().call("sc_vol2pcd_release")
     nat.backend().call("sc_dbscan_release")
@@ -114,11 +114,7 @@ def vol2pcd(volume, origin, voxel_size, level_set_value=0, device=0, as_open3d=T
         rc = b.call("sc_vol2pcd", ptr, on_device, code, shape[0], shape[1], shape[2], nat.addr(origin64),
                     float(voxel_size), float(level_set_value), nat.addr(gw), int(device), nat.addr(out),
                     nat.addr(out) + 8, nat.addr(cnt))
-    if rc != 0:
-        msg = b.string(b.call("sc_vol2pcd_last_error"))
-        if rc == nat.SC_ERR_INVALID:
-            raise ValueError(f"sc_vol2pcd: {msg}")
-        raise nat.SpaceCarveError(f"sc_vol2pcd: {msg} (code {rc})")
+    nat.check(rc, "sc_vol2pcd", "sc_vol2pcd_last_error")
     n = int(cnt[0])
     if n:
         # the library's buffers become the arrays (no copy); they are released with the last view
@@ -195,11 +191,7 @@ def label_points(points, cameras, masks, device=0):
     labels = np.zeros(P, dtype=np.int32)
     rc = b.call("sc_label_points", nat.addr(pts), P, L, V, nat.addr(K), nat.addr(R), nat.addr(t), mptr, on_dev,
                 H, W, int(device), nat.addr(scores), nat.addr(labels))
-    if rc != 0:
-        msg = b.string(b.call("sc_label_points_last_error"))
-        if rc == nat.SC_ERR_INVALID:
-            raise ValueError(f"sc_label_points: {msg}")
-        raise nat.SpaceCarveError(f"sc_label_points: {msg} (code {rc})")
+    nat.check(rc, "sc_label_points", "sc_label_points_last_error")
     return labels, scores
 
 
@@ -222,16 +214,6 @@ def cluster_dbscan(points, eps, min_points, device=0):
 
     b = nat.backend()
 
-    def check(rc):
-        if rc == nat.SC_OK:
-            return
-        msg = f"sc_dbscan: {b.string(b.call('sc_dbscan_last_error'))} (code {rc})"
-        if rc == nat.SC_ERR_INVALID:
-            raise ValueError(msg)
-        if rc == nat.SC_ERR_NOMEM:
-            raise MemoryError(msg)
-        raise nat.SpaceCarveError(msg)
-
     if not isinstance(points, np.ndarray) and hasattr(points, "points"):
         points = points.points
     if not isinstance(points, np.ndarray) and hasattr(points, "data_ptr"):  # torch tensor on the device
@@ -244,8 +226,8 @@ def cluster_dbscan(points, eps, min_points, device=0):
         out = torch.empty((P,), dtype=torch.int32, device=points.device)
         if P:
             stream = torch.cuda.current_stream(dev).cuda_stream
-            check(b.call("sc_dbscan", points.data_ptr(), 1, P, float(eps), int(min_points), int(dev), out.data_ptr(), 1, 0,
-                         int(stream)))
+            nat.check(b.call("sc_dbscan", points.data_ptr(), 1, P, float(eps), int(min_points), int(dev), out.data_ptr(), 1, 0,
+                             int(stream)), "sc_dbscan", "sc_dbscan_last_error")
         return out
     pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
     if pts.ndim != 2 or pts.shape[1] != 3:
@@ -255,5 +237,6 @@ def cluster_dbscan(points, eps, min_points, device=0):
     P = pts.shape[0]
     labels = np.full(max(P, 1), -1, dtype=np.int32)
     keep = pts if P else np.zeros((1, 3))  # a valid address for an empty cloud
-    check(b.call("sc_dbscan", nat.addr(keep), 0, P, float(eps), int(min_points), int(device), nat.addr(labels), 0, 0, 0))
+    nat.check(b.call("sc_dbscan", nat.addr(keep), 0, P, float(eps), int(min_points), int(device), nat.addr(labels), 0, 0, 0),
+              "sc_dbscan", "sc_dbscan_last_error")
     return labels[:P]

@@ -217,3 +217,44 @@ def test_non_finite_in_device_points(gpu_device, blobs):
         proc3d.cluster_dbscan(broken, device=gpu_device, **oracle.BLOBS)
     # the call after a refused one is a whole one
     assert np.array_equal(proc3d.cluster_dbscan(torch.from_numpy(cloud).cuda(gpu_device), **oracle.BLOBS).cpu().numpy(), st["labels"])
+
+
+# ---- 11: the life of the work buffers ---------------------------------------------------------------------------
+def _blobs(P, seed):
+    """``oracle.blobs_cloud``'s form with P points: four Gaussian blobs of P / 5 and P / 5 points of uniform noise."""
+    rng = np.random.default_rng(seed)
+    centres = np.array([[0.0, 0.0, 0.0], [6.5, 0.0, 0.0], [0.0, 12.0, 3.0], [10.0, 10.0, -4.0]])
+    parts = [c + rng.normal(scale=1.3, size=(P // 5, 3)) for c in centres]
+    parts.append(rng.uniform(-6.0, 16.0, size=(P - 4 * (P // 5), 3)))
+    return np.ascontiguousarray(np.concatenate(parts))
+
+
+@pytest.mark.gpu
+def test_work_buffers_grow_are_released_and_come_back(gpu_device):
+    """A small cloud, a larger one on another stream that has to replace the work buffers, the small one in the larger
+    buffers, a refused call, the release, and the small one in buffers allocated anew: each the checker's labels."""
+    import torch
+    from plant3dvision_amd import _native as nat
+    small, large = _blobs(300, 41), _blobs(6000, 42)
+    ws, wl = oracle.labels(small, **oracle.BLOBS), oracle.labels(large, **oracle.BLOBS)
+    assert ws.max() >= 0 and (ws == -1).any() and wl.max() >= 1 and (wl == -1).any()
+    nat.backend().call("sc_dbscan_release")  # whatever earlier tests left: the first call allocates
+    ts, tl = torch.from_numpy(small).cuda(gpu_device), torch.from_numpy(large).cuda(gpu_device)
+    side = torch.cuda.Stream(device=gpu_device)
+    side.wait_stream(torch.cuda.current_stream(gpu_device))  # the uploads
+    l1 = proc3d.cluster_dbscan(ts, **oracle.BLOBS)
+    with torch.cuda.stream(side):
+        l2 = proc3d.cluster_dbscan(tl, **oracle.BLOBS)  # grows: waits for the first call before it frees its buffers
+    l3 = proc3d.cluster_dbscan(ts, **oracle.BLOBS)
+    with pytest.raises(ValueError, match="eps must be finite"):
+        proc3d.cluster_dbscan(ts, -1.0, 5)
+    l4 = proc3d.cluster_dbscan(ts, **oracle.BLOBS)
+    side.synchronize()
+    torch.cuda.current_stream(gpu_device).synchronize()
+    assert np.array_equal(l1.cpu().numpy(), ws)
+    assert np.array_equal(l2.cpu().numpy(), wl)
+    assert np.array_equal(l3.cpu().numpy(), ws)
+    assert np.array_equal(l4.cpu().numpy(), ws)
+    nat.backend().call("sc_dbscan_release")
+    assert np.array_equal(proc3d.cluster_dbscan(ts, **oracle.BLOBS).cpu().numpy(), ws)
+    assert np.array_equal(proc3d.cluster_dbscan(small, device=gpu_device, **oracle.BLOBS), ws)  # the host route

@@ -184,3 +184,37 @@ def test_hand_over_to_the_carve(gpu_device):
     want = oracle_c.carve(shape, origin, vs, [(K, R, t, wa[q]) for q, (K, R, t, _) in enumerate(views)])
     assert vols["plant"].dtype == np.int32 and np.array_equal(vols["plant"], want)
     assert len(np.unique(want)) > 1
+
+
+@pytest.mark.gpu
+def test_work_buffers_grow_are_released_and_come_back(gpu_device):
+    """The life of the device's work buffers: a small call, a larger one on another stream that has to replace them
+    while the small call's work may still be running, the small call in the larger buffers, a refused call, the
+    release, and the small call in buffers allocated anew -- each result is the checker's."""
+    import torch
+    rng = np.random.default_rng(70)
+    small = rng.integers(0, 256, size=(1, 33, 70, 3), dtype=np.uint8)
+    large = rng.integers(0, 256, size=(3, 130, 200, 3), dtype=np.uint8)
+    kw = dict(type="linear", parameters=[0, 1, 0], threshold=0.9, dilation=2)
+    ws, wl = (oracle.masks_batch(x, type="linear", parameters=[0, 1, 0], threshold=0.9, dilation_n=2) for x in (small, large))
+    assert 0.05 < (ws != 0).mean() < 0.95 and 0.05 < (wl != 0).mean() < 0.95
+    nat.backend().call("sc_masks_release")  # whatever earlier tests left: the first call allocates
+    ts, tl = torch.from_numpy(small).cuda(gpu_device), torch.from_numpy(large).cuda(gpu_device)
+    side = torch.cuda.Stream(device=gpu_device)
+    side.wait_stream(torch.cuda.current_stream(gpu_device))  # the uploads
+    m1 = proc2d.masks_from_images(ts, **kw)
+    with torch.cuda.stream(side):
+        m2 = proc2d.masks_from_images(tl, **kw)  # grows: waits for the first call before it frees its buffers
+    m3 = proc2d.masks_from_images(ts, **kw)
+    with pytest.raises(ValueError, match="finite"):
+        proc2d.masks_from_images(ts, **dict(kw, threshold=float("nan")))
+    m4 = proc2d.masks_from_images(ts, **kw)
+    side.synchronize()
+    torch.cuda.current_stream(gpu_device).synchronize()
+    assert np.array_equal(m1.cpu().numpy(), ws)
+    assert np.array_equal(m2.cpu().numpy(), wl)
+    assert np.array_equal(m3.cpu().numpy(), ws)
+    assert np.array_equal(m4.cpu().numpy(), ws)
+    nat.backend().call("sc_masks_release")
+    assert np.array_equal(proc2d.masks_from_images(ts, **kw).cpu().numpy(), ws)
+    assert np.array_equal(proc2d.masks_from_images(small, device=gpu_device, **kw), ws)  # the host route

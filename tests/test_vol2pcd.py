@@ -160,3 +160,27 @@ def test_ball_at_1024_cubed_in_slabs(gpu_device):
         assert np.array_equal(res[name].normals.view(np.uint64), whole.normals.view(np.uint64)), name
     rad = np.linalg.norm(whole.points, axis=1)
     assert abs(np.median(rad) - (r - 0.5)) < 1.0
+
+
+def _ball(n):
+    ax = np.arange(n) - n / 2
+    return (ax[:, None, None] ** 2 + ax[None, :, None] ** 2 + ax[None, None, :] ** 2 < (0.3 * n) ** 2).astype(np.float64)
+
+
+@pytest.mark.gpu
+def test_work_buffers_grow_are_released_and_come_back(gpu_device):
+    """A small volume, a larger one that has to replace the cached work buffers, the small one in the larger buffers,
+    a refused call, the release, and the small one in buffers allocated anew: each against the oracle."""
+    from plant3dvision_amd import _native as nat
+    small, large = _ball(20), _ball(40)
+    origin = np.array([-3.0, 2.5, 0.0])
+    nat.backend().call("sc_vol2pcd_release")  # whatever earlier tests left: the first call allocates
+    for k, vol in enumerate((small, large, small)):
+        got = proc3d.vol2pcd(vol, origin, 0.5, 0.0, device=gpu_device, as_open3d=False)
+        assert len(got.points) > 100
+        _check(vol, origin, 0.5, 0.0, got)
+    with pytest.raises(ValueError, match="at least 2 voxels"):
+        proc3d.vol2pcd(np.zeros((1, 4, 4)), origin, 0.5, device=gpu_device)
+    _check(small, origin, 0.5, 0.0, proc3d.vol2pcd(small, origin, 0.5, 0.0, device=gpu_device, as_open3d=False))
+    nat.backend().call("sc_vol2pcd_release")
+    _check(small, origin, 0.5, 0.0, proc3d.vol2pcd(small, origin, 0.5, 0.0, device=gpu_device, as_open3d=False))
