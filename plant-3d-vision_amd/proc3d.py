@@ -67,6 +67,10 @@ def vol2pcd(volume, origin, voxel_size, level_set_value=0, device=0, as_open3d=T
     bricks (1 byte per voxel) and read in place.
     Returns an ``open3d.geometry.PointCloud`` when open3d is importable (and ``as_open3d``),
     else a :class:`PointCloud` with the same ``points`` / ``normals``.
+
+    Deviation: a volume of one class -- nothing above 0.5, or nothing at or below it -- yields an empty
+    cloud at every ``level_set_value``; the reference returns up to 5 points at corner (0, 0, 0) there, an artefact of
+    SciPy's distance transform on an input without a site.
     """
     import ctypes
 

@@ -184,3 +184,331 @@ def test_work_buffers_grow_are_released_and_come_back(gpu_device):
     _check(small, origin, 0.5, 0.0, proc3d.vol2pcd(small, origin, 0.5, 0.0, device=gpu_device, as_open3d=False))
     nat.backend().call("sc_vol2pcd_release")
     _check(small, origin, 0.5, 0.0, proc3d.vol2pcd(small, origin, 0.5, 0.0, device=gpu_device, as_open3d=False))
+
+
+# ---- inputs the tests above never feed: values, nz > 1024, short axes, zero gradients, level sets, one class ----
+#
+# Every volume is built by a helper that the CPU test (what the oracle says the volume exercises) and the GPU tests
+# (the unit against the oracle on it) share.
+
+def _stats(vol, lsv):
+    """What the oracle's own dist and smoothed gradients say about a volume at a level set: the shell voxels, those of
+    them with a gradient norm of exactly zero (proc3d.py:544 drops them), the points kept, the points per 1024-voxel
+    z segment, the smallest non-zero norm on the shell, and the shell's voxel indices."""
+    pts, _, dist, (gx, gy, gz), idx = vol2pcd_oracle.vol2pcd(vol, np.zeros(3), 1.0, lsv)
+    on = (dist > -lsv) & (dist <= -lsv + np.sqrt(3))
+    norm = np.sqrt((gx[on] ** 2 + gy[on] ** 2) + gz[on] ** 2)
+    assert len(idx) == len(pts) == int((norm > 0).sum())
+    nseg = (vol.shape[2] + 1023) // 1024
+    return {"shell": int(on.sum()), "zero": int((norm == 0).sum()), "kept": len(pts),
+            "seg": np.bincount(idx[:, 2] // 1024, minlength=nseg).tolist(),
+            "min_norm": float(norm[norm > 0].min()) if (norm > 0).any() else None, "shell_idx": np.argwhere(on)}
+
+
+def _balls(shape, count, rlo, rhi, seed):
+    rng = np.random.default_rng(seed)
+    g = np.stack(np.meshgrid(*[np.arange(s) for s in shape], indexing="ij"), axis=-1)
+    vol = np.zeros(shape, dtype=np.uint8)
+    for _ in range(count):
+        c = rng.uniform(0, 1, 3) * np.array(shape)
+        r = rng.uniform(rlo, rhi)
+        vol[((g - c) ** 2).sum(-1) < r * r] = 1
+    return vol
+
+
+def _special_values(dtype):
+    half = dtype(0.5)
+    return [half, np.nextafter(half, dtype(1)), np.nextafter(half, dtype(0)), dtype(-0.0), np.finfo(dtype).smallest_subnormal,
+            dtype(-3.0), dtype(7.0), dtype(np.inf), dtype(-np.inf), dtype(np.nan)]
+
+
+_SPECIAL_AT = [(3, 4, 5), (20, 3, 17), (11, 12, 13), (5, 19, 8), (16, 16, 2), (8, 7, 21), (13, 2, 10), (1, 22, 22),
+               (22, 10, 6), (10, 15, 18)]
+
+
+def _value_field(dtype):
+    """An averaging-like volume: a smooth field in [0, 1], 58 % of it above 0.5, with the values a comparison with 0.5
+    can get wrong written over single voxels -- 0.5 itself and its two neighbours in `dtype`, -0.0, a denormal,
+    values outside [0, 1], both infinities and a NaN (not above 0.5, like in the reference)."""
+    from scipy.ndimage import zoom
+    vol = zoom(np.random.default_rng(0).random((6, 6, 6)), 4, order=1).astype(dtype)
+    for at, value in zip(_SPECIAL_AT, _special_values(dtype)):
+        vol[at] = value
+    return vol
+
+
+def _class_pattern():
+    """Blobs as a boolean pattern (21 x 26 x 19, some cut by the border) for the label and dtype cases."""
+    return _balls((21, 26, 19), 7, 2, 7, 11).astype(bool)
+
+
+def _labels(dtype, fg, bg):
+    """The class pattern with the foreground drawn from the labels `fg` and the background from `bg`."""
+    mask = _class_pattern()
+    rng = np.random.default_rng(12)
+    return np.where(mask, rng.choice(fg, mask.shape), rng.choice(bg, mask.shape)).astype(dtype)
+
+
+def _tall():
+    """nz = 2100: three 1024-voxel segments per row; balls everywhere and a box across each segment border."""
+    vol = _balls((9, 10, 2100), 40, 2, 5, 7)
+    vol[3:6, 3:7, 1015:1035] = 1
+    vol[1:8, 2:9, 2040:2056] = 1
+    return vol
+
+
+def _tall_for_slabs():
+    """70 planes of 8 x 1100: more planes than the smallest slab (2H + 8 = 52 at lsv 0, 54 at lsv 1), two segments per
+    row.  Balls and a box, no thin structures: its smallest norm (0.12) clears the 1e-3 bar like the others'."""
+    vol = _balls((70, 8, 1100), 40, 2, 5, 0)
+    vol[30:40, 2:6, 1015:1035] = 1  # across z = 1023 / 1024 and across the slab border
+    return vol
+
+
+_SHORT_SHAPES = [(2, 2, 2), (2, 3, 9), (3, 3, 3), (5, 2, 7), (4, 4, 4), (7, 9, 2), (8, 8, 8), (9, 2, 1030)]
+
+
+def _short(shape):
+    return (np.random.default_rng(sum(shape)).random(shape) < 0.5).astype(np.uint8)
+
+
+def _plate(axis):
+    """A one-voxel plate across the whole volume, normal to `axis`, and a cube: on the plate the distance depends on
+    one coordinate only and is symmetric about the plate, so the smoothed gradient there is exactly zero."""
+    vol = np.zeros((40, 42, 44), dtype=np.uint8)
+    vol[tuple(12 if a == axis else slice(None) for a in range(3))] = 1
+    vol[30:36, 30:36, 30:36] = 1
+    return vol
+
+
+def _cube21():
+    """A centred 5^3 cube in 21^3: by symmetry the gradient at its centre voxel is exactly zero."""
+    vol = np.zeros((21, 21, 21), dtype=np.uint8)
+    vol[8:13, 8:13, 8:13] = 1
+    return vol
+
+
+def _ball_at(shape, centre, radius):
+    g = np.stack(np.meshgrid(*[np.arange(s) for s in shape], indexing="ij"), axis=-1)
+    return (((g - np.array(centre)) ** 2).sum(-1) < radius * radius).astype(np.uint8)
+
+
+def _level_set_ball():
+    return _ball_at((48, 40, 44), (20, 22, 18), 6)
+
+
+def _long_ball():
+    """150 planes for slabs with the halo of lsv = 6.5 (H = R + 8 = 28: slabs of 64 planes, 8 of them their own): every
+    ball spans several slabs' own planes, two sit at the volume's ends."""
+    vol = _ball_at((150, 24, 24), (56, 12, 11), 6)
+    vol |= _ball_at((150, 24, 24), (4, 8, 14), 5)
+    vol |= _ball_at((150, 24, 24), (143, 15, 9), 5)
+    vol |= _ball_at((150, 24, 24), (100, 11, 13), 7)
+    return vol
+
+
+# The expected figures are the oracle's, measured once on the CPU; `min_norm` is a floor (the measured value rounded
+# down) and never less than 1e-3 -- the bar below which a last-bit difference in a gradient, amplified by the
+# normalisation, would exceed _check's rtol of 1e-12 for no practical reason.
+_FIXTURES = {}
+
+
+def _fixture(name, build, lsv, shell, zero, kept, seg, min_norm):
+    assert min_norm is None or min_norm >= 1e-3
+    _FIXTURES[name] = (build, lsv, {"shell": shell, "zero": zero, "kept": kept, "seg": seg}, min_norm)
+
+
+for _dt in (np.float32, np.float64):
+    _fixture(f"values-{_dt.__name__}", lambda _dt=_dt: _value_field(_dt), 0.0, 5233, 0, 5233, [5233], 0.08)
+_fixture("labels-int32", lambda: _labels(np.int32, [1, 2, 255], [-1, 0]), 0.0, 1698, 0, 1698, [1698], 0.16)
+_fixture("labels-uint8", lambda: _labels(np.uint8, [1, 2, 255], [0]), 0.0, 1698, 0, 1698, [1698], 0.16)
+_fixture("tall-0", _tall, 0.0, 5304, 0, 5304, [2311, 2593, 400], 0.20)
+_fixture("tall-1", _tall, 1.0, 10201, 0, 10201, [4439, 5154, 608], 0.24)
+_fixture("tall-slabs-0", _tall_for_slabs, 0.0, 5944, 0, 5944, [4720, 1224], 0.12)
+_fixture("tall-slabs-1", _tall_for_slabs, 1.0, 11657, 0, 11657, [9450, 2207], 0.16)
+for _shape, _n0, _n1, _m0, _m1 in zip(_SHORT_SHAPES, [4, 21, 9, 28, 29, 55, 267, 9155], [7, 54, 27, 69, 63, 126, 498, 18195],
+                                      [1.1, 0.12, 0.18, 0.07, 0.17, 0.03, 0.017, 0.002],
+                                      [1.1, 0.07, 0.05, 0.07, 0.10, 0.03, 0.010, 0.002]):
+    _segs = (lambda n, s=_shape: [n] if s[2] <= 1024 else None)
+    _fixture(f"short-{_shape}-0", lambda s=_shape: _short(s), 0.0, _n0, 0, _n0, _segs(_n0) or [9103, 52], _m0)
+    _fixture(f"short-{_shape}-1", lambda s=_shape: _short(s), 1.0, _n1, 0, _n1, _segs(_n1) or [18090, 105], _m1)
+for _axis, _zero, _kept in ((0, 1848, 4136), (1, 1760, 3960), (2, 1680, 3800)):
+    _fixture(f"plate-{_axis}", lambda a=_axis: _plate(a), 1.0, _zero + _kept, _zero, _kept, [_kept], 0.64)
+_fixture("cube-centre", _cube21, -1.0, 27, 1, 26, [26], 0.42)
+_fixture("cube-centre-only", _cube21, -2.0, 1, 1, 0, [0], None)
+for _lsv, _n, _m in ((-1.0, 344, 0.79), (3.0, 1520, 0.91), (6.5, 2618, 0.97), (13.0, 7471, 0.98)):
+    _fixture(f"ball-lsv{_lsv}", _level_set_ball, _lsv, _n, 0, _n, [_n], _m)
+_fixture("long-ball", _long_ball, 6.5, 7906, 0, 7906, [7906], 0.93)
+
+
+@pytest.mark.parametrize("name", list(_FIXTURES))
+def test_new_volumes_do_their_job_by_the_oracles_account(name):
+    """No GPU: the oracle's dist and gradients say that each volume holds what its GPU test is about."""
+    build, lsv, want, min_norm = _FIXTURES[name]
+    vol = build()
+    assert vol.size < 700_000
+    st = _stats(vol, lsv)
+    assert {k: st[k] for k in want} == want
+    if min_norm is None:
+        assert st["min_norm"] is None and st["kept"] == 0
+    else:
+        assert st["min_norm"] >= min_norm >= 1e-3
+    if name.startswith(("tall", "short-(9, 2, 1030)")):  # nz > 1024: points in every segment, a shell on both sides of every border
+        assert all(n > 0 for n in st["seg"]) and len(st["seg"]) == (vol.shape[2] + 1023) // 1024 >= 2
+        z = st["shell_idx"][:, 2]
+        for border in range(1024, vol.shape[2], 1024):
+            assert (z == border - 1).any() and (z == border).any()
+    if name.startswith(("plate", "cube")):
+        assert st["zero"] > 0
+    if name == "ball-lsv13.0":  # shell voxels on the face z = 0 (one-sided difference, reflection) and within the
+        lo = st["shell_idx"].min(axis=0)  # Gaussian's radius of the face x = 0 (reflection)
+        assert lo[2] == 0 and lo[0] < 4
+
+
+def test_value_field_holds_the_values_around_one_half():
+    for dtype in (np.float32, np.float64):
+        vol = _value_field(dtype)
+        assert vol.dtype == dtype and abs((vol > 0.5).mean() - 0.58) < 0.01
+        got = [vol[at] for at in _SPECIAL_AT]
+        assert got[0] == 0.5 and got[1] > 0.5 and got[2] < 0.5 and float(got[1]) - float(got[2]) < 1e-7
+        assert np.signbit(got[3]) and got[3] == 0 and 0 < got[4] < np.finfo(dtype).tiny
+        assert got[5:9] == [-3.0, 7.0, np.inf, -np.inf] and np.isnan(got[9])
+        assert [bool(g > 0.5) for g in got] == [False, True, False, False, False, False, True, True, False, False]
+    assert set(np.unique(_labels(np.int32, [1, 2, 255], [-1, 0]))) == {-1, 0, 1, 2, 255}
+    assert set(np.unique(_labels(np.uint8, [1, 2, 255], [0]))) == {0, 1, 2, 255}
+
+
+_ONE_CLASS = [(fill, lsv) for fill in (0, 1) for lsv in (0.0, 0.5, 1.0)]
+
+
+@pytest.mark.parametrize("fill,lsv", _ONE_CLASS)
+def test_one_class_volumes_where_the_reference_deviates(fill, lsv):
+    """A volume without foreground, or without background, has no surface, and this unit returns an empty cloud for
+    it.  The reference does not always: scipy's distance_transform_edt on an input without a background
+    voxel behaves as if one sat just outside corner (0, 0, 0), and a few voxels of that corner land on the shell.
+    This pins how far the deviation goes on the oracle's side: a handful of points, all from that corner."""
+    vol = np.full((8, 9, 10), fill, dtype=np.float64)
+    pts, _, _, _, idx = vol2pcd_oracle.vol2pcd(vol, np.zeros(3), 1.0, lsv)
+    assert len(pts) <= 16
+    assert (idx <= 3).all()
+
+
+def _bits_equal(a, b):
+    return (a.points.shape == b.points.shape and np.array_equal(a.points.view(np.uint64), b.points.view(np.uint64))
+            and np.array_equal(a.normals.view(np.uint64), b.normals.view(np.uint64)))
+
+
+_ORIGIN = np.array([1.5, -2.0, 7.0])
+
+
+def _run(vol, lsv, vs=0.5):
+    got = proc3d.vol2pcd(vol, _ORIGIN, vs, lsv, as_open3d=False)
+    assert not np.isnan(got.points).any() and not np.isnan(got.normals).any()
+    return got
+
+
+def _run_and_check(name):
+    build, lsv, want, _ = _FIXTURES[name]
+    vol = build()
+    got = _run(vol, lsv)
+    print(f"{name}: oracle {want['kept']} points, unit {len(got.points)}")
+    _check(vol, _ORIGIN, 0.5, lsv, got)
+    assert len(got.points) == want["kept"]
+    return vol, lsv, got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [n for n in _FIXTURES if n.startswith(("values", "labels"))])
+def test_values_not_just_classes(gpu_device, name):
+    """float32 / float64 fields with 0.5, its neighbours, -0.0, a denormal, infinities and NaN; int32 and uint8 labels
+    other than 0 and 1: the cloud of `volume > 0.5`."""
+    _run_and_check(name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [np.bool_, np.int8, np.int64, np.float16])
+def test_dtypes_the_wrapper_converts(gpu_device, dtype):
+    """bool goes in as its bytes, other dtypes as float64: each gives the cloud of its `> 0.5` mask."""
+    mask = _class_pattern()
+    vol = mask.astype(dtype) if dtype != np.int8 else _labels(np.int8, [1, 2, 127], [-1, 0])
+    assert vol.dtype == dtype and np.array_equal(vol > 0.5, mask)
+    got = _run(vol, 0.0)
+    print(f"{np.dtype(dtype).name}: oracle {_FIXTURES['labels-uint8'][2]['kept']} points, unit {len(got.points)}")
+    _check(vol, _ORIGIN, 0.5, 0.0, got)
+    assert _bits_equal(got, _run(mask.astype(np.float64), 0.0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [np.bool_, np.float32])
+def test_strided_and_fortran_ordered_volumes(gpu_device, dtype):
+    """A view with a stride and a Fortran-ordered copy give the cloud of their C-ordered copy, bit for bit."""
+    base = _labels(np.int32, [1, 2, 255], [-1, 0])
+    base = (base > 0) if dtype == np.bool_ else base.astype(dtype) * dtype(0.375)  # 0.375, 0.75, 95.6; -0.375, 0
+    for vol in (base[::2], base[:, ::2, 1:], np.asfortranarray(base)):
+        assert not vol.flags["C_CONTIGUOUS"]
+        want = _run(np.ascontiguousarray(vol), 0.0)
+        assert len(want.points) > 300
+        assert _bits_equal(_run(vol, 0.0), want)
+        _check(vol, _ORIGIN, 0.5, 0.0, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tall-0", "tall-1"])
+def test_rows_longer_than_one_chunk(gpu_device, name):
+    """nz = 2100: every row is three chunks of the shell kernels, the counts and offsets of all three are used."""
+    _run_and_check(name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tall-slabs-0", "tall-slabs-1", "long-ball"])
+def test_slabs_of_long_rows_and_of_a_wide_halo(gpu_device, name):
+    """In the smallest slabs the halo allows: rows of two chunks (nz = 1100), and the halo of lsv = 6.5 (28 planes, more
+    than any other slab test's) -- bit for bit the cloud of the volume in one piece, which is the oracle's."""
+    build, lsv, want, _ = _FIXTURES[name]
+    vol = build()
+    try:
+        proc3d.set_scratch_limit(0)
+        whole = _run(vol, lsv)
+        proc3d.set_scratch_limit(1)
+        slabs = _run(vol, lsv)
+    finally:
+        proc3d.set_scratch_limit(8 << 30)
+    print(f"{name}: oracle {want['kept']} points, one piece {len(whole.points)}, slabs {len(slabs.points)}")
+    assert _bits_equal(slabs, whole)
+    _check(vol, _ORIGIN, 0.5, lsv, slabs)
+    assert len(whole.points) == want["kept"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lsv", [0, 1])
+@pytest.mark.parametrize("shape", _SHORT_SHAPES, ids=str)
+def test_axes_shorter_than_a_block(gpu_device, shape, lsv):
+    """Axes of 2 to 9 voxels: the Gaussian's reflection wraps more than once, np.gradient's two ends meet, every block
+    is partial; and a row of 1030 beside axes of 9 and 2."""
+    _run_and_check(f"short-{shape}-{lsv}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["plate-0", "plate-1", "plate-2", "cube-centre", "cube-centre-only"])
+def test_shell_voxels_with_a_zero_gradient_are_dropped(gpu_device, name):
+    """Shell voxels whose smoothed gradient is exactly zero (proc3d.py:544): the same ones as in the reference, so the
+    same count and order, and no NaN in what comes back."""
+    vol, lsv, got = _run_and_check(name)
+    assert len(got.points) == _FIXTURES[name][2]["shell"] - _FIXTURES[name][2]["zero"]
+    if name == "cube-centre-only":
+        assert got.points.shape == (0, 3) and got.normals.shape == (0, 3)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lsv", [-1.0, 3.0, 6.5, 13.0])
+def test_level_sets_that_widen_the_reach(gpu_device, lsv):
+    """lsv -1, 3, 6.5, 13: block radii 2, 3, 3, 4; at 13 the shell lies on the volume's faces."""
+    _run_and_check(f"ball-lsv{lsv}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fill,lsv", _ONE_CLASS)
+def test_one_class_volumes_give_an_empty_cloud(gpu_device, fill, lsv):
+    for dtype in (np.uint8, np.float64):
+        got = _run(np.full((8, 9, 10), fill, dtype=dtype), lsv)
+        assert got.points.shape == (0, 3) and got.normals.shape == (0, 3)
