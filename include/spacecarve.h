@@ -552,6 +552,53 @@ const char *sc_dbscan_last_error(void);
  * HIP device is left as it was. */
 void sc_dbscan_release(void);
 
+/*
+ * The two evaluation tasks' counting passes on the GPU.
+ *
+ * sc_eval_voxels: what plant3dvision/tasks/evaluation.py::VoxelsEvaluation.evaluate (:421-477) counts.  pred and gt
+ * are host arrays of L pointers to volumes in C order: the predictions all of shape (nx, ny, nz) and of pred_dtype
+ * (SC_EVAL_F32 / SC_EVAL_F64), the ground truths all of shape (gx, gy, gz), every axis >= the prediction's, and of
+ * gt_dtype (SC_EVAL_F32 / SC_EVAL_F64 / SC_EVAL_U8); only the corner [0:nx, 0:ny, 0:nz] of a ground truth is read.
+ * The volumes are all in host memory (on_device == 0) or all device pointers on `device`, read in place on
+ * hip_stream (NULL = the legacy default stream).  Per voxel, in IEEE binary64 (float32 is widened first):
+ *   m = the first index of the greatest of the L predictions, v1 = that value, v2 = the greatest of the other L - 1;
+ *   the voxel predicts class m iff v1 > min_contrast * v2 and none of its L values is NaN, and no other class.
+ * For every class c other than `background` (an index, or -1 for none), with g = gt_c at the voxel: g > 0.5 counts
+ * into tp (predicted) or fn, g < 0.5 into fp (predicted) or tn; g == 0.5 or NaN counts nowhere.  The reference
+ * hard-codes min_contrast = 10.
+ * counts_out (host): int64 [L][4] = tp, fp, tn, fn; the background's row is zero; gt[background] is not read and
+ * may be NULL.  projection_out (host, may be NULL): uint8 [L][ny][nz], 1 where some x of the column predicts the
+ * class (prediction_c.max(0), :455); the background's plane is zero.  The call returns when both are complete.
+ * Counts are integers: two calls agree exactly.
+ * Host volumes go through in x-slabs of whole planes (for a ground truth whole gy x gz planes) copied into the
+ * unit's work buffer, whose size sc_eval_set_chunk_bytes bounds (default 256 MiB; <= 0 restores the default; one
+ * x-plane of all volumes is taken as one slab even where it is larger).  A slabbed call counts what one piece counts.
+ * Judged before any device call (SC_ERR_INVALID): NULL pointers, L outside 2..32 (the reference fails at L = 1),
+ * dtype codes, background outside -1..L-1, an axis < 1 or >= 2^31, a ground truth smaller than the prediction.
+ *
+ * sc_eval_masks: plant3dvision/metrics.py::MaskEvaluator.evaluate (:246-272) for a stack of pictures.  gt and pred:
+ * uint8 [n][H][W], both on the host or both on `device` (read in place on hip_stream).  Per picture: p = pred != 0
+ * dilated dilation_amount times by the 4-connected cross with background outside the picture (binary_dilation's
+ * default structure and border_value; any amount >= 0), g = gt != 0; counts_out (host): int64 [n][4] in the
+ * reference's order tp, fn, tn, fp.  The call returns when counts_out is complete.  Host pictures go through in
+ * batches of whole pictures within the same bound.  Judged before any device call: NULL pointers, n, H or W < 1,
+ * H W >= 2^31, a negative dilation_amount.
+ *
+ * The work buffers are the library's, one set per device, kept between calls, ordered across streams as
+ * sc_masks_from_rgb's are, given back by sc_eval_release (the caller's current HIP device is left as it was).
+ */
+#define SC_EVAL_F32 1
+#define SC_EVAL_F64 2
+#define SC_EVAL_U8 3
+int sc_eval_voxels(const void *const *pred, int pred_dtype, const void *const *gt, int gt_dtype, int L, int64_t nx, int64_t ny,
+                   int64_t nz, int64_t gx, int64_t gy, int64_t gz, int background, double min_contrast, int on_device, int device,
+                   void *hip_stream, int64_t *counts_out, uint8_t *projection_out);
+int sc_eval_masks(const void *gt, const void *pred, int on_device, int n, int H, int W, int dilation_amount, int device,
+                  void *hip_stream, int64_t *counts_out);
+void sc_eval_set_chunk_bytes(int64_t bytes);
+const char *sc_eval_last_error(void);
+void sc_eval_release(void);
+
 /* Page-locked host memory for the read-back of sc_get_values (no reference counterpart: the
  * reference's values_h is a pageable NumPy array, cl.py:173).  A 512 MiB volume reads back in
  * ~10 ms into such a buffer against ~50 ms into pageable memory, but allocating it takes ~0.1 s

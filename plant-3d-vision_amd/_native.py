@@ -48,6 +48,7 @@ SC_OPT_DENSE_EXTRA = 44
 SC_OPT_SPEC_SHARE, SC_OPT_SPEC_BLOCKS, SC_OPT_LATE_ROAD = 45, 46, 47
 SC_OPT_PACK_REACH = 48
 SC_FILTER_LINEAR, SC_FILTER_EXCESS_GREEN = 0, 1
+SC_EVAL_F32, SC_EVAL_F64, SC_EVAL_U8 = 1, 2, 3
 SC_FOOT = {"t0": 0, "t90": 1, "t180": 2, "t270": 3, "diamond": 4, "square": 5}  # SC_FOOT_*: names of masks2d._FOOTPRINTS
 
 # name -> (restype, [argtypes]); 'p' pointer, 'i' int, 'q' int64, 'f' float, 's' const char*
@@ -134,6 +135,11 @@ _SIGNATURES = {
     "sc_dbscan": ("i", ["p", "i", "q", "d", "q", "i", "p", "i", "p", "p"]),
     "sc_dbscan_last_error": ("s", []),
     "sc_dbscan_release": ("v", []),
+    "sc_eval_voxels": ("i", ["p", "i", "p", "i", "i", "q", "q", "q", "q", "q", "q", "i", "d", "i", "i", "p", "p", "p"]),
+    "sc_eval_masks": ("i", ["p", "p", "i", "i", "i", "i", "i", "i", "p", "p"]),
+    "sc_eval_set_chunk_bytes": ("v", ["q"]),
+    "sc_eval_last_error": ("s", []),
+    "sc_eval_release": ("v", []),
     "sc_create_sharded": ("i", ["p", "q", "q", "q", "p", "f", "i", "f", "p", "i", "i"]),
     "sc_group_destroy": ("v", ["p"]),
     "sc_group_size": ("i", ["p"]),

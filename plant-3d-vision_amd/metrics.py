@@ -1,0 +1,260 @@
+"""The set metrics of the reference (``plant3dvision/metrics.py:98-272``) over the device counting passes
+(``sc_eval_masks`` / ``sc_eval_voxels``, ``csrc/evaluate.hip``).
+
+``SetEvaluator``, ``SetMetrics``, ``MaskEvaluator`` and ``CompareMasks`` keep the reference's names, signatures and
+results; ``MaskEvaluator.evaluate`` counts on the GPU.  ``compare_mask_stacks`` is the batched form a fileset
+comparison calls once per label, ``voxel_confusion`` the counting of ``VoxelsEvaluation.evaluate``
+(``tasks/evaluation.py:421-477``).  The nearest-neighbour and mesh metrics of the reference's module are not here.
+There is no CPU fallback: without the library or a gfx950 device the calls raise.
+"""
+from abc import ABC, abstractmethod
+
+import numpy as np
+
+
+class SetEvaluator(ABC):
+    """Domain-specific comparison of a ground truth with a prediction: ``evaluate`` returns ``(tp, fn, tn, fp)``."""
+
+    @abstractmethod
+    def evaluate(self, groundtruth, prediction):
+        pass
+
+
+class SetMetrics(ABC):
+    """Confusion counts of arrays compared as sets, summed over ``add`` / ``+``; precision, recall and the mean of the
+    per-comparison IoUs (metrics.py:105-204).  A ratio whose denominator is zero is ``None``."""
+
+    def __init__(self, evaluator, groundtruth=None, prediction=None):
+        self.evaluator = evaluator
+        self.tp = 0
+        self.fn = 0
+        self.tn = 0
+        self.fp = 0
+        self._miou = 0
+        self._miou_count = 0
+        if groundtruth is not None and prediction is not None:
+            self._compare(groundtruth, prediction)
+
+    def __add__(self, other):
+        self._update_metrics(other.tp, other.fn, other.tn, other.fp)  # (the other's totals count as ONE comparison)
+        return self
+
+    def add(self, groundtruth, prediction):
+        self._compare(groundtruth, prediction)
+
+    def __str__(self):
+        return str(self.as_dict())
+
+    def as_dict(self):
+        return {"tp": self.tp, "fn": self.fn, "tn": self.tn, "fp": self.fp, "precision": self.precision(),
+                "recall": self.recall(), "miou": self.miou()}
+
+    def _compare(self, groundtruth, prediction):
+        tp, fn, tn, fp = self.evaluator.evaluate(groundtruth, prediction)
+        self._update_metrics(tp, fn, tn, fp)
+
+    def _update_metrics(self, tp, fn, tn, fp):
+        self.tp += tp
+        self.fn += fn
+        self.tn += tn
+        self.fp += fp
+        if (tp + fp + fn) != 0:
+            self._miou += tp / (tp + fp + fn)
+            self._miou_count += 1
+
+    def precision(self):
+        return self.tp / (self.tp + self.fp) if (self.tp + self.fp) != 0 else None
+
+    def recall(self):
+        return self.tp / (self.tp + self.fn) if (self.tp + self.fn) != 0 else None
+
+    def miou(self):
+        return self._miou / self._miou_count if self._miou_count > 0 else None
+
+
+def _picture(a, what):
+    a = np.asarray(a)
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError(f"{what} must be a 2-D uint8 picture (got {a.dtype}, shape {a.shape}): the device route "
+                         f"takes masks only")
+    return a
+
+
+class MaskEvaluator(SetEvaluator):
+    """``MaskEvaluator`` of the reference (metrics.py:242-272) on the GPU: the prediction's non-zero pixels, dilated
+    ``dilation_amount`` times by ``scipy.ndimage.binary_dilation``'s default cross, against the ground truth's
+    non-zero pixels.  Pictures are 2-D uint8 (or bool); anything else -- the reference would dilate a colour picture
+    across its channels -- raises ``ValueError``."""
+
+    def __init__(self, dilation_amount=0, device=0):
+        self.dilation_amount = dilation_amount
+        self.device = device
+
+    def evaluate(self, groundtruth, prediction):
+        self._assert_same_size(groundtruth, prediction)
+        gt, pr = _picture(groundtruth, "groundtruth"), _picture(prediction, "prediction")
+        c = compare_mask_stacks(gt[None], pr[None], self.dilation_amount, device=self.device)[0]
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
+    def _assert_same_size(self, groundtruth, prediction):
+        if np.shape(groundtruth) != np.shape(prediction):
+            raise ValueError("The groundtruth and prediction are different in size: %s vs %s"
+                             % (str(np.shape(groundtruth)), str(np.shape(prediction))))
+
+
+class CompareMasks(SetMetrics):
+    """The metrics of one ground-truth mask against one predicted mask (metrics.py:207-239)."""
+
+    def __init__(self, groundtruth, prediction, dilation_amount=0):
+        super(CompareMasks, self).__init__(MaskEvaluator(dilation_amount), groundtruth, prediction)
+
+
+def _is_tensor(a):
+    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+
+
+def compare_mask_stacks(groundtruths, predictions, dilation_amount=0, device=0):
+    """``MaskEvaluator.evaluate`` for ``n`` pictures in one call (``sc_eval_masks``).
+
+    groundtruths, predictions : uint8 (or bool) ``[n, H, W]``, both NumPy arrays or both contiguous CUDA torch tensors
+        of one device; tensors are read in place on torch's current stream.
+    Returns the NumPy int64 array ``[n, 4]`` of ``tp, fn, tn, fp`` (the reference's order)."""
+    from . import _native as nat
+
+    k = int(dilation_amount)
+    if k < 0:
+        raise ValueError("dilation_amount must not be negative")
+    if _is_tensor(groundtruths) != _is_tensor(predictions):
+        raise ValueError("ground truths and predictions must both be NumPy arrays or both CUDA tensors")
+    b = nat.backend()
+    if _is_tensor(groundtruths):
+        import torch
+        gt, pr = groundtruths, predictions
+        for t in (gt, pr):
+            if t.dtype not in (torch.uint8, torch.bool) or t.dim() != 3 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device masks must be contiguous uint8 CUDA tensors [n, H, W]")
+        if tuple(gt.shape) != tuple(pr.shape) or gt.device != pr.device:
+            raise ValueError("The groundtruth and prediction are different in size: %s vs %s"
+                             % (str(tuple(gt.shape)), str(tuple(pr.shape))))
+        n, H, W = (int(s) for s in gt.shape)
+        dev = gt.device.index
+        gptr, pptr, on_dev, stream = gt.data_ptr(), pr.data_ptr(), 1, torch.cuda.current_stream(dev).cuda_stream
+    else:
+        gt, pr = np.asarray(groundtruths), np.asarray(predictions)
+        if gt.shape != pr.shape:
+            raise ValueError("The groundtruth and prediction are different in size: %s vs %s" % (str(gt.shape), str(pr.shape)))
+        keep = []
+        for a in (gt, pr):
+            if a.dtype == np.bool_:
+                a = a.view(np.uint8)
+            if a.ndim != 3 or a.dtype != np.uint8:
+                raise ValueError("masks must be uint8 [n, H, W]")
+            keep.append(np.ascontiguousarray(a))
+        n, H, W = keep[0].shape
+        dev, gptr, pptr, on_dev, stream = int(device), nat.addr(keep[0]), nat.addr(keep[1]), 0, 0
+    counts = np.zeros((max(n, 1), 4), dtype=np.int64)
+    if n == 0:
+        return counts[:0]
+    if H == 0 or W == 0:
+        raise ValueError("pictures must not be empty")
+    nat.check(b.call("sc_eval_masks", gptr, pptr, on_dev, n, H, W, min(k, 2 ** 31 - 1), dev, int(stream), nat.addr(counts)),
+              "sc_eval_masks", "sc_eval_last_error")
+    return counts
+
+
+def set_chunk_bytes(nbytes):
+    """Largest device work buffer a call with host volumes or host pictures may take (``sc_eval_set_chunk_bytes``;
+    default 256 MiB, ``0`` restores it): larger inputs go through in x-slabs / batches of pictures, same counts."""
+    from . import _native as nat
+    nat.backend().call("sc_eval_set_chunk_bytes", int(nbytes))
+
+
+def voxel_confusion(voxels, groundtruths, background="background", min_contrast=10.0, projections=False, device=0):
+    """The counting of ``VoxelsEvaluation.evaluate`` (tasks/evaluation.py:428-477) on the GPU (``sc_eval_voxels``).
+
+    voxels, groundtruths : dicts ``{label: volume}``.  The classes are the ground truth's keys in their order, as in
+        the reference; every one of them must be in ``voxels``.  Predictions share one shape ``(nx, ny, nz)``, ground
+        truths one shape with every axis at least as long (only their corner ``[0:nx, 0:ny, 0:nz]`` is read).  All
+        volumes are NumPy arrays or all contiguous CUDA torch tensors of one device (read in place on torch's current
+        stream).  Predictions are float32 or float64, ground truths float32, float64 or uint8; bool is viewed as
+        uint8; NumPy arrays of other dtypes are converted to float64 on the host.  Comparisons are in float64.
+    background : the label that is not evaluated (it still takes part in the arg-max), or ``None``.
+    min_contrast : a voxel predicts its arg-max class only if that value exceeds ``min_contrast`` times the greatest
+        other one; the reference hard-codes 10.
+
+    Returns ``{label: {"tp", "fp", "tn", "fn"}}`` (Python ints) for every label but the background -- the reference's
+    ``histograms`` -- and with ``projections=True`` the pair ``(that, {label: uint8 [ny, nz]})``: 1 where some x of
+    the column predicts the label (``prediction_c.max(0)``, :455)."""
+    from . import _native as nat
+
+    labels = list(groundtruths.keys())
+    L = len(labels)
+    if L < 2:
+        raise ValueError("at least two classes are needed (the reference fails with one: its max runs over nothing)")
+    if L > 32:
+        raise ValueError("at most 32 classes")
+    for label in labels:
+        if label not in voxels:
+            raise ValueError(f"label '{label}' of the ground truth is missing from the voxels")
+    pred, gt = [voxels[label] for label in labels], [groundtruths[label] for label in labels]
+    tensors = [_is_tensor(v) for v in pred + gt]
+    if any(tensors) and not all(tensors):
+        raise ValueError("volumes must be all NumPy arrays or all CUDA tensors")
+    bg = labels.index(background) if background in labels else -1
+    codes = {np.dtype(np.float32): nat.SC_EVAL_F32, np.dtype(np.float64): nat.SC_EVAL_F64, np.dtype(np.uint8): nat.SC_EVAL_U8}
+
+    def same(things, what):
+        if any(t != things[0] for t in things):
+            raise ValueError(f"the {what} differ: {sorted(set(str(t) for t in things))}")
+        return things[0]
+
+    if all(tensors):
+        import torch
+        tcodes = {torch.float32: nat.SC_EVAL_F32, torch.float64: nat.SC_EVAL_F64, torch.uint8: nat.SC_EVAL_U8, torch.bool: nat.SC_EVAL_U8}
+        for t in pred + gt:
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 3:
+                raise ValueError("device volumes must be contiguous 3-D CUDA tensors")
+        dev = same([t.device for t in pred + gt], "devices").index
+        pshape = same([tuple(int(s) for s in t.shape) for t in pred], "shapes of the voxels")
+        gshape = same([tuple(int(s) for s in t.shape) for t in gt], "shapes of the ground truths")
+        pdt, gdt = same([t.dtype for t in pred], "dtypes of the voxels"), same([t.dtype for t in gt], "dtypes of the ground truths")
+        if pdt not in (torch.float32, torch.float64) or gdt not in tcodes:
+            raise ValueError("device voxels must be float32 or float64, device ground truths float32, float64, uint8 or bool")
+        pcode, gcode = tcodes[pdt], tcodes[gdt]
+        pptr, gptr = [t.data_ptr() for t in pred], [t.data_ptr() for t in gt]
+        on_dev, stream = 1, torch.cuda.current_stream(dev).cuda_stream
+    else:
+        pred, gt = [np.asarray(v) for v in pred], [np.asarray(v) for v in gt]
+        pshape = same([v.shape for v in pred], "shapes of the voxels")
+        gshape = same([v.shape for v in gt], "shapes of the ground truths")
+        pdt, gdt = same([v.dtype for v in pred], "dtypes of the voxels"), same([v.dtype for v in gt], "dtypes of the ground truths")
+        if len(pshape) != 3 or len(gshape) != 3:
+            raise ValueError("volumes must be 3-D")
+        if pdt not in (np.float32, np.float64):
+            pred = [v.astype(np.float64) for v in pred]
+        if gdt == np.bool_:
+            gt = [v.view(np.uint8) for v in gt]
+        elif gdt not in codes:
+            gt = [v.astype(np.float64) for v in gt]
+        pred, gt = [np.ascontiguousarray(v) for v in pred], [np.ascontiguousarray(v) for v in gt]
+        pcode, gcode = codes[pred[0].dtype], codes[gt[0].dtype]
+        pptr, gptr = [nat.addr(v) for v in pred], [nat.addr(v) for v in gt]
+        dev, on_dev, stream = int(device), 0, 0
+    if any(g < p for g, p in zip(gshape, pshape)):
+        raise ValueError(f"ground truth {gshape} smaller than the prediction {pshape}")
+    if min(pshape) < 1:
+        raise ValueError("volumes must not be empty")
+    pp, gp = np.array(pptr, dtype=np.uintp), np.array(gptr, dtype=np.uintp)
+    counts = np.zeros((L, 4), dtype=np.int64)
+    proj = np.zeros((L, pshape[1], pshape[2]), dtype=np.uint8) if projections else None
+    nat.check(nat.backend().call("sc_eval_voxels", nat.addr(pp), pcode, nat.addr(gp), gcode, L, pshape[0], pshape[1], pshape[2],
+                                 gshape[0], gshape[1], gshape[2], bg, float(min_contrast), on_dev, dev, int(stream),
+                                 nat.addr(counts), nat.addr(proj) if projections else 0),
+              "sc_eval_voxels", "sc_eval_last_error")
+    out = {label: {"tp": int(counts[q, 0]), "fp": int(counts[q, 1]), "tn": int(counts[q, 2]), "fn": int(counts[q, 3])}
+           for q, label in enumerate(labels) if q != bg}
+    if projections:
+        return out, {label: proj[q] for q, label in enumerate(labels) if q != bg}
+    return out

@@ -40,11 +40,13 @@ def gaussian_weights(sigma=1.0, truncate=4.0):
 
 def release_device_buffers():
     """Give back the device work buffers ``vol2pcd`` keeps between calls (``sc_vol2pcd_release``; it keeps them
-    only while they are at most 1 GiB) and those of ``cluster_dbscan`` (``sc_dbscan_release``).
+    only while they are at most 1 GiB), those of ``cluster_dbscan`` (``sc_dbscan_release``) and those of the
+    evaluation counts of ``metrics`` (``sc_eval_release``).
     ``Backprojection.close`` calls this."""
     from . import _native as nat
     nat.backend().call("sc_vol2pcd_release")
     nat.backend().call("sc_dbscan_release")
+    nat.backend().call("sc_eval_release")
 
 
 def set_scratch_limit(nbytes):
