@@ -463,6 +463,13 @@ int sc_vol2pcd(const void *volume, int on_device, int dtype, int64_t nx, int64_t
 int sc_vol2pcd_packed(const void *recv_dev, int64_t rank_bytes, int world, int partition, int bits, int64_t nx,
                       int64_t ny, int64_t nz, const double origin[3], double voxel_size, double level_set_value,
                       const double gauss_w[5], int device, double **points_out, double **normals_out, int64_t *count);
+/* The same for ONE CLASS of a winner volume (sc_select_classes below): winner is uint8 [nx][ny][nz], on the host or on
+ * `device` (on_device != 0, read in place on the device's default stream: the caller has waited for what wrote it);
+ * the occupancy is `winner == cls` (cls 0..255), written by one kernel in front of the unchanged pipeline.  The result
+ * is bit for bit that of sc_vol2pcd on the uint8 volume (winner == cls); slabs as for uint8 (1 byte per voxel). */
+int sc_vol2pcd_class(const uint8_t *winner, int on_device, int cls, int64_t nx, int64_t ny, int64_t nz, const double origin[3],
+                     double voxel_size, double level_set_value, const double gauss_w[5], int device, double **points_out,
+                     double **normals_out, int64_t *count);
 const char *sc_vol2pcd_last_error(void);
 /* sc_vol2pcd keeps its device work buffers (49 bytes per voxel, per device) between calls while they are at most
  * 1 GiB (larger ones are freed when the call ends); this gives back what is kept.  The caller's current HIP
@@ -598,6 +605,42 @@ int sc_eval_masks(const void *gt, const void *pred, int on_device, int n, int H,
 void sc_eval_set_chunk_bytes(int64_t bytes);
 const char *sc_eval_last_error(void);
 void sc_eval_release(void);
+
+/*
+ * The decision step of the multiclass PointCloud task (plant3dvision/tasks/proc3d.py::PointCloud.run :84-115) on the
+ * GPU: L class volumes -> ONE winner volume.  volumes: a host array of L pointers to volumes in C
+ * order, all of shape (nx, ny, nz) and of `dtype` (SC_EVAL_F32 / SC_EVAL_F64 / SC_EVAL_U8), in the order of the
+ * reference's `l = list(voxels.keys())`; `background` is the index of the key 'background', or -1 without one.
+ * The rule, per voxel, every value taken to IEEE binary64 and the background's value multiplied by background_prior
+ * in binary64 first (:89):
+ *   m  = np.argmax over the L values (:93): the first index of the greatest value; if any value is NaN, the index of
+ *        the first NaN;
+ *   v2 = np.max of the other L - 1 values (:110): NaN if any of them is NaN;
+ *   the voxel belongs to class m iff all three hold:
+ *     m != background;
+ *     min_contrast > 1.0 is false, or 1.0 > min_contrast * v2 (product and comparison in binary64; a NaN product
+ *       compares false) (:113-114, where pred_c is the boolean res_idx == i, so `pred_c > x` is `1 > x` where it is
+ *       true and irrelevant where it is false);
+ *     1.0 > min_score (:115);
+ *   it belongs to no other class, and to none if a test fails.
+ * winner: uint8 [nx][ny][nz], the class index m or 255 for "no class": the reference's volume of class c is
+ * `winner == c`.  counts (host, int64 [L]): the voxels of each class, 0 for the background.
+ * volumes and winner are both in host memory (on_device == 0) or both device pointers on `device`, read and written
+ * in place on hip_stream (NULL = the legacy default stream).  The call returns when the counts (and a host winner) are
+ * complete.  Host volumes go through in x-slabs of whole planes copied into the unit's work buffer, whose size
+ * sc_select_set_chunk_bytes bounds (default 256 MiB; <= 0 restores the default; one x-plane of all volumes is taken
+ * as one slab even where it is larger); a slabbed call writes what one piece writes.
+ * Judged before any device call (SC_ERR_INVALID): NULL pointers, L outside 2..32 (with one key the reference takes
+ * its single-volume branch), the dtype code, background outside -1..L-1, an axis < 1 or >= 2^31.
+ * The work buffers are the library's, one set per device, kept between calls, ordered across streams as
+ * sc_masks_from_rgb's are, given back by sc_select_release.  Both leave the caller's current HIP device as it was.
+ */
+int sc_select_classes(const void *const *volumes, int dtype, int L, int background /* index, -1: none */, int64_t nx, int64_t ny,
+                      int64_t nz, double background_prior, double min_contrast, double min_score, int on_device, int device,
+                      void *hip_stream, uint8_t *winner, int64_t *counts /* host, L */);
+void sc_select_set_chunk_bytes(int64_t bytes);
+const char *sc_select_last_error(void);
+void sc_select_release(void);
 
 /* Page-locked host memory for the read-back of sc_get_values (no reference counterpart: the
  * reference's values_h is a pageable NumPy array, cl.py:173).  A 512 MiB volume reads back in

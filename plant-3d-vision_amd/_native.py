@@ -140,6 +140,11 @@ _SIGNATURES = {
     "sc_eval_set_chunk_bytes": ("v", ["q"]),
     "sc_eval_last_error": ("s", []),
     "sc_eval_release": ("v", []),
+    "sc_select_classes": ("i", ["p", "i", "i", "i", "q", "q", "q", "d", "d", "d", "i", "i", "p", "p", "p"]),
+    "sc_select_set_chunk_bytes": ("v", ["q"]),
+    "sc_select_last_error": ("s", []),
+    "sc_select_release": ("v", []),
+    "sc_vol2pcd_class": ("i", ["p", "i", "i", "q", "q", "q", "p", "d", "d", "p", "i", "p", "p", "p"]),
     "sc_create_sharded": ("i", ["p", "q", "q", "q", "p", "f", "i", "f", "p", "i", "i"]),
     "sc_group_destroy": ("v", ["p"]),
     "sc_group_size": ("i", ["p"]),

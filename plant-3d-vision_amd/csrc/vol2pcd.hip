@@ -139,6 +139,26 @@ __global__ __launch_bounds__(kB) void occ_kernel(const T *__restrict__ vol, uint
     }
 }
 
+// a class of a winner volume (class_select.hip): occ = winner == cls, the same 16 voxels per thread
+__global__ __launch_bounds__(kB) void occ_class_kernel(const uint8_t *__restrict__ winner, uint8_t *__restrict__ occ, int64_t n,
+                                                       uint32_t cls) {
+    int64_t i0 = ((int64_t)blockIdx.x * kB + threadIdx.x) * 16;
+    if (i0 >= n) return;
+    if (i0 + 16 <= n && (reinterpret_cast<uintptr_t>(occ) & 15) == 0) {
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t bits = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bits |= ((uint32_t)winner[i0 + q * 4 + e] == cls ? 1u : 0u) << (8 * e);
+            w[q] = bits;
+        }
+        *reinterpret_cast<uint4 *>(occ + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        for (int64_t i = i0; i < min(n, i0 + 16); ++i) occ[i] = (uint32_t)winner[i] == cls ? 1 : 0;
+    }
+}
+
 // The same from carve labels as the ranks of a sharded run leave them after an all-gather: `world` ranks' planes at
 // 2 bits (label & 3) or 1 bit (label == 1) per voxel, rank-major ([world][rank_words] words; plane i of the grid is
 // plane i / world of rank i % world, or plane i - first(r) of the rank whose slab holds it).  A label is one of
@@ -645,7 +665,8 @@ struct ScratchLayout {
 static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t nx, int64_t ny, int64_t nz, int xoff,
                          int cx0, int cx1, const double origin[3], double voxel_size, double level_set_value,
                          const double gauss_w[5], int device, double **points_out, double **normals_out,
-                         int64_t *count, const PackedIn *pk = nullptr) {  // pk: packed labels instead of `volume`
+                         int64_t *count, const PackedIn *pk = nullptr,  // pk: packed labels instead of `volume`
+                         int sel = -1) {  // sel >= 0: `volume` is a winner volume (uint8), the occupancy is winner == sel
     *points_out = *normals_out = nullptr;
     *count = 0;
     const int64_t n = nx * ny * nz;
@@ -712,6 +733,8 @@ static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t n
     if (pk != nullptr) {
         if (pk->bits == 2) hipLaunchKernelGGL(occ_packed_kernel<2>, dim3(blocks_for((n + 15) / 16)), block, 0, st, *pk, occ, n, (uint64_t)ny * (uint64_t)nz, (uint32_t)xoff);
         else hipLaunchKernelGGL(occ_packed_kernel<1>, dim3(blocks_for((n + 15) / 16)), block, 0, st, *pk, occ, n, (uint64_t)ny * (uint64_t)nz, (uint32_t)xoff);
+    } else if (sel >= 0) {
+        hipLaunchKernelGGL(occ_class_kernel, dim3(blocks_for((n + 15) / 16)), block, 0, st, (const uint8_t *)vol_d, occ, n, (uint32_t)sel);
     } else
     switch (dtype) {
         case 0: hipLaunchKernelGGL(occ_kernel<int32_t>, dim3(blocks_for((n + 15) / 16)), block, 0, st, (const int32_t *)vol_d, occ, n); break;
@@ -803,7 +826,7 @@ void sc_vol2pcd_set_scratch_limit(int64_t bytes) { g_scratch_limit = bytes < 0 ?
 static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t nx, int64_t ny, int64_t nz,
                           const double origin[3], double voxel_size, double level_set_value,
                           const double gauss_w[5], int device, double **points_out, double **normals_out,
-                          int64_t *count, const PackedIn *pk) {
+                          int64_t *count, const PackedIn *pk, int sel = -1) {
     if ((!volume && !pk) || !origin || !gauss_w || !points_out || !normals_out || !count)
         return g_err.fail(SC_ERR_INVALID, "null argument");
     if (nx < 2 || ny < 2 || nz < 2) return g_err.fail(SC_ERR_INVALID, "np.gradient needs at least 2 voxels per axis");
@@ -821,7 +844,7 @@ static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t 
     }
     if (planes >= nx)
         return vol2pcd_range(volume, on_device, dtype, nx, ny, nz, 0, 0, (int)nx, origin, voxel_size, level_set_value,
-                             gauss_w, device, points_out, normals_out, count, pk);
+                             gauss_w, device, points_out, normals_out, count, pk, sel);
     const int64_t S = planes - 2 * H;
     const size_t esz = dtype == 0 ? 4 : dtype == 1 ? 4 : dtype == 2 ? 8 : 1;
     std::vector<double *> ps, ns;
@@ -833,7 +856,7 @@ static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t 
         double *p = nullptr, *q = nullptr;
         int64_t c = 0;
         rc = vol2pcd_range(pk ? nullptr : static_cast<const char *>(volume) + (size_t)a * ny * nz * esz, on_device, dtype, b - a, ny, nz,
-                           (int)a, (int)(c0 - a), (int)(c1 - a), origin, voxel_size, level_set_value, gauss_w, device, &p, &q, &c, pk);
+                           (int)a, (int)(c0 - a), (int)(c1 - a), origin, voxel_size, level_set_value, gauss_w, device, &p, &q, &c, pk, sel);
         ps.push_back(p); ns.push_back(q); cs.push_back(c);
         total += c;
     }
@@ -882,6 +905,14 @@ int sc_vol2pcd_packed(const void *recv_dev, int64_t rank_bytes, int world, int p
                       partition == 0 ? 1 : 0, bits};
     return vol2pcd_driver(nullptr, 1, 3, nx, ny, nz, origin, voxel_size, level_set_value, gauss_w, device, points_out,
                           normals_out, count, &pk);
+}
+
+int sc_vol2pcd_class(const uint8_t *winner, int on_device, int cls, int64_t nx, int64_t ny, int64_t nz, const double origin[3],
+                     double voxel_size, double level_set_value, const double gauss_w[5], int device, double **points_out,
+                     double **normals_out, int64_t *count) {
+    if (cls < 0 || cls > 255) return g_err.fail(SC_ERR_INVALID, "cls must be 0..255 (a byte of the winner volume)");
+    return vol2pcd_driver(winner, on_device, 3, nx, ny, nz, origin, voxel_size, level_set_value, gauss_w, device, points_out,
+                          normals_out, count, nullptr, cls);
 }
 
 void sc_vol2pcd_release(void) {

@@ -17,11 +17,13 @@ def point2index(points, origin, voxel_size):
 
 class PointCloud:
     """What ``vol2pcd`` returns where open3d is absent: ``points`` and ``normals`` as float64
-    ``[n, 3]`` arrays (the two attributes the reference's callers read from the open3d object)."""
+    ``[n, 3]`` arrays (the two attributes the reference's callers read from the open3d object); ``colors`` is
+    ``None`` or a float64 ``[n, 3]`` array (what ``tasks/proc3d.py::point_cloud_run`` sets, tasks/proc3d.py:118-124)."""
 
-    def __init__(self, points, normals):
+    def __init__(self, points, normals, colors=None):
         self.points = points
         self.normals = normals
+        self.colors = colors
 
     def __len__(self):
         return len(self.points)
@@ -40,13 +42,14 @@ def gaussian_weights(sigma=1.0, truncate=4.0):
 
 def release_device_buffers():
     """Give back the device work buffers ``vol2pcd`` keeps between calls (``sc_vol2pcd_release``; it keeps them
-    only while they are at most 1 GiB), those of ``cluster_dbscan`` (``sc_dbscan_release``) and those of the
-    evaluation counts of ``metrics`` (``sc_eval_release``).
+    only while they are at most 1 GiB), those of ``cluster_dbscan`` (``sc_dbscan_release``), those of the
+    evaluation counts of ``metrics`` (``sc_eval_release``) and those of ``select_classes`` (``sc_select_release``).
     ``Backprojection.close`` calls this."""
     from . import _native as nat
     nat.backend().call("sc_vol2pcd_release")
     nat.backend().call("sc_dbscan_release")
     nat.backend().call("sc_eval_release")
+    nat.backend().call("sc_select_release")
 
 
 def set_scratch_limit(nbytes):
@@ -54,6 +57,48 @@ def set_scratch_limit(nbytes):
     more -- 49 bytes per voxel -- goes through in x-slabs with a halo, same points in the same order."""
     from . import _native as nat
     nat.backend().call("sc_vol2pcd_set_scratch_limit", int(nbytes))
+
+
+def _make_cloud(points, normals, colors=None, as_open3d=True):
+    """An ``open3d.geometry.PointCloud`` when open3d is importable (and ``as_open3d``), else a :class:`PointCloud`."""
+    if as_open3d:
+        try:
+            import open3d as o3d  # type: ignore
+        except ImportError:
+            o3d = None
+        if o3d is not None:
+            pcd = o3d.geometry.PointCloud()
+            pcd.points = o3d.utility.Vector3dVector(points)
+            pcd.normals = o3d.utility.Vector3dVector(normals)
+            if colors is not None:
+                pcd.colors = o3d.utility.Vector3dVector(colors)
+            return pcd
+    return PointCloud(points, normals, colors)
+
+
+def _adopt_cloud(b, out, cnt, as_open3d):
+    """The tail ``vol2pcd`` and ``vol2pcd_class`` share: the library's two buffers (``out``: their addresses, ``cnt``:
+    the point count) become the arrays, points without a normal are dropped, the cloud object is made."""
+    import ctypes
+
+    n = int(cnt[0])
+    if n:
+        # the library's buffers become the arrays (no copy); they are released with the last view
+        import weakref
+
+        def adopt(address):
+            owner = (ctypes.c_double * (3 * n)).from_address(address)
+            weakref.finalize(owner, b.call, "sc_free_host", address)
+            return np.frombuffer(owner, dtype=np.float64).reshape(n, 3)
+
+        pts, nrm = adopt(int(out[0])), adopt(int(out[1]))
+    else:
+        pts = np.zeros((0, 3))
+        nrm = np.zeros((0, 3))
+    ok = ~np.isnan(nrm).any(axis=1)  # proc3d.py:559-561: keep points with a positive gradient norm
+    if not ok.all():
+        pts, nrm = pts[ok], nrm[ok]
+    return _make_cloud(pts, nrm, None, as_open3d)
 
 
 def vol2pcd(volume, origin, voxel_size, level_set_value=0, device=0, as_open3d=True):
@@ -74,8 +119,6 @@ def vol2pcd(volume, origin, voxel_size, level_set_value=0, device=0, as_open3d=T
     cloud at every ``level_set_value``; the reference returns up to 5 points at corner (0, 0, 0) there, an artefact of
     SciPy's distance transform on an input without a site.
     """
-    import ctypes
-
     from . import _native as nat
 
     b = nat.backend()
@@ -121,34 +164,129 @@ def vol2pcd(volume, origin, voxel_size, level_set_value=0, device=0, as_open3d=T
                     float(voxel_size), float(level_set_value), nat.addr(gw), int(device), nat.addr(out),
                     nat.addr(out) + 8, nat.addr(cnt))
     nat.check(rc, "sc_vol2pcd", "sc_vol2pcd_last_error")
-    n = int(cnt[0])
-    if n:
-        # the library's buffers become the arrays (no copy); they are released with the last view
-        import weakref
+    return _adopt_cloud(b, out, cnt, as_open3d)
 
-        def adopt(address):
-            owner = (ctypes.c_double * (3 * n)).from_address(address)
-            weakref.finalize(owner, b.call, "sc_free_host", address)
-            return np.frombuffer(owner, dtype=np.float64).reshape(n, 3)
 
-        pts, nrm = adopt(int(out[0])), adopt(int(out[1]))
+def _is_tensor(a):
+    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+
+
+def set_select_chunk_bytes(nbytes):
+    """Largest device work buffer a ``select_classes`` call on host arrays may take (``sc_select_set_chunk_bytes``;
+    default 256 MiB, 0 restores it): larger stacks go through in x-slabs of whole planes, same winners."""
+    from . import _native as nat
+    nat.backend().call("sc_select_set_chunk_bytes", int(nbytes))
+
+
+def select_classes(voxels, background_prior=1.0, min_contrast=10.0, min_score=0.2, background="background", device=0):
+    """The decision step of the multiclass ``PointCloud.run`` (``tasks/proc3d.py:84-115``) on the GPU
+    (``sc_select_classes``, ``csrc/class_select.hip``; the rule is the contract in ``include/spacecarve.h``).
+
+    voxels : dict ``{label: volume}`` of at least two and at most 32 classes, in the reference's key order.  All
+        volumes are NumPy arrays of one shape ``(nx, ny, nz)`` and dtype, or all contiguous CUDA torch tensors of one
+        device, shape and dtype (read in place on torch's current stream).  float32, float64 and uint8 are read as they
+        are; bool is viewed as uint8; NumPy arrays of other dtypes are converted to float64 on the host.  Comparisons
+        are in float64.
+    background : the label whose value is multiplied by ``background_prior`` and that owns no voxel, or ``None``.
+
+    Returns ``(winner, labels, counts)``: ``winner`` uint8 ``[nx, ny, nz]`` -- the index into ``labels`` of the class
+    the voxel belongs to, 255 for none; the reference's volume of class ``c`` is ``winner == c`` -- a NumPy array, or a
+    CUDA tensor on the inputs' device; ``labels = list(voxels.keys())``; ``counts`` int64 ``[L]``, the voxels of each
+    class (0 for the background)."""
+    from . import _native as nat
+
+    labels = list(voxels.keys())
+    L = len(labels)
+    if L < 2:
+        raise ValueError("at least two classes are needed (with one key the reference takes its single-volume branch)")
+    if L > 32:
+        raise ValueError("at most 32 classes")
+    vols = [voxels[label] for label in labels]
+    tensors = [_is_tensor(v) for v in vols]
+    if any(tensors) and not all(tensors):
+        raise ValueError("volumes must be all NumPy arrays or all CUDA tensors")
+    bg = labels.index(background) if background in labels else -1
+    codes = {np.dtype(np.float32): nat.SC_EVAL_F32, np.dtype(np.float64): nat.SC_EVAL_F64, np.dtype(np.uint8): nat.SC_EVAL_U8}
+
+    def same(things, what):
+        if any(t != things[0] for t in things):
+            raise ValueError(f"the {what} differ: {sorted(set(str(t) for t in things))}")
+        return things[0]
+
+    if all(tensors):
+        import torch
+        tcodes = {torch.float32: nat.SC_EVAL_F32, torch.float64: nat.SC_EVAL_F64, torch.uint8: nat.SC_EVAL_U8, torch.bool: nat.SC_EVAL_U8}
+        for t in vols:
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 3:
+                raise ValueError("device volumes must be contiguous 3-D CUDA tensors")
+        tdev = same([t.device for t in vols], "devices")
+        shape = same([tuple(int(s) for s in t.shape) for t in vols], "shapes of the voxels")
+        dt = same([t.dtype for t in vols], "dtypes of the voxels")
+        if dt not in tcodes:
+            raise ValueError("device volumes must be float32, float64, uint8 or bool")
+        if min(shape) < 1:
+            raise ValueError("volumes must not be empty")
+        code, dev, on_dev = tcodes[dt], tdev.index, 1
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        winner = torch.empty(shape, dtype=torch.uint8, device=tdev)
+        ptrs, wptr = [t.data_ptr() for t in vols], winner.data_ptr()
     else:
-        pts = np.zeros((0, 3))
-        nrm = np.zeros((0, 3))
-    ok = ~np.isnan(nrm).any(axis=1)  # proc3d.py:559-561: keep points with a positive gradient norm
-    if not ok.all():
-        pts, nrm = pts[ok], nrm[ok]
-    if as_open3d:
-        try:
-            import open3d as o3d  # type: ignore
-        except ImportError:
-            o3d = None
-        if o3d is not None:
-            pcd = o3d.geometry.PointCloud()
-            pcd.points = o3d.utility.Vector3dVector(pts)
-            pcd.normals = o3d.utility.Vector3dVector(nrm)
-            return pcd
-    return PointCloud(pts, nrm)
+        vols = [np.asarray(v) for v in vols]
+        shape = same([v.shape for v in vols], "shapes of the voxels")
+        dt = same([v.dtype for v in vols], "dtypes of the voxels")
+        if len(shape) != 3:
+            raise ValueError("volumes must be 3-D")
+        if min(shape) < 1:
+            raise ValueError("volumes must not be empty")
+        if dt == np.bool_:
+            vols = [v.view(np.uint8) for v in vols]
+        elif dt not in codes:
+            vols = [v.astype(np.float64) for v in vols]
+        vols = [np.ascontiguousarray(v) for v in vols]
+        code, dev, on_dev, stream = codes[vols[0].dtype], int(device), 0, 0
+        winner = np.empty(shape, dtype=np.uint8)
+        ptrs, wptr = [nat.addr(v) for v in vols], nat.addr(winner)
+    pp = np.array(ptrs, dtype=np.uintp)
+    counts = np.zeros(L, dtype=np.int64)
+    nat.check(nat.backend().call("sc_select_classes", nat.addr(pp), code, L, bg, shape[0], shape[1], shape[2], float(background_prior),
+                                 float(min_contrast), float(min_score), on_dev, dev, int(stream), wptr, nat.addr(counts)),
+              "sc_select_classes", "sc_select_last_error")
+    return winner, labels, counts
+
+
+def vol2pcd_class(winner, index, origin, voxel_size, level_set_value=0, device=0, as_open3d=True):
+    """``vol2pcd`` of one class of a winner volume: the cloud of ``winner == index`` (``sc_vol2pcd_class``), bit for bit
+    what ``vol2pcd((winner == index).astype(np.uint8), ...)`` returns -- without that volume being made.
+
+    winner : uint8 ``[nx, ny, nz]``, what ``select_classes`` returns: a NumPy array, or a contiguous CUDA torch tensor
+        read in place (it never leaves the device; only points and normals come back).
+    index : the class, 0..255 (255: the voxels of no class)."""
+    from . import _native as nat
+
+    b = nat.backend()
+    origin64 = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    gw = gaussian_weights(1.0)
+    assert gw.size == 5
+    out = np.zeros(2, dtype=np.uintp)
+    cnt = np.zeros(1, dtype=np.int64)
+    if _is_tensor(winner):
+        import torch
+        if winner.dtype != torch.uint8 or winner.dim() != 3 or not winner.is_contiguous() or not winner.is_cuda:
+            raise ValueError("a device winner volume must be a contiguous uint8 CUDA tensor [nx, ny, nz]")
+        torch.cuda.current_stream(winner.device.index).synchronize()  # sc_vol2pcd_class runs on the default stream
+        keep, shape = winner, [int(s) for s in winner.shape]
+        ptr, on_device, device = winner.data_ptr(), 1, winner.device.index
+    else:
+        keep = np.asarray(winner)
+        if keep.ndim != 3 or keep.dtype != np.uint8:
+            raise ValueError("the winner volume must be uint8 [nx, ny, nz]")
+        keep = np.ascontiguousarray(keep)
+        ptr, shape, on_device = nat.addr(keep), list(keep.shape), 0
+    rc = b.call("sc_vol2pcd_class", ptr, on_device, int(index), shape[0], shape[1], shape[2], nat.addr(origin64),
+                float(voxel_size), float(level_set_value), nat.addr(gw), int(device), nat.addr(out), nat.addr(out) + 8,
+                nat.addr(cnt))
+    nat.check(rc, "sc_vol2pcd_class", "sc_vol2pcd_last_error")
+    return _adopt_cloud(b, out, cnt, as_open3d)
 
 
 def backproject_points(points, K, rot, tvec):
