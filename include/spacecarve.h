@@ -642,6 +642,56 @@ void sc_select_set_chunk_bytes(int64_t bytes);
 const char *sc_select_last_error(void);
 void sc_select_release(void);
 
+/*
+ * The nearest point of another cloud, for the point-cloud evaluations: what open3d's
+ * compute_point_cloud_distance, evaluate_registration and the KDTreeFlann loop of CompareSegmentedPointClouds compute
+ * (plant3dvision/metrics.py:16-95, :384-519; tasks/evaluation.py:278-353), on the GPU.  queries: float64 [Q][3],
+ * targets: float64 [P][3].  The rules, order-free (nanoflann's search cannot be run here: parity unpinned):
+ *   N1. d2(q, t) = ((dx dx) + (dy dy)) + (dz dz) in IEEE binary64 without contraction, dx = qx - tx;
+ *   N2. the nearest target of q is the t of least d2; among equal d2 the smallest target index wins;
+ *   N3. with max_distance > 0 a query is matched iff d2 < max_distance * max_distance (strict, the product rounded
+ *       once); an unmatched query reports index -1 and d2 = +inf; without it every query is matched when P > 0;
+ *   N4. P == 0: every index -1 and every d2 +inf; Q == 0: nothing written; neither makes a device call (P == 0 with
+ *       device outputs is therefore refused);
+ *   N5. deviations: non-finite coordinates are refused (in host arrays before any device call, naming the first bad
+ *       point; in device arrays by the first kernels), and so is a max_distance that is NaN or infinite or whose
+ *       square is not a normal number;
+ *   N6. sums_out = {n, sum d2, sum sqrt(d2)} over the matched queries, added in an order that depends on Q alone (a
+ *       tree per block, the block partials by a tree): two calls give the same bits; no floating-point atomics.
+ * The search is exact for every finite input: a dense grid over the targets' bounding box (at most 2^22 cells), rings
+ * of cells around the query's cell until a proved lower bound on what is unvisited exceeds the best d2 strictly, and
+ * for queries that four rings do not settle a pass over all P targets, one wavefront per query: O(P) per query at most.
+ *
+ * index_out [Q] int32 and d2_out [Q] double may each be NULL; both live where out_on_device says.
+ * sums_out: NULL, or 3 host doubles {n matched, sum d2, sum sqrt(d2)}: the call then ends in a wait.
+ * max_distance <= 0 means unbounded (N3).  queries_on_device / targets_on_device != 0: device pointers on `device`,
+ * read in place on hip_stream (NULL = the legacy default stream).  The call waits once mid-way (the finite flags and
+ * the targets' box) and, with sums_out or host outputs, at its end; otherwise it returns with the rest enqueued.
+ * Judged before any device call (SC_ERR_INVALID): NULL queries / targets (with Q / P > 0), all three outputs NULL, Q or
+ * P outside 0 .. 2^31 - 1, max_distance as in N5, the device ordinal, non-finite coordinates in host arrays.
+ *
+ * sc_nearest_confusion: counts_out: L*L host int64, counts[a*L + b] = queries with label a whose nearest target has
+ * label b; queries with index -1 are not counted.  index and query_labels ([Q] int32) live where on_device says,
+ * target_labels ([P] int32) where target_labels_on_device says.  Labels outside 0..L-1 -- and an index outside
+ * -1..P-1 -- are refused (a flag kernel for device arrays; counts_out is zero then).  1 <= L <= 4096; tables with
+ * L*L <= 1024 are gathered per block in LDS, larger ones by 64-bit integer atomics in global memory: the counts are
+ * exact either way.  The call returns when counts_out is complete.
+ *
+ * The work buffers (28 bytes per target, 4 per query, three cell tables of at most 16 MiB, staging for host arrays) are the library's, one
+ * set per device, shared by both entries, kept between calls, ordered across streams as sc_masks_from_rgb's are, given
+ * back by sc_nearest_release (the caller's current HIP device is left as it was).
+ */
+int sc_nearest(const double *queries, int queries_on_device, int64_t Q,
+               const double *targets, int targets_on_device, int64_t P,
+               double max_distance, int device,
+               int32_t *index_out, double *d2_out, int out_on_device,
+               double *sums_out, void *hip_stream);
+int sc_nearest_confusion(const int32_t *index, const int32_t *query_labels, int on_device, int64_t Q,
+                         const int32_t *target_labels, int target_labels_on_device, int64_t P,
+                         int L, int device, int64_t *counts_out, void *hip_stream);
+const char *sc_nearest_last_error(void);
+void sc_nearest_release(void);
+
 /* Page-locked host memory for the read-back of sc_get_values (no reference counterpart: the
  * reference's values_h is a pageable NumPy array, cl.py:173).  A 512 MiB volume reads back in
  * ~10 ms into such a buffer against ~50 ms into pageable memory, but allocating it takes ~0.1 s

@@ -144,6 +144,10 @@ _SIGNATURES = {
     "sc_select_set_chunk_bytes": ("v", ["q"]),
     "sc_select_last_error": ("s", []),
     "sc_select_release": ("v", []),
+    "sc_nearest": ("i", ["p", "i", "q", "p", "i", "q", "d", "i", "p", "p", "i", "p", "p"]),
+    "sc_nearest_confusion": ("i", ["p", "p", "i", "q", "p", "i", "q", "i", "i", "p", "p"]),
+    "sc_nearest_last_error": ("s", []),
+    "sc_nearest_release": ("v", []),
     "sc_vol2pcd_class": ("i", ["p", "i", "i", "q", "q", "q", "p", "d", "d", "p", "i", "p", "p", "p"]),
     "sc_create_sharded": ("i", ["p", "q", "q", "q", "p", "f", "i", "f", "p", "i", "i"]),
     "sc_group_destroy": ("v", ["p"]),

@@ -1,0 +1,495 @@
+// nearest.hip -- the nearest point of another cloud, for the point-cloud evaluations.
+//
+// Replaces open3d's compute_point_cloud_distance, evaluate_registration and the one-query-per-point KDTreeFlann loop
+// of CompareSegmentedPointClouds (plant3dvision/metrics.py:16-95, :384-519; tasks/evaluation.py:278-353) for Q float64
+// queries against P float64 targets.  PARITY UNPINNED: open3d is not available, this restates what
+// nanoflann's search computes in an order-free form:
+//   N1. d2(q, t) = ((dx dx) + (dy dy)) + (dz dz) in IEEE binary64 without contraction (-ffp-contract=off), dx = qx - tx;
+//   N2. the nearest target is the t of least d2; among equal d2 the smallest target index wins;
+//   N3. with max_distance, a query is matched iff d2 < fl(max_distance * max_distance) (strict, the product rounded
+//       once); an unmatched query reports index -1 and d2 = +inf;
+//   N4. P = 0: every index -1, every d2 +inf; Q = 0: empty outputs; neither makes a device call;
+//   N5. non-finite coordinates are refused, and a max_distance whose square is not a normal number;
+//   N6. n, sum d2 and sum sqrt(d2) over the matched queries are added in an order the launch geometry alone fixes: a
+//       tree per block, the block partials by one block, again a tree.  No floating-point atomics.
+//
+// Launches per call: box (targets: finite flag and bounding box), finite (queries), [box_final]; then histogram,
+// [scan], scatter, rings, far, [sums, sums_final].  The grid is dense and bounded (sc_nearest.h: plan, cells, the
+// stop rule and its proof).  Every launch reads what an earlier launch wrote or writes its own query's words; the
+// only traffic between blocks inside a launch is integer atomics (the histogram, the cursors, the far list's
+// length, the confusion counts), and nothing depends on their order.  Stand-alone unit: nothing shared with the engine.
+
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#include "sc_nearest.h"
+#include "sc_unit.h"
+
+namespace {
+
+constexpr int kB = 256;
+constexpr int kPartials = 256;     // blocks of the box and the sums launches: one final block takes a partial per thread
+constexpr int kFarBlocks = 2048;   // blocks of the far pass: 4 wavefronts each, grid-stride over the far list
+constexpr int kLdsTable = 1024;    // confusion counts with L * L up to this are gathered per block in LDS (L <= 32)
+constexpr int kMaxLabels = 4096;
+
+thread_local UnitError g_err;
+
+// header of the work buffer
+struct Header {
+    unsigned int bad_targets, bad_queries, bad_labels, nfar;
+    double box[6];   // lo x y z, hi x y z
+    double sums[3];  // n, sum d2, sum sqrt(d2)
+};
+
+// ---- box: whether every target coordinate is finite, and the targets' bounding box --------------------------------
+// One partial per block (6 doubles: lo, hi); min and max do not depend on any order.  Also the judge of device points.
+__global__ __launch_bounds__(kB) void nearest_box_kernel(const double *__restrict__ pts, int P, unsigned int *flag, double *__restrict__ partial) {
+    __shared__ double sh[6][kB];
+    __shared__ int sbad;
+    if (threadIdx.x == 0) sbad = 0;
+    __syncthreads();
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x; i < P; i += (int64_t)gridDim.x * kB)
+        for (int a = 0; a < 3; ++a) {
+            const double v = pts[3 * (size_t)i + a];
+            if (!(fabs(v) <= DBL_MAX)) bad = 1;
+            lo[a] = fmin(lo[a], v);
+            hi[a] = fmax(hi[a], v);
+        }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&sbad, 1);
+    for (int a = 0; a < 3; ++a) {
+        sh[a][threadIdx.x] = lo[a];
+        sh[3 + a][threadIdx.x] = hi[a];
+    }
+    __syncthreads();
+    for (int s = kB / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int a = 0; a < 3; ++a) {
+                sh[a][threadIdx.x] = fmin(sh[a][threadIdx.x], sh[a][threadIdx.x + s]);
+                sh[3 + a][threadIdx.x] = fmax(sh[3 + a][threadIdx.x], sh[3 + a][threadIdx.x + s]);
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) partial[6 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
+    if (threadIdx.x == 0 && sbad) atomicAdd(flag, 1u);
+}
+
+// one block: the partials of the launch before (a kernel boundary lies between) to the header's box
+__global__ __launch_bounds__(kB) void nearest_box_final_kernel(const double *__restrict__ partial, int nparts, double *__restrict__ box) {
+    __shared__ double sh[6][kB];
+    const bool have = (int)threadIdx.x < nparts;
+    for (int a = 0; a < 3; ++a) {
+        sh[a][threadIdx.x] = have ? partial[6 * threadIdx.x + a] : HUGE_VAL;
+        sh[3 + a][threadIdx.x] = have ? partial[6 * threadIdx.x + 3 + a] : -HUGE_VAL;
+    }
+    __syncthreads();
+    for (int s = kB / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int a = 0; a < 3; ++a) {
+                sh[a][threadIdx.x] = fmin(sh[a][threadIdx.x], sh[a][threadIdx.x + s]);
+                sh[3 + a][threadIdx.x] = fmax(sh[3 + a][threadIdx.x], sh[3 + a][threadIdx.x + s]);
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) box[threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// flag: zeroed before the launch; one add per block that saw a NaN or an infinity
+__global__ __launch_bounds__(kB) void nearest_finite_kernel(const double *__restrict__ pts, int64_t n3, unsigned int *flag) {
+    __shared__ int sbad;
+    if (threadIdx.x == 0) sbad = 0;
+    __syncthreads();
+    int bad = 0;
+    for (int64_t k = (int64_t)blockIdx.x * kB + threadIdx.x; k < n3; k += (int64_t)gridDim.x * kB)
+        if (!(fabs(pts[k]) <= DBL_MAX)) bad = 1;
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&sbad, 1);
+    __syncthreads();
+    if (threadIdx.x == 0 && sbad) atomicAdd(flag, 1u);
+}
+
+// ---- counting sort of the targets by cell --------------------------------------------------------------------------
+__device__ __forceinline__ int cell_index(const nn::Grid &g, double x, double y, double z) {
+    const int cx = nn::cell_of(x, g.lo[0], g.h, g.n[0]), cy = nn::cell_of(y, g.lo[1], g.h, g.n[1]), cz = nn::cell_of(z, g.lo[2], g.h, g.n[2]);
+    return (cz * g.n[1] + cy) * g.n[0] + cx;  // below kMaxCells
+}
+
+__global__ __launch_bounds__(kB) void nearest_hist_kernel(const double *__restrict__ pts, int P, nn::Grid g, uint32_t *__restrict__ count) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;  // unsigned: P may be just below 2^31
+    if (i >= (uint32_t)P) return;
+    atomicAdd(&count[cell_index(g, pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2])], 1u);
+}
+
+// cursor = a copy of start; afterwards cursor[c] == start[c + 1].  The order inside a cell is whatever the atomics
+// give; no result depends on it (N2 decides by the ORIGINAL index, carried in sidx).
+__global__ __launch_bounds__(kB) void nearest_scatter_kernel(const double *__restrict__ pts, int P, nn::Grid g, uint32_t *__restrict__ cursor,
+                                                             double *__restrict__ spts, int *__restrict__ sidx) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;  // unsigned: P may be just below 2^31
+    if (i >= (uint32_t)P) return;
+    const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    const uint32_t t = atomicAdd(&cursor[cell_index(g, x, y, z)], 1u);  // below P: the cell's count is what the histogram saw
+    spts[3 * (size_t)t] = x;
+    spts[3 * (size_t)t + 1] = y;
+    spts[3 * (size_t)t + 2] = z;
+    sidx[t] = (int)i;
+}
+
+// ---- rings: one thread per query -------------------------------------------------------------------------------------
+// A settled query writes its own two words; an unsettled one appends its number to the far list (capacity Q: it cannot
+// overflow) and writes nothing.  nfar is only added to here and only read by the next launch.
+__global__ __launch_bounds__(kB) void nearest_rings_kernel(const double *__restrict__ qs, int Q, nn::Grid g, const uint32_t *__restrict__ start,
+                                                           const double *__restrict__ spts, const int *__restrict__ sidx,
+                                                           int32_t *__restrict__ index, double *__restrict__ d2, int *__restrict__ far,
+                                                           unsigned int *nfar) {
+    const uint32_t q = blockIdx.x * kB + threadIdx.x;  // unsigned: Q may be just below 2^31
+    if (q >= (uint32_t)Q) return;
+    nn::Best best;
+    if (nn::ring_search(g, start, spts, sidx, qs[3 * (size_t)q], qs[3 * (size_t)q + 1], qs[3 * (size_t)q + 2], best)) {
+        const bool matched = best.d2 < g.md2;  // N3; false as well when nothing was found (d2 = +inf)
+        index[q] = matched ? best.idx : -1;
+        d2[q] = matched ? best.d2 : HUGE_VAL;
+    } else {
+        far[atomicAdd(nfar, 1u)] = (int)q;
+    }
+}
+
+// ---- far: one wavefront per query of the far list, all P targets in their original order ----------------------------
+// Costs O(P) per query whatever the data are.  A lane sees its targets in rising index, so `<` keeps the smallest
+// index of its own ties; across lanes the pair (d2, index) is reduced lexicographically (N2).
+__global__ __launch_bounds__(kB) void nearest_far_kernel(const double *__restrict__ qs, const double *__restrict__ pts, int P, double md2,
+                                                         const int *__restrict__ far, const unsigned int *__restrict__ nfar,
+                                                         int32_t *__restrict__ index, double *__restrict__ d2) {
+    const int lane = (int)(threadIdx.x & 63);
+    const unsigned int n = *nfar, waves = gridDim.x * (kB / 64);
+    for (unsigned int w = blockIdx.x * (kB / 64) + (threadIdx.x >> 6); w < n; w += waves) {
+        const int q = far[w];
+        const double qx = qs[3 * (size_t)q], qy = qs[3 * (size_t)q + 1], qz = qs[3 * (size_t)q + 2];
+        nn::Best best;
+        best.d2 = HUGE_VAL;
+        best.idx = 0x7fffffff;
+        for (int t = lane; t < P; t += 64) {
+            const double d = nn::dist2(qx, qy, qz, pts[3 * (size_t)t], pts[3 * (size_t)t + 1], pts[3 * (size_t)t + 2]);
+            if (d < best.d2) {
+                best.d2 = d;
+                best.idx = t;
+            }
+        }
+        for (int s = 32; s > 0; s >>= 1) best.take(__shfl_xor(best.d2, s, 64), __shfl_xor(best.idx, s, 64));
+        if (lane == 0) {
+            const bool matched = best.d2 < md2;
+            index[q] = matched ? best.idx : -1;
+            d2[q] = matched ? best.d2 : HUGE_VAL;
+        }
+    }
+}
+
+// ---- sums (N6) -----------------------------------------------------------------------------------------------------------
+// A thread adds its queries in rising index, a block adds its threads by a tree, and block b leaves its three partials
+// at partial[3 b]: the order is a function of Q, kB and the block count.
+__device__ __forceinline__ void block_tree3(double (*sh)[kB], double a, double b, double c) {
+    sh[0][threadIdx.x] = a;
+    sh[1][threadIdx.x] = b;
+    sh[2][threadIdx.x] = c;
+    __syncthreads();
+    for (int s = kB / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int k = 0; k < 3; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kB) void nearest_sums_kernel(const double *__restrict__ d2, int Q, double *__restrict__ partial) {
+    __shared__ double sh[3][kB];
+    double n = 0.0, s2 = 0.0, s1 = 0.0;  // n is a whole number below 2^31: exact
+    for (int64_t q = (int64_t)blockIdx.x * kB + threadIdx.x; q < Q; q += (int64_t)gridDim.x * kB) {
+        const double d = d2[q];
+        if (d < HUGE_VAL) {
+            n += 1.0;
+            s2 += d;
+            s1 += sqrt(d);
+        }
+    }
+    block_tree3(sh, n, s2, s1);
+    if (threadIdx.x < 3) partial[3 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(kB) void nearest_sums_final_kernel(const double *__restrict__ partial, int nparts, double *__restrict__ sums) {
+    __shared__ double sh[3][kB];
+    const bool have = (int)threadIdx.x < nparts;
+    block_tree3(sh, have ? partial[3 * threadIdx.x] : 0.0, have ? partial[3 * threadIdx.x + 1] : 0.0, have ? partial[3 * threadIdx.x + 2] : 0.0);
+    if (threadIdx.x < 3) sums[threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// ---- confusion counts ------------------------------------------------------------------------------------------------------
+// labels: the judge of device arrays.  An index outside -1..P-1 or a label outside 0..L-1 raises the flag.
+__global__ __launch_bounds__(kB) void nearest_labels_kernel(const int32_t *__restrict__ index, const int32_t *__restrict__ qlab, int Q,
+                                                            const int32_t *__restrict__ tlab, int P, int L, unsigned int *flag) {
+    int bad = 0;
+    for (int64_t k = (int64_t)blockIdx.x * kB + threadIdx.x; k < Q; k += (int64_t)gridDim.x * kB)
+        if (index[k] < -1 || index[k] >= P || qlab[k] < 0 || qlab[k] >= L) bad = 1;
+    for (int64_t k = (int64_t)blockIdx.x * kB + threadIdx.x; k < P; k += (int64_t)gridDim.x * kB)
+        if (tlab[k] < 0 || tlab[k] >= L) bad = 1;
+    if (bad) atomicOr(flag, 1u);
+}
+
+// counts[a L + b] += 1 for a query of label a whose nearest target has label b.  Every access is checked again here:
+// a refused call (the labels launch) still reads and writes inside its arrays.  kLds: L * L <= kLdsTable, the block
+// counts in LDS (at most 2^31 per block: 32 bits) and adds its non-zero cells once.
+template <bool kLds>
+__global__ __launch_bounds__(kB) void nearest_confusion_kernel(const int32_t *__restrict__ index, const int32_t *__restrict__ qlab, int Q,
+                                                               const int32_t *__restrict__ tlab, int P, int L, unsigned long long *counts) {
+    __shared__ unsigned int tab[kLds ? kLdsTable : 1];
+    if (kLds) {
+        for (int k = (int)threadIdx.x; k < L * L; k += kB) tab[k] = 0u;
+        __syncthreads();
+    }
+    for (int64_t q = (int64_t)blockIdx.x * kB + threadIdx.x; q < Q; q += (int64_t)gridDim.x * kB) {
+        const int t = index[q], a = qlab[q];
+        if (t < 0 || t >= P || a < 0 || a >= L) continue;
+        const int b = tlab[t];
+        if (b < 0 || b >= L) continue;
+        if (kLds)
+            atomicAdd(&tab[a * L + b], 1u);
+        else
+            atomicAdd(&counts[(size_t)a * L + b], 1ull);
+    }
+    if (kLds) {
+        __syncthreads();
+        for (int k = (int)threadIdx.x; k < L * L; k += kB)
+            if (tab[k]) atomicAdd(&counts[k], (unsigned long long)tab[k]);
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+// Work buffers are kept per device: the slot protocol of sc_unit.h.  Both entries share the slot.
+WorkSlot g_slots[kUnitDevices];
+
+int first_non_finite(const double *p, int64_t n, const char *what) {
+    for (int64_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(p[k])) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "non-finite coordinate in %s %lld", what, (long long)(k / 3));
+            return g_err.fail(SC_ERR_INVALID, msg);
+        }
+    return SC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *sc_nearest_last_error(void) { return g_err.msg; }
+
+int sc_nearest(const double *queries, int queries_on_device, int64_t Q, const double *targets, int targets_on_device, int64_t P,
+               double max_distance, int device, int32_t *index_out, double *d2_out, int out_on_device, double *sums_out,
+               void *hip_stream) {
+    // every argument is judged before the first device call
+    if (Q < 0 || Q >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "Q must be 0 .. 2^31 - 1");
+    if (P < 0 || P >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "P must be 0 .. 2^31 - 1");
+    if ((Q > 0 && !queries) || (P > 0 && !targets)) return g_err.fail(SC_ERR_INVALID, "null argument (queries, targets)");
+    if (!index_out && !d2_out && !sums_out) return g_err.fail(SC_ERR_INVALID, "null argument (one of index_out, d2_out, sums_out is needed)");
+    if (!std::isfinite(max_distance)) return g_err.fail(SC_ERR_INVALID, "max_distance must be finite (<= 0: unbounded)");
+    if (max_distance > 0.0 && (!(max_distance * max_distance >= DBL_MIN) || !std::isfinite(max_distance * max_distance)))
+        return g_err.fail(SC_ERR_INVALID, "max_distance * max_distance must be a normal number (max_distance out of range)");
+    if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
+    if (P == 0 && Q > 0 && out_on_device && (index_out || d2_out))
+        return g_err.fail(SC_ERR_INVALID, "P == 0 makes no device call: device outputs cannot be filled");
+    if (!queries_on_device) {
+        const int rc = first_non_finite(queries, Q, "query");
+        if (rc != SC_OK) return rc;
+    }
+    if (!targets_on_device) {
+        const int rc = first_non_finite(targets, P, "target");
+        if (rc != SC_OK) return rc;
+    }
+    if (sums_out) sums_out[0] = sums_out[1] = sums_out[2] = 0.0;
+    if (Q == 0) return SC_OK;
+    if (P == 0) {  // N4
+        for (int64_t q = 0; q < Q; ++q) {
+            if (index_out) index_out[q] = -1;
+            if (d2_out) d2_out[q] = HUGE_VAL;
+        }
+        return SC_OK;
+    }
+
+    const int nq = (int)Q, np = (int)P;
+    const int64_t cap = nn::cell_cap(P);
+    const uint32_t qblocks = (uint32_t)((Q + kB - 1) / kB), pblocks = (uint32_t)((P + kB - 1) / kB);
+    const int box_parts = (int)std::min<uint32_t>(pblocks, kPartials), sum_parts = (int)std::min<uint32_t>(qblocks, kPartials);
+
+    WorkSlot &sl = g_slots[device];
+    std::lock_guard<std::mutex> lock(sl.mu);
+    int rc = SC_OK;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    size_t tmp = 0;
+    Header hh;
+    nn::Grid g;
+
+    // layout of the work buffer
+    Layout lay;
+    const size_t o_hdr = lay.take(sizeof(Header)), o_part = lay.take((size_t)kPartials * 6 * 8);
+    const size_t o_count = lay.take(((size_t)cap + 1) * 4), o_start = lay.take(((size_t)cap + 1) * 4), o_cursor = lay.take(((size_t)cap + 1) * 4);
+    const size_t o_spts = lay.take((size_t)P * 24), o_sidx = lay.take((size_t)P * 4), o_far = lay.take((size_t)Q * 4);
+    const size_t o_qs = lay.take(queries_on_device ? 0 : (size_t)Q * 24), o_ts = lay.take(targets_on_device ? 0 : (size_t)P * 24);
+    const size_t o_idx = lay.take(index_out && out_on_device ? 0 : (size_t)Q * 4), o_d2 = lay.take(d2_out && out_on_device ? 0 : (size_t)Q * 8);
+    size_t o_tmp = 0;  // the scan's temporary storage: the last buffer, sized below
+
+    UNIT_TRY(hipSetDevice(device));
+    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
+    // the scan's temporary storage for the largest table (a size query: no device work)
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(cap + 1), stream));
+    o_tmp = lay.take(tmp);
+    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
+    {
+        char *const w = sl.base;
+        Header *hdr = reinterpret_cast<Header *>(w + o_hdr);
+        double *partial = reinterpret_cast<double *>(w + o_part);
+        uint32_t *count = reinterpret_cast<uint32_t *>(w + o_count), *start = reinterpret_cast<uint32_t *>(w + o_start),
+                 *cursor = reinterpret_cast<uint32_t *>(w + o_cursor);
+        double *spts = reinterpret_cast<double *>(w + o_spts);
+        int *sidx = reinterpret_cast<int *>(w + o_sidx), *far = reinterpret_cast<int *>(w + o_far);
+        const double *qs_d = queries_on_device ? queries : reinterpret_cast<const double *>(w + o_qs);
+        const double *ts_d = targets_on_device ? targets : reinterpret_cast<const double *>(w + o_ts);
+        int32_t *idx_d = index_out && out_on_device ? index_out : reinterpret_cast<int32_t *>(w + o_idx);
+        double *d2_d = d2_out && out_on_device ? d2_out : reinterpret_cast<double *>(w + o_d2);
+        void *tmp_d = w + o_tmp;
+
+        UNIT_TRY(sl.wait(stream));
+        if (!queries_on_device) UNIT_TRY(hipMemcpyAsync(w + o_qs, queries, (size_t)Q * 24, hipMemcpyHostToDevice, stream));
+        if (!targets_on_device) UNIT_TRY(hipMemcpyAsync(w + o_ts, targets, (size_t)P * 24, hipMemcpyHostToDevice, stream));
+        UNIT_TRY(hipMemsetAsync(hdr, 0, sizeof(Header), stream));
+        hipLaunchKernelGGL(nearest_box_kernel, dim3(box_parts), dim3(kB), 0, stream, ts_d, np, &hdr->bad_targets, partial);
+        hipLaunchKernelGGL(nearest_box_final_kernel, dim3(1), dim3(kB), 0, stream, partial, box_parts, hdr->box);
+        hipLaunchKernelGGL(nearest_finite_kernel, dim3(std::min<uint32_t>(qblocks, 1024u)), dim3(kB), 0, stream, qs_d, 3 * Q, &hdr->bad_queries);
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpyAsync(&hh, hdr, sizeof(Header), hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(hipStreamSynchronize(stream));  // the call's one mid-way wait
+        if (hh.bad_queries != 0u || hh.bad_targets != 0u) {  // device points: the first kernels are the judge
+            rc = g_err.fail(SC_ERR_INVALID, hh.bad_queries ? "non-finite coordinate in the device queries" : "non-finite coordinate in the device targets");
+            goto done;
+        }
+        nn::plan_grid(hh.box, hh.box + 3, P, max_distance, g);
+        const int ncell = g.n[0] * g.n[1] * g.n[2];  // <= cap
+
+        UNIT_TRY(hipMemsetAsync(count, 0, ((size_t)ncell + 1) * 4, stream));
+        hipLaunchKernelGGL(nearest_hist_kernel, dim3(pblocks), dim3(kB), 0, stream, ts_d, np, g, count);
+        UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp, count, start, ncell + 1, stream));
+        UNIT_TRY(hipMemcpyAsync(cursor, start, (size_t)ncell * 4, hipMemcpyDeviceToDevice, stream));
+        hipLaunchKernelGGL(nearest_scatter_kernel, dim3(pblocks), dim3(kB), 0, stream, ts_d, np, g, cursor, spts, sidx);
+        hipLaunchKernelGGL(nearest_rings_kernel, dim3(qblocks), dim3(kB), 0, stream, qs_d, nq, g, start, spts, sidx, idx_d, d2_d, far, &hdr->nfar);
+        hipLaunchKernelGGL(nearest_far_kernel, dim3(std::min<uint32_t>((uint32_t)((Q + 3) / 4), kFarBlocks)), dim3(kB), 0, stream, qs_d, ts_d, np,
+                           g.md2, far, &hdr->nfar, idx_d, d2_d);
+        if (sums_out) {
+            hipLaunchKernelGGL(nearest_sums_kernel, dim3(sum_parts), dim3(kB), 0, stream, d2_d, nq, partial);
+            hipLaunchKernelGGL(nearest_sums_final_kernel, dim3(1), dim3(kB), 0, stream, partial, sum_parts, hdr->sums);
+        }
+        UNIT_TRY(hipGetLastError());
+        if (index_out && !out_on_device) UNIT_TRY(hipMemcpyAsync(index_out, idx_d, (size_t)Q * 4, hipMemcpyDeviceToHost, stream));
+        if (d2_out && !out_on_device) UNIT_TRY(hipMemcpyAsync(d2_out, d2_d, (size_t)Q * 8, hipMemcpyDeviceToHost, stream));
+        if (sums_out) UNIT_TRY(hipMemcpyAsync(hh.sums, hdr->sums, sizeof hh.sums, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(sl.record(stream));
+        if (sums_out || ((index_out || d2_out) && !out_on_device)) {
+            UNIT_TRY(hipStreamSynchronize(stream));
+            if (sums_out)
+                for (int k = 0; k < 3; ++k) sums_out[k] = hh.sums[k];
+        }
+    }
+
+done:
+    if (rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);  // nothing of ours still reads host memory
+    return rc;
+}
+
+int sc_nearest_confusion(const int32_t *index, const int32_t *query_labels, int on_device, int64_t Q, const int32_t *target_labels,
+                         int target_labels_on_device, int64_t P, int L, int device, int64_t *counts_out, void *hip_stream) {
+    // every argument is judged before the first device call
+    if (Q < 0 || Q >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "Q must be 0 .. 2^31 - 1");
+    if (P < 0 || P >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "P must be 0 .. 2^31 - 1");
+    if (L < 1 || L > kMaxLabels) return g_err.fail(SC_ERR_INVALID, "L must be 1 .. 4096");
+    if (!counts_out || (Q > 0 && (!index || !query_labels)) || (P > 0 && !target_labels))
+        return g_err.fail(SC_ERR_INVALID, "null argument (index, query_labels, target_labels, counts_out)");
+    if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
+    char msg[160];
+    if (!on_device)
+        for (int64_t q = 0; q < Q; ++q) {
+            if (index[q] < -1 || index[q] >= P) {
+                snprintf(msg, sizeof msg, "index %lld is outside -1 .. P - 1", (long long)q);
+                return g_err.fail(SC_ERR_INVALID, msg);
+            }
+            if (query_labels[q] < 0 || query_labels[q] >= L) {
+                snprintf(msg, sizeof msg, "query label %lld is outside 0 .. L - 1", (long long)q);
+                return g_err.fail(SC_ERR_INVALID, msg);
+            }
+        }
+    if (!target_labels_on_device)
+        for (int64_t t = 0; t < P; ++t)
+            if (target_labels[t] < 0 || target_labels[t] >= L) {
+                snprintf(msg, sizeof msg, "target label %lld is outside 0 .. L - 1", (long long)t);
+                return g_err.fail(SC_ERR_INVALID, msg);
+            }
+    const size_t cells = (size_t)L * L;
+    for (size_t k = 0; k < cells; ++k) counts_out[k] = 0;
+    if (Q == 0 || P == 0) return SC_OK;  // with no target every index is -1: nothing is counted
+
+    const uint32_t blocks = (uint32_t)std::min<int64_t>((std::max(Q, P) + kB - 1) / kB, 1024);
+    WorkSlot &sl = g_slots[device];
+    std::lock_guard<std::mutex> lock(sl.mu);
+    int rc = SC_OK;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    unsigned int bad = 0;
+
+    Layout lay;
+    const size_t o_hdr = lay.take(sizeof(Header)), o_counts = lay.take(cells * 8);
+    const size_t o_idx = lay.take(on_device ? 0 : (size_t)Q * 4), o_ql = lay.take(on_device ? 0 : (size_t)Q * 4);
+    const size_t o_tl = lay.take(target_labels_on_device ? 0 : (size_t)P * 4);
+
+    UNIT_TRY(hipSetDevice(device));
+    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
+    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
+    {
+        char *const w = sl.base;
+        Header *hdr = reinterpret_cast<Header *>(w + o_hdr);
+        unsigned long long *counts = reinterpret_cast<unsigned long long *>(w + o_counts);
+        const int32_t *idx_d = on_device ? index : reinterpret_cast<const int32_t *>(w + o_idx);
+        const int32_t *ql_d = on_device ? query_labels : reinterpret_cast<const int32_t *>(w + o_ql);
+        const int32_t *tl_d = target_labels_on_device ? target_labels : reinterpret_cast<const int32_t *>(w + o_tl);
+
+        UNIT_TRY(sl.wait(stream));
+        if (!on_device) {
+            UNIT_TRY(hipMemcpyAsync(w + o_idx, index, (size_t)Q * 4, hipMemcpyHostToDevice, stream));
+            UNIT_TRY(hipMemcpyAsync(w + o_ql, query_labels, (size_t)Q * 4, hipMemcpyHostToDevice, stream));
+        }
+        if (!target_labels_on_device) UNIT_TRY(hipMemcpyAsync(w + o_tl, target_labels, (size_t)P * 4, hipMemcpyHostToDevice, stream));
+        UNIT_TRY(hipMemsetAsync(hdr, 0, sizeof(Header), stream));
+        UNIT_TRY(hipMemsetAsync(counts, 0, cells * 8, stream));
+        hipLaunchKernelGGL(nearest_labels_kernel, dim3(blocks), dim3(kB), 0, stream, idx_d, ql_d, (int)Q, tl_d, (int)P, L, &hdr->bad_labels);
+        if (cells <= (size_t)kLdsTable)
+            hipLaunchKernelGGL(nearest_confusion_kernel<true>, dim3(blocks), dim3(kB), 0, stream, idx_d, ql_d, (int)Q, tl_d, (int)P, L, counts);
+        else
+            hipLaunchKernelGGL(nearest_confusion_kernel<false>, dim3(blocks), dim3(kB), 0, stream, idx_d, ql_d, (int)Q, tl_d, (int)P, L, counts);
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpyAsync(&bad, &hdr->bad_labels, 4, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(hipMemcpyAsync(counts_out, counts, cells * 8, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(hipStreamSynchronize(stream));
+        if (bad != 0u) {  // device arrays: the labels launch is the judge
+            for (size_t k = 0; k < cells; ++k) counts_out[k] = 0;
+            rc = g_err.fail(SC_ERR_INVALID, "a label outside 0 .. L - 1 or an index outside -1 .. P - 1 in the device arrays");
+        }
+    }
+
+done:
+    if (rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);  // nothing of ours still reads host memory
+    return rc;
+}
+
+void sc_nearest_release(void) { release_slots(g_slots); }
+
+}  // extern "C"

@@ -1,0 +1,189 @@
+// sc_nearest.h -- the arithmetic of nearest.hip that does not depend on how threads are laid out: the
+// plan of the dense grid over the targets, the cell of a coordinate, the ring walk of one query with its stop rule.
+// Host and device: nearest.hip runs it one thread per query; tools/nearest_rehearsal.cpp runs the same text on the
+// CPU, one query after the other, against all pairs.
+#pragma once
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define NN_HD __host__ __device__ __forceinline__
+#else
+#define NN_HD inline
+#endif
+
+namespace nn {
+
+constexpr int64_t kMaxCells = (int64_t)1 << 22;  // cap on nx * ny * nz: three 16 MiB tables at most
+constexpr int kNearRings = 3;                    // rings 0..3 (at most 7^3 cells) per thread; what is left goes to the far pass
+constexpr double kShrink = 1.0 - 1.0 / 1048576.0;  // 1 - 2^-20: the margin of the stop rule, see ring_bound
+constexpr double kEdgeMin = 0x1p-480, kEdgeMax = 0x1p480;  // outside this range of cell edges the grid is one cell
+
+struct Grid {
+    double lo[3];  // the targets' least coordinate per axis
+    double h;      // the edge of a cell, the same on every axis
+    int n[3];      // cells per axis; n[0] * n[1] * n[2] <= kMaxCells
+    double md2;    // fl(max_distance * max_distance), +inf when unbounded (N3)
+};
+
+// The cells a call may use at most: known from P alone, so the work buffer is sized before the box is.
+inline int64_t cell_cap(int64_t P) {
+    int64_t c = 2 * P;
+    if (c < 64) c = 64;
+    return c < kMaxCells ? c : kMaxCells;
+}
+
+// u(x) = fl(fl(x - lo) / h): the cell coordinate before the floor.  x - lo may overflow to an infinity (the clamp
+// takes it); it is never NaN for finite x and lo, and h is a normal number.
+NN_HD int cell_of(double x, double lo, double h, int n) {
+    const double u = floor((x - lo) / h);
+    return (int)fmin(fmax(u, 0.0), (double)(n - 1));
+}
+
+// The plan.  One edge h for all axes, n[a] = floor(fl(fl(hi[a] - lo[a]) / h)) + 1: by the monotonicity of rounding
+// every target's u lies in [0, n[a]), so a TARGET IS NEVER CLAMPED (cell_of's clamp is a belt for them) -- the proof
+// below needs that.  An axis of zero extent gets one cell.  h aims at cell_cap(P) / 2 cells in the box spanned by the
+// axes of non-zero extent and grows by a quarter until the product of the counts fits under cell_cap(P): at most
+// kPlanSteps times, after which (or when an extent is not finite, or h leaves [kEdgeMin, kEdgeMax]) the grid is ONE
+// cell and ring 0 is the whole search.
+constexpr int kPlanSteps = 8192;
+
+inline void plan_grid(const double lo[3], const double hi[3], int64_t P, double max_distance, Grid &g) {
+    const double cap = (double)cell_cap(P);
+    double ext[3], logsum = 0.0;
+    int k = 0;
+    bool ok = true;
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = lo[a];
+        g.n[a] = 1;
+        ext[a] = hi[a] - lo[a];
+        if (!(ext[a] >= 0.0) || !std::isfinite(ext[a])) ok = false;
+        if (ext[a] > 0.0) {
+            logsum += std::log(ext[a]);
+            ++k;
+        }
+    }
+    g.h = 1.0;
+    g.md2 = max_distance > 0.0 ? max_distance * max_distance : HUGE_VAL;
+    if (!ok || k == 0) return;
+    double h = std::exp((logsum - std::log(cap / 2.0)) / k);
+    for (int step = 0; step < kPlanSteps; ++step, h *= 1.25) {
+        if (!(h >= kEdgeMin)) continue;  // grows into the range
+        if (!(h <= kEdgeMax)) return;    // one cell
+        double prod = 1.0, cnt[3];
+        for (int a = 0; a < 3; ++a) {
+            cnt[a] = floor(ext[a] / h) + 1.0;
+            prod *= cnt[a];
+        }
+        if (prod <= cap) {  // also false for an infinite or NaN product
+            g.h = h;
+            for (int a = 0; a < 3; ++a) g.n[a] = (int)cnt[a];
+            return;
+        }
+    }
+}
+
+NN_HD double dist2(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    return ((dx * dx) + (dy * dy)) + (dz * dz);
+}
+
+// N2: the pair (d2, index) is kept lexicographically.
+struct Best {
+    double d2;
+    int idx;
+    NN_HD void take(double d, int i) {
+        if (d < d2 || (d == d2 && i < idx)) {
+            d2 = d;
+            idx = i;
+        }
+    }
+};
+
+// ---- the stop rule -----------------------------------------------------------------------------------------------
+// Claim.  Let the query's cell be c (cell_of per axis, clamped into the grid) and let rings 0..r around c have been
+// visited, r >= 1, ring k = the cells at Chebyshev distance k from c, clipped to the grid.  Then every target t that
+// was not visited has a computed d2(q, t) >= ring_bound(h, r) = fl(fl(fl(h r) fl(h r)) kShrink), kShrink = 1 - 2^-20.
+//
+// Proof.  An unvisited t has a cell ct with |ct[a] - c[a]| >= r + 1 on some axis a.  Write u(x) = fl(fl(x - lo) / h)
+// and rho(x) = (x - lo) / h in exact arithmetic.  u carries two roundings: |u - rho| <= |u| 2^-52 (1 + 2^-52) (a
+// quotient that underflows is off by less than 2^-1074, and fl(x - lo), the quotient and rho share their sign).
+//   Targets are never clamped (plan_grid), so ct = floor(u(tx)) with 0 <= u(tx) < n <= 2^22, |u(tx) - rho(tx)| < 2^-29.
+//   High side, ct >= c + r + 1: then u(tx) >= c + r + 1.  The query's cell was not clamped from above (there is no
+//   cell beyond n - 1 for t to be in), so floor(u(qx)) <= c, u(qx) < c + 1.  If u(qx) >= -1 then |u(qx)| < 2^22 and
+//   rho(qx) < c + 1 + 2^-29; if u(qx) < -1 (a query left of the box, -inf included) then rho(qx) < 0 < c + 1.  Either
+//   way rho(tx) - rho(qx) > r - 2^-28.
+//   Low side, ct <= c - r - 1: then u(tx) < c - r, rho(tx) < c - r + 2^-29.  The query's cell was not clamped from below,
+//   so u(qx) >= c.  If u(qx) <= 2^23, rho(qx) > c - 2^-28; otherwise (a query right of the box, +inf included)
+//   rho(qx) > 2^23 - 1 >= c + 2^22 > c.  Either way rho(qx) - rho(tx) > r - 2^-27.
+// So the clamped query needs no case of its own: a query outside the box still has every unvisited target more than
+// r - 2^-27 cell edges away on that axis, |qx - tx| > h (r - 2^-27) >= h r (1 - 2^-27).
+//   N1: dx = fl(qx - tx), |dx| >= |qx - tx| (1 - 2^-53); fl(dx dx) >= dx^2 (1 - 2^-53) (normal: h r >= kEdgeMin =
+//   2^-480, so the square is above 2^-961); rounded sums of non-negative terms never fall below a term.  Hence
+//   d2 >= h^2 r^2 (1 - 2^-27)^2 (1 - 2^-53)^3 > h^2 r^2 (1 - 2^-25).
+//   ring_bound carries three roundings upward at most: <= h^2 r^2 (1 - 2^-20) (1 + 2^-53)^3 < h^2 r^2 (1 - 2^-21), and
+//   h r <= kEdgeMax 2^22 = 2^502 does not overflow when squared.  The margin taken is 2^-21 against a need of 2^-25.
+//
+// Use.  A query stops after ring r when ring_bound > best d2 STRICTLY -- at equality a tie with a smaller index may
+// sit in the next ring (N2) -- or when ring_bound >= md2: nothing unvisited can be matched (N3).  It also stops when
+// ring r reached the grid's far faces on every axis: nothing is unvisited then, whatever the numbers are.  After
+// ring 0 the bound is 0 and stops nobody.
+NN_HD double ring_bound(double h, int r) {
+    const double hr = h * (double)r;
+    return (hr * hr) * kShrink;
+}
+
+// Visits ring r of the query cell (cx, cy, cz).  Cells are numbered (z ny + y) nx + x, so a run of cells along x is
+// a run of sorted slots: start[first cell] .. start[last cell + 1].  Every loop is bounded by the cell counts or P.
+NN_HD void visit_ring(const Grid &g, int cx, int cy, int cz, int r, const uint32_t *__restrict__ start,
+                      const double *__restrict__ spts, const int *__restrict__ sidx, double qx, double qy, double qz, Best &best) {
+    const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
+    const int x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < nx - 1 ? cx + r : nx - 1;
+    const int y0 = cy - r > 0 ? cy - r : 0, y1 = cy + r < ny - 1 ? cy + r : ny - 1;
+    const int z0 = cz - r > 0 ? cz - r : 0, z1 = cz + r < nz - 1 ? cz + r : nz - 1;
+    for (int z = z0; z <= z1; ++z)
+        for (int y = y0; y <= y1; ++y) {
+            const int row = (z * ny + y) * nx;
+            const bool face = z - cz == r || cz - z == r || y - cy == r || cy - y == r;
+            // a face row is visited whole; of an inner row only its two end cells belong to ring r
+            for (int part = 0; part < 2; ++part) {
+                int a, b;  // cells a..b of the row
+                if (face) {
+                    if (part) break;
+                    a = x0;
+                    b = x1;
+                } else {
+                    a = b = part ? cx + r : cx - r;
+                    if (a < 0 || a > nx - 1) continue;
+                }
+                const uint32_t t0 = start[row + a], t1 = start[row + b + 1];
+                for (uint32_t t = t0; t < t1; ++t)
+                    best.take(dist2(qx, qy, qz, spts[3 * (size_t)t], spts[3 * (size_t)t + 1], spts[3 * (size_t)t + 2]), sidx[t]);
+            }
+        }
+}
+
+// The ring walk of one query.  Returns true when the answer is final (best holds it, before N3's test); false when
+// kNearRings rings did not settle it: the far pass then searches all P targets.
+NN_HD bool ring_search(const Grid &g, const uint32_t *__restrict__ start, const double *__restrict__ spts,
+                       const int *__restrict__ sidx, double qx, double qy, double qz, Best &best) {
+    const int cx = cell_of(qx, g.lo[0], g.h, g.n[0]), cy = cell_of(qy, g.lo[1], g.h, g.n[1]), cz = cell_of(qz, g.lo[2], g.h, g.n[2]);
+    int last = cx > g.n[0] - 1 - cx ? cx : g.n[0] - 1 - cx;  // the ring that reaches the far faces on every axis
+    last = cy > last ? cy : last;
+    last = g.n[1] - 1 - cy > last ? g.n[1] - 1 - cy : last;
+    last = cz > last ? cz : last;
+    last = g.n[2] - 1 - cz > last ? g.n[2] - 1 - cz : last;
+    best.d2 = HUGE_VAL;
+    best.idx = 0x7fffffff;
+    for (int r = 0; r <= kNearRings; ++r) {
+        visit_ring(g, cx, cy, cz, r, start, spts, sidx, qx, qy, qz, best);
+        if (r >= last) return true;
+        const double b = ring_bound(g.h, r);
+        if (b > best.d2 || b >= g.md2) return true;
+    }
+    return false;
+}
+
+}  // namespace nn

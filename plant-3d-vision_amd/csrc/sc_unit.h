@@ -1,4 +1,4 @@
-// sc_unit.h -- the host scaffold of the stand-alone device units (vol2pcd, label_points, masks_rgb, dbscan, evaluate, class_select): the
+// sc_unit.h -- the host scaffold of the stand-alone device units (vol2pcd, label_points, masks_rgb, dbscan, evaluate, class_select, nearest): the
 // "last error" of a unit, the layout of a work buffer, and the per-device work-buffer slot of DESIGN.md 12.
 // Host only, internal linkage: every unit that includes it has its own copy and its own state.
 #pragma once

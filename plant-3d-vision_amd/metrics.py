@@ -4,7 +4,11 @@
 ``SetEvaluator``, ``SetMetrics``, ``MaskEvaluator`` and ``CompareMasks`` keep the reference's names, signatures and
 results; ``MaskEvaluator.evaluate`` counts on the GPU.  ``compare_mask_stacks`` is the batched form a fileset
 comparison calls once per label, ``voxel_confusion`` the counting of ``VoxelsEvaluation.evaluate``
-(``tasks/evaluation.py:421-477``).  The nearest-neighbour and mesh metrics of the reference's module are not here.
+(``tasks/evaluation.py:421-477``).
+
+``chamfer_distance``, ``point_cloud_registration_fitness`` (metrics.py:16-95) and ``CompareSegmentedPointClouds``
+(:384-519) rest on the nearest-point search of ``csrc/nearest.hip`` (``proc3d.nearest_points``; parity
+with open3d unpinned).  The mesh metrics of the reference's module are not here.
 There is no CPU fallback: without the library or a gfx950 device the calls raise.
 """
 from abc import ABC, abstractmethod
@@ -258,3 +262,132 @@ def voxel_confusion(voxels, groundtruths, background="background", min_contrast=
     if projections:
         return out, {label: proj[q] for q, label in enumerate(labels) if q != bg}
     return out
+
+
+# ---- the cloud metrics ---------------------------------------------------------------------------------
+def _n_points(cloud):
+    if not isinstance(cloud, np.ndarray) and hasattr(cloud, "points"):
+        cloud = cloud.points
+    return int(cloud.shape[0]) if hasattr(cloud, "shape") else len(cloud)
+
+
+def chamfer_distance(ref_pcd, flo_pcd, device=0):
+    """The symmetric chamfer distance of the reference (metrics.py:16-55): the mean distance from every point of
+    ``ref_pcd`` to its nearest point of ``flo_pcd`` plus the same the other way.  Clouds as ``proc3d.nearest_points``
+    takes them; only the sums leave the device (rule N6 of DESIGN.md 16).  An empty cloud raises ``ValueError`` (the
+    reference divides by zero)."""
+    from .proc3d import nearest_sums
+
+    na, nb = _n_points(ref_pcd), _n_points(flo_pcd)
+    if na == 0 or nb == 0:
+        raise ValueError("chamfer_distance needs two clouds that are not empty")
+    _, _, sa = nearest_sums(ref_pcd, flo_pcd, None, device=device)
+    _, _, sb = nearest_sums(flo_pcd, ref_pcd, None, device=device)
+    return sa / na + sb / nb
+
+
+def point_cloud_registration_fitness(ref_pcd, flo_pcd, max_distance=2, device=0):
+    """``(fitness, inlier_rmse)`` of open3d's ``evaluate_registration(ref_pcd, flo_pcd, max_distance)``
+    (metrics.py:58-95): every point of ``ref_pcd`` -- the source -- searches ``flo_pcd``; a point is matched iff its
+    nearest target is closer than ``max_distance`` (strict, rule N3); ``fitness`` = matched / points of the source,
+    ``inlier_rmse`` = sqrt(sum d2 / matched); both 0.0 when nothing is matched or the source is empty, which is what
+    open3d returns without correspondences."""
+    from .proc3d import nearest_sums
+
+    Q = _n_points(ref_pcd)
+    n, s2, _ = nearest_sums(ref_pcd, flo_pcd, max_distance, device=device)
+    if Q == 0 or n == 0:
+        return 0.0, 0.0
+    return n / Q, float(np.sqrt(s2 / n))
+
+
+def _device_tables(source, source_ids, target, target_ids, n_labels, device=0):
+    """The product's table function: ``counts[a, b]`` = source points of label id ``a`` whose nearest target point has
+    label id ``b``, by ``sc_nearest`` and ``sc_nearest_confusion``.  With CUDA tensors as points the indices stay on
+    the device and the label ids are sent there."""
+    from .proc3d import nearest_confusion, nearest_points
+
+    index, _ = nearest_points(source, target, None, device=device)
+    if _is_tensor(index):
+        import torch
+        source_ids = torch.from_numpy(np.ascontiguousarray(source_ids, dtype=np.int32)).to(index.device)
+        target_ids = torch.from_numpy(np.ascontiguousarray(target_ids, dtype=np.int32)).to(index.device)
+    return nearest_confusion(index, source_ids, target_ids, n_labels, device=device)
+
+
+class CompareSegmentedPointClouds:
+    """``CompareSegmentedPointClouds`` of the reference (metrics.py:384-519): ``results`` holds, for each direction
+    (``'groundtruth-to-prediction'``, ``'prediction-to-groundtruth'``) and each label of ``set(groundtruth_labels)``,
+    ``tp, fp, tn, fn, precision, recall, iou``, and ``'miou'``: per label the mean of the two directions' IoUs or
+    ``None``.  The reference's naming is kept: ``fp`` = the source point has the label and its nearest target point
+    has not, ``fn`` the reverse.  A label only the prediction has counts as "other".  A ratio with a zero denominator
+    is ``None``.
+
+    The reference asks a ``KDTreeFlann`` once per point; here each direction is one nearest-point search and one
+    ``L x L`` table on the GPU, and everything else follows from the two tables with the reference's expressions.
+    ``tables_fn(source, source_ids, target, target_ids, L)`` is an argument only: the CPU tests pass the checker's."""
+
+    def __init__(self, groundtruth, groundtruth_labels, prediction, prediction_labels, device=0, tables_fn=None):
+        self.groundtruth = groundtruth
+        self.prediction = prediction
+        self.groundtruth_labels = groundtruth_labels
+        self.prediction_labels = prediction_labels
+        self.unique_labels = set(groundtruth_labels)
+        self.device = device
+        self.results = {}
+        self._assure_sizes()
+        if tables_fn is None:  # the product: the HIP kernels
+            def tables_fn(*args):
+                return _device_tables(*args, device=device)
+        self._tables_fn = tables_fn
+        self._evaluate()
+
+    def _assure_sizes(self):
+        self.assure_size(self.groundtruth, self.groundtruth_labels)
+        self.assure_size(self.prediction, self.prediction_labels)
+
+    def assure_size(self, pointcloud, labels):
+        num_points = _n_points(pointcloud)
+        if num_points != len(labels):
+            raise ValueError("The number of points should be the same as the number of "
+                             f"labels (#points({num_points}) != #labels({len(labels)}))")
+
+    def _evaluate(self):
+        names = list(self.unique_labels)  # ids 0..G-1; every other name is id G, "other"
+        ids = {name: k for k, name in enumerate(names)}
+        other = len(names)
+        gt_ids = np.array([ids.get(name, other) for name in self.groundtruth_labels], dtype=np.int32)
+        pr_ids = np.array([ids.get(name, other) for name in self.prediction_labels], dtype=np.int32)
+        L = other + (1 if (pr_ids == other).any() else 0)
+        gt_pts = self.groundtruth.points if hasattr(self.groundtruth, "points") else self.groundtruth
+        pr_pts = self.prediction.points if hasattr(self.prediction, "points") else self.prediction
+        if L == 0:  # no ground-truth point at all: nothing to evaluate
+            self.results = {"groundtruth-to-prediction": {}, "prediction-to-groundtruth": {}, "miou": {}}
+            return
+        self.results["groundtruth-to-prediction"] = self._compare(names, self._tables_fn(gt_pts, gt_ids, pr_pts, pr_ids, L))
+        self.results["prediction-to-groundtruth"] = self._compare(names, self._tables_fn(pr_pts, pr_ids, gt_pts, gt_ids, L))
+        self.results["miou"] = {}
+        for label in names:
+            iou_1 = self.results["groundtruth-to-prediction"][label]["iou"]
+            iou_2 = self.results["prediction-to-groundtruth"][label]["iou"]
+            self.results["miou"][label] = (iou_1 + iou_2) / 2.0 if iou_1 is not None and iou_2 is not None else None
+
+    @staticmethod
+    def _compare(names, table):
+        """One direction's dictionary from its table (rows: the source's label, columns: the nearest target's)."""
+        table = np.asarray(table, dtype=np.int64)
+        total = int(table.sum())
+        results = {}
+        for k, label in enumerate(names):
+            tp = int(table[k, k])
+            fp = int(table[k, :].sum()) - tp
+            fn = int(table[:, k].sum()) - tp
+            res = {"tp": tp, "fp": fp, "tn": total - tp - fp - fn, "fn": fn, "precision": None, "recall": None, "iou": None}
+            if tp + fp > 0:
+                res["precision"] = tp / (tp + fp)
+            if tp + fn > 0:
+                res["recall"] = tp / (tp + fn)
+            if tp + fn + fp > 0:
+                res["iou"] = tp / (tp + fn + fp)
+            results[label] = res
+        return results

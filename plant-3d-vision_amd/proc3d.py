@@ -43,13 +43,14 @@ def gaussian_weights(sigma=1.0, truncate=4.0):
 def release_device_buffers():
     """Give back the device work buffers ``vol2pcd`` keeps between calls (``sc_vol2pcd_release``; it keeps them
     only while they are at most 1 GiB), those of ``cluster_dbscan`` (``sc_dbscan_release``), those of the
-    evaluation counts of ``metrics`` (``sc_eval_release``) and those of ``select_classes`` (``sc_select_release``).
-    ``Backprojection.close`` calls this."""
+    evaluation counts of ``metrics`` (``sc_eval_release``), those of ``select_classes`` (``sc_select_release``) and
+    those of ``nearest_points`` and the cloud metrics (``sc_nearest_release``).  ``Backprojection.close`` calls this."""
     from . import _native as nat
     nat.backend().call("sc_vol2pcd_release")
     nat.backend().call("sc_dbscan_release")
     nat.backend().call("sc_eval_release")
     nat.backend().call("sc_select_release")
+    nat.backend().call("sc_nearest_release")
 
 
 def set_scratch_limit(nbytes):
@@ -384,3 +385,135 @@ def cluster_dbscan(points, eps, min_points, device=0):
     nat.check(b.call("sc_dbscan", nat.addr(keep), 0, P, float(eps), int(min_points), int(device), nat.addr(labels), 0, 0, 0),
               "sc_dbscan", "sc_dbscan_last_error")
     return labels[:P]
+
+
+def _cloud_points(cloud, what):
+    """``cloud`` as the search takes it: ``(kind, points)`` with kind ``"tensor"`` (a contiguous float64 CUDA tensor
+    ``[n, 3]``, used in place) or ``"array"`` (a C-contiguous float64 NumPy array ``[n, 3]``)."""
+    if not isinstance(cloud, np.ndarray) and hasattr(cloud, "points"):
+        cloud = cloud.points
+    if _is_tensor(cloud):
+        import torch
+        if (cloud.dtype != torch.float64 or not cloud.is_cuda or not cloud.is_contiguous() or cloud.dim() != 2
+                or cloud.shape[1] != 3):
+            raise ValueError(f"device {what} must be a contiguous float64 CUDA tensor [n, 3]")
+        return "tensor", cloud
+    pts = np.ascontiguousarray(np.asarray(cloud, dtype=np.float64))
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        if pts.size:
+            raise ValueError(f"{what} must be [n, 3]")
+        pts = pts.reshape(0, 3)
+    return "array", pts
+
+
+def _max_distance_arg(max_distance):
+    """``None`` -> 0.0 (unbounded, rule N3); anything else must be positive and finite (rule N5)."""
+    if max_distance is None:
+        return 0.0
+    md = float(max_distance)
+    if not (md > 0.0 and md != float("inf")):
+        raise ValueError("max_distance must be positive and finite (None: unbounded)")
+    return md
+
+
+def _nearest_call(queries, targets, max_distance, device, want_points, want_sums):
+    """One ``sc_nearest`` call: ``(index, d2, sums)``; ``index`` / ``d2`` are ``None`` without ``want_points``,
+    ``sums`` (NumPy float64 ``[3]``: n, sum d2, sum sqrt d2) is ``None`` without ``want_sums``."""
+    from . import _native as nat
+
+    md = _max_distance_arg(max_distance)
+    qkind, q = _cloud_points(queries, "queries")
+    tkind, t = _cloud_points(targets, "targets")
+    if qkind != tkind:
+        raise ValueError("queries and targets must both be arrays (or clouds) or both CUDA tensors")
+    Q, P = int(q.shape[0]), int(t.shape[0])
+    sums = np.zeros(3, dtype=np.float64) if want_sums else None
+    sptr = nat.addr(sums) if want_sums else 0
+    b = nat.backend()
+    if qkind == "tensor":
+        import torch
+        if q.device != t.device:
+            raise ValueError("queries and targets must be on one device")
+        dev = q.device.index
+        index = d2 = None
+        if want_points:
+            index = torch.full((Q,), -1, dtype=torch.int32, device=q.device)
+            d2 = torch.full((Q,), float("inf"), dtype=torch.float64, device=q.device)
+        if Q and P:  # rule N4 otherwise: the outputs are filled already
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            nat.check(b.call("sc_nearest", q.data_ptr(), 1, Q, t.data_ptr(), 1, P, md, int(dev), index.data_ptr() if want_points else 0,
+                             d2.data_ptr() if want_points else 0, 1, sptr, int(stream)), "sc_nearest", "sc_nearest_last_error")
+        return index, d2, sums
+    index = np.full(max(Q, 1), -1, dtype=np.int32)
+    d2 = np.full(max(Q, 1), np.inf, dtype=np.float64)
+    keep_q = q if Q else np.zeros((1, 3))  # valid addresses for empty clouds
+    keep_t = t if P else np.zeros((1, 3))
+    nat.check(b.call("sc_nearest", nat.addr(keep_q), 0, Q, nat.addr(keep_t), 0, P, md, int(device), nat.addr(index), nat.addr(d2), 0, sptr, 0),
+              "sc_nearest", "sc_nearest_last_error")
+    return (index[:Q], d2[:Q], sums) if want_points else (None, None, sums)
+
+
+def nearest_points(queries, targets, max_distance=None, device=0):
+    """For every query the nearest point of ``targets`` and its squared distance, on the GPU (``sc_nearest``,
+    ``csrc/nearest.hip``): the primitive under open3d's ``compute_point_cloud_distance``,
+    ``evaluate_registration`` and the ``KDTreeFlann`` loop of ``CompareSegmentedPointClouds``.
+
+    queries, targets : array-likes ``[n, 3]``, :class:`PointCloud` objects or anything with ``.points`` -> NumPy
+        ``(index int32 [Q], d2 float64 [Q])``; or two contiguous float64 CUDA torch tensors ``[n, 3]`` on one device,
+        read in place on torch's current stream -> CUDA tensors on that device.  Mixed kinds raise ``ValueError``.
+    max_distance : ``None`` (unbounded) or a positive finite number.
+
+    PARITY UNPINNED: open3d is not available here.  The rules restate nanoflann's search in an
+    order-free form: N1 ``d2 = ((dx dx) + (dy dy)) + (dz dz)`` in float64; N2 the least ``d2`` wins, among equal ``d2``
+    the smallest target index; N3 with ``max_distance`` a query is matched iff ``d2 < max_distance * max_distance``
+    (strict; at exactly ``max_distance`` it is not), an unmatched query reports ``-1`` and ``+inf``; N4 no target: all
+    ``-1`` / ``+inf``.  Deviation (N5): non-finite coordinates, and a ``max_distance`` that is not positive and finite,
+    raise ``ValueError``.  There is no CPU fallback."""
+    index, d2, _ = _nearest_call(queries, targets, max_distance, device, True, False)
+    return index, d2
+
+
+def nearest_sums(queries, targets, max_distance=None, device=0):
+    """``(n, sum d2, sum sqrt(d2))`` over the matched queries (rule N6: added in an order fixed by the number of
+    queries alone, so two calls give the same bits); no per-query array leaves the device."""
+    _, _, sums = _nearest_call(queries, targets, max_distance, device, False, True)
+    return int(sums[0]), float(sums[1]), float(sums[2])
+
+
+def nearest_confusion(index, query_labels, target_labels, n_labels, device=0):
+    """``counts[a, b]`` = queries of label id ``a`` whose nearest target has label id ``b`` (``sc_nearest_confusion``):
+    NumPy int64 ``[L, L]``.  ``index`` / ``query_labels`` are both int32 NumPy arrays or both int32 CUDA tensors,
+    ``target_labels`` either; queries with index -1 are not counted; ids outside ``0..L-1`` raise ``ValueError``."""
+    from . import _native as nat
+
+    L = int(n_labels)
+    if _is_tensor(index) != _is_tensor(query_labels):
+        raise ValueError("index and query_labels must both be arrays or both CUDA tensors")
+    keep, ptrs, on_dev, devs = [], [], [], []
+    for a, what in ((index, "index"), (query_labels, "query_labels"), (target_labels, "target_labels")):
+        if _is_tensor(a):
+            import torch
+            if a.dtype != torch.int32 or not a.is_cuda or not a.is_contiguous() or a.dim() != 1:
+                raise ValueError(f"device {what} must be a contiguous int32 CUDA tensor [n]")
+            keep.append(a)
+            ptrs.append(a.data_ptr() if a.numel() else 0)
+            on_dev.append(1)
+            devs.append(a.device)
+        else:
+            arr = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+            keep.append(arr)
+            ptrs.append(nat.addr(arr) if arr.size else 0)
+            on_dev.append(0)
+    if len(keep[0]) != len(keep[1]):
+        raise ValueError("one label per query")
+    if len(set(devs)) > 1:
+        raise ValueError("the device arrays must be on one device")
+    stream = 0
+    if devs:
+        import torch
+        device = devs[0].index
+        stream = torch.cuda.current_stream(device).cuda_stream
+    counts = np.zeros((max(L, 1), max(L, 1)), dtype=np.int64)
+    nat.check(nat.backend().call("sc_nearest_confusion", ptrs[0], ptrs[1], on_dev[0], len(keep[0]), ptrs[2], on_dev[2], len(keep[2]), L,
+                                 int(device), nat.addr(counts), int(stream)), "sc_nearest_confusion", "sc_nearest_last_error")
+    return counts

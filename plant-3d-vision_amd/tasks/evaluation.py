@@ -1,6 +1,8 @@
 """The ``VoxelsEvaluation`` and ``Segmentation2DEvaluation`` task logic of the reference
 (``plant3dvision/tasks/evaluation.py:356-477``, ``plant3dvision/metrics.py:275-381``) around the device counting
-passes (``metrics.voxel_confusion``, ``metrics.compare_mask_stacks``).
+passes (``metrics.voxel_confusion``, ``metrics.compare_mask_stacks``), and the ``PointCloudEvaluation`` and
+``SegmentedPointCloudEvaluation`` logic (``tasks/evaluation.py:278-353``) around the device's nearest-point search
+(``metrics.point_cloud_registration_fitness``, ``metrics.CompareSegmentedPointClouds``).
 
 As with ``tasks/proc2d.py::masks_run`` and ``tasks/proc3d.py::organ_segmentation_run``, the tasks' *logic* is plain
 functions without luigi / plantdb.  The ground-truth producers and the matplotlib figures of the reference stay where
@@ -89,3 +91,57 @@ def segmentation2d_evaluation_run(groundtruth_files, prediction_files, labels, d
             metrics_label += metrics_file
         results[label] = metrics_label.as_dict()
     return results
+
+
+def _points_of(cloud):
+    return cloud.points if not isinstance(cloud, np.ndarray) and hasattr(cloud, "points") else cloud
+
+
+def _subset(points, idx):
+    """The rows ``idx`` of a NumPy array or of a CUDA tensor (which stays on its device)."""
+    if not isinstance(points, np.ndarray) and hasattr(points, "data_ptr"):
+        import torch
+        return points[torch.as_tensor(idx, dtype=torch.long, device=points.device)].contiguous()
+    return np.asarray(points, dtype=np.float64).reshape(-1, 3)[idx]
+
+
+def point_cloud_evaluation_run(source, target, labels=None, labels_gt=None, max_distance=2, task_id=None, registration_fn=None):
+    """``PointCloudEvaluation.evaluate`` (tasks/evaluation.py:319-353) without luigi / plantdb.
+
+    source, target : the evaluated cloud and the ground truth, as ``proc3d.nearest_points`` takes them.
+    labels, labels_gt : one name per point of ``source`` / ``target``, or ``labels = None`` for the whole clouds only.
+    registration_fn : ``metrics.point_cloud_registration_fitness`` by default; an argument only, the CPU tests pass a
+        function of theirs.  Called as ``registration_fn(source, target, max_distance)`` -> ``(fitness, inlier_rmse)``.
+
+    Returns ``{"id": task_id, "all": {...}, label: {"fitness", "inlier_rmse"}}``: a label per name of
+    ``set(labels_gt)``; a name without a ground-truth point is skipped (:341-342), one without a source point gives
+    0.0 / 0.0 (what open3d returns for an empty source)."""
+    if registration_fn is None:  # the product: the HIP kernels
+        from ..metrics import point_cloud_registration_fitness as registration_fn
+    fitness, rmse = registration_fn(source, target, max_distance)
+    out = {"id": task_id, "all": {"fitness": fitness, "inlier_rmse": rmse}}
+    if labels is not None:
+        src, tgt = _points_of(source), _points_of(target)
+        for name in set(labels_gt):
+            idx = [i for i in range(len(labels)) if labels[i] == name]
+            idx_gt = [i for i in range(len(labels_gt)) if labels_gt[i] == name]
+            if len(idx_gt) == 0:
+                continue
+            logger.debug("label : %s, gt points: %i, pcd points: %i", name, len(idx_gt), len(idx))
+            fitness, rmse = registration_fn(_subset(src, idx), _subset(tgt, idx_gt), max_distance) if idx else (0.0, 0.0)
+            out[name] = {"fitness": fitness, "inlier_rmse": rmse}
+    return out
+
+
+def segmented_point_cloud_evaluation_run(prediction, labels, groundtruth, labels_gt, compare_fn=None):
+    """``SegmentedPointCloudEvaluation.evaluate`` (tasks/evaluation.py:278-290) without luigi / plantdb: the
+    ``results`` of ``CompareSegmentedPointClouds(groundtruth, labels_gt, prediction, labels)``.  Empty ``labels``
+    raise the reference's ``ValueError`` (:284-286).
+
+    compare_fn : ``metrics.CompareSegmentedPointClouds`` by default; an argument only, the CPU tests pass a function
+        of theirs.  Called as ``compare_fn(groundtruth, labels_gt, prediction, labels)``; its ``.results`` is returned."""
+    if len(labels) == 0:
+        raise ValueError("The labels parameter is empty. No continuing because the results may not be what expected.")
+    if compare_fn is None:  # the product: the HIP kernels
+        from ..metrics import CompareSegmentedPointClouds as compare_fn
+    return compare_fn(groundtruth, labels_gt, prediction, labels).results
