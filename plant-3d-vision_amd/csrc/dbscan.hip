@@ -10,10 +10,11 @@
 //   5. a non-core point with core neighbours takes the smallest id among them;  6. every other point is -1.
 //
 // No neighbour list is stored: every pass finds its candidates again in a uniform grid of cells (points sorted by a
-// hash of their cell, a counting sort) and decides each pair with rules 1 and 2 alone.  Launches per call: finite,
+// hash of their cell, a counting sort) and decides each pair with rules 1 and 2 alone.  Launches per call: finite (sc_points.h),
 // histogram, [scan], scatter, core, link, flatten, border, [scan], labels.  The link launch is the only one in
 // which blocks exchange data (the parent array): every access to it there is a relaxed agent-scope atomic.
-// Stand-alone unit: nothing shared with the carve's engine.
+// Stand-alone unit: nothing shared with the carve's engine; rule 1 (dist2) and the judges of non-finite coordinates
+// are sc_points.h, shared with nearest.hip.
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -23,6 +24,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "sc_points.h"
 #include "sc_unit.h"
 
 namespace {
@@ -75,11 +77,6 @@ __device__ __forceinline__ uint32_t bucket_of(int64_t cx, int64_t cy, int64_t cz
     return (uint32_t)h & mask;
 }
 
-__device__ __forceinline__ double dist2(double ax, double ay, double az, double bx, double by, double bz) {
-    const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
-
 // Calls f(t, original index of t) for every sorted slot t whose point is a neighbour (rules 1, 2) of the point at
 // (x, y, z), itself included; f returns true to stop.
 template <class F>
@@ -102,20 +99,6 @@ __device__ __forceinline__ void for_each_neighbour(const Grid &g, const uint32_t
                         if (f(t, (int)c.w)) return;
                 }
             }
-}
-
-// ---- finite: whether every coordinate is finite (device points have no other judge) -----------------------------
-// flag: zeroed before the launch; one add per block that saw a NaN or an infinity.
-__global__ __launch_bounds__(kB) void dbscan_finite_kernel(const double *__restrict__ pts, int64_t n3, unsigned int *flag) {
-    __shared__ int sbad;
-    if (threadIdx.x == 0) sbad = 0;
-    __syncthreads();
-    int bad = 0;
-    for (int64_t k = (int64_t)blockIdx.x * kB + threadIdx.x; k < n3; k += (int64_t)gridDim.x * kB)
-        if (!(fabs(pts[k]) <= DBL_MAX)) bad = 1;
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&sbad, 1);
-    __syncthreads();
-    if (threadIdx.x == 0 && sbad) atomicAdd(flag, 1u);
 }
 
 // ---- counting sort by bucket -----------------------------------------------------------------------------------
@@ -258,13 +241,7 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
         return g_err.fail(SC_ERR_INVALID, "eps * eps must be a normal number (eps out of range)");
     if (min_points < 0) return g_err.fail(SC_ERR_INVALID, "min_points must not be negative");
     if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
-    if (!points_on_device)
-        for (int64_t k = 0; k < 3 * P; ++k)
-            if (!std::isfinite(points[k])) {
-                char msg[160];
-                snprintf(msg, sizeof msg, "non-finite coordinate in point %lld", (long long)(k / 3));
-                return g_err.fail(SC_ERR_INVALID, msg);
-            }
+    if (!points_on_device && first_non_finite(g_err, points, P, "point") != SC_OK) return SC_ERR_INVALID;
     if (P == 0) {
         if (nclusters_out) *nclusters_out = 0;
         return SC_OK;
@@ -276,10 +253,9 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
     const uint32_t blocks = (uint32_t)((P + kB - 1) / kB);
     const int64_t minp = std::max<int64_t>(min_points, 1);  // a point is its own neighbour: 0 behaves as 1
 
-    WorkSlot &sl = g_slots[device];
-    std::lock_guard<std::mutex> lock(sl.mu);
     int rc = SC_OK;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    UnitCall call(g_err, g_slots, device, stream, rc);
     size_t tmp1 = 0, tmp2 = 0;
     double anchor[3] = {0, 0, 0};
     unsigned int bad = 0;
@@ -297,15 +273,14 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
     const size_t o_pts = lay.take(points_on_device ? 0 : (size_t)P * 24), o_lab = lay.take(labels_on_device ? 0 : (size_t)P * 4);
     size_t o_tmp = 0;  // the scans' temporary storage: the last buffer, sized below
 
-    UNIT_TRY(hipSetDevice(device));
-    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
+    if ((rc = call.enter()) != SC_OK) goto done;
     // the scans' temporary storage (a size query: no device work)
     UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(nb + 1), stream));
     UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (const int *)nullptr, (int *)nullptr, n, stream));
     o_tmp = lay.take(std::max(tmp1, tmp2));
-    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
+    if ((rc = call.grow(lay.total)) != SC_OK) goto done;
     {
-        char *const w = sl.base;
+        char *const w = call.sl.base;
         unsigned int *flag = reinterpret_cast<unsigned int *>(w + o_hdr);
         uint32_t *count = reinterpret_cast<uint32_t *>(w + o_count), *start = reinterpret_cast<uint32_t *>(w + o_start),
                  *cursor = reinterpret_cast<uint32_t *>(w + o_cursor);
@@ -319,15 +294,15 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
         int32_t *lab_d = labels_on_device ? labels_out : reinterpret_cast<int32_t *>(w + o_lab);
         void *tmp_d = w + o_tmp;
 
-        UNIT_TRY(sl.wait(stream));
+        UNIT_TRY(call.sl.wait(stream));
         if (!points_on_device)
             UNIT_TRY(hipMemcpyAsync(w + o_pts, points, (size_t)P * 24, hipMemcpyHostToDevice, stream));
         UNIT_TRY(hipMemsetAsync(flag, 0, 128, stream));
-        hipLaunchKernelGGL(dbscan_finite_kernel, dim3(std::min<uint32_t>(blocks, 1024u)), dim3(kB), 0, stream, pts_d, 3 * P, flag);
+        launch_points_finite(stream, pts_d, P, flag);
         UNIT_TRY(hipGetLastError());
         UNIT_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, stream));
         UNIT_TRY(hipMemcpyAsync(anchor, pts_d, 24, hipMemcpyDeviceToHost, stream));
-        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(call.sl.record(stream));
         UNIT_TRY(hipStreamSynchronize(stream));
         if (bad != 0u) {  // device points: the first kernel is the judge
             rc = g_err.fail(SC_ERR_INVALID, "non-finite coordinate in the device points");
@@ -355,7 +330,7 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
         UNIT_TRY(hipGetLastError());
         if (!labels_on_device) UNIT_TRY(hipMemcpyAsync(labels_out, lab_d, (size_t)P * 4, hipMemcpyDeviceToHost, stream));
         if (nclusters_out) UNIT_TRY(hipMemcpyAsync(&ncl, ncl_d, 4, hipMemcpyDeviceToHost, stream));
-        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(call.sl.record(stream));
         if (!labels_on_device || nclusters_out) {
             UNIT_TRY(hipStreamSynchronize(stream));
             if (nclusters_out) *nclusters_out = ncl;
@@ -363,7 +338,6 @@ int sc_dbscan(const double *points, int points_on_device, int64_t P, double eps,
     }
 
 done:
-    if (rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);  // nothing of ours still reads host memory
     return rc;
 }
 

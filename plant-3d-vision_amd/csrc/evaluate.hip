@@ -14,30 +14,31 @@
 // pred != 0, then four sums against gt != 0.  The steps run on bit planes (1 bit per pixel, 64-bit words), up to 32
 // of them per launch on tiles in LDS; more steps take more launches; H + W steps saturate any picture.
 //
-// Every count is an integer: no result depends on the order of the atomics.  Stand-alone unit: nothing shared with
-// the carve's engine or with masks_rgb.hip.
+// Every count is an integer: no result depends on the order of the atomics.  Nothing shared with the engine; the quad
+// walk over volumes is sc_quads.h (with class_select.hip), the dilation of bit planes sc_bitplane.h (with masks_rgb.hip).
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 
+#include "sc_bitplane.h"
+#include "sc_quads.h"
 #include "sc_unit.h"
 
 namespace {
 
-constexpr int kB = 256;
+constexpr int kB = kQuadThreads;
 constexpr int kMaxL = 32;
 
 thread_local UnitError g_err;
-std::atomic<int64_t> g_chunk_bytes{(int64_t)256 << 20};
+ChunkLimit g_chunk;
 
 // ---- volumes ---------------------------------------------------------------------------------------------------
-// A thread owns one quad -- 4 consecutive voxels of one z-row -- of the (y, z) plane and walks a run of x-planes with
-// it: lanes run along z, every value is read once, a quad whose 4 values lie inside the row and whose address is
-// aligned is one wide load (16 bytes of float32, 2 x 16 of float64, 4 of uint8), any other quad up to 4 scalar loads.
+// The quad walk of sc_quads.h: loads and planning come from there.  The geometry stays here: VoxArgs holds QuadGeom's
+// fields flat and the kernel derives its place itself, the arithmetic of quad_at.  With the struct embedded or quad_at
+// called, the compiler schedules this kernel differently and it ran 1 to 2% slower (profiles/units_refactor_ab.json).
 // Ground truth is indexed with its own pitches (gy, gz); only its corner [0:nx, 0:ny, 0:nz] is touched.
 //
 // Counting: the four predicates of a class are wave-wide ballots whose bit counts land in scalar registers; lanes
@@ -48,57 +49,12 @@ std::atomic<int64_t> g_chunk_bytes{(int64_t)256 << 20};
 struct VoxArgs {
     const void *pred[kMaxL];
     const void *gt[kMaxL];  // gt[background] is not read
-    int L, background;
-    int nx, ny, nz;  // of this launch
-    int Q;           // quads per row
-    int xc;          // x-planes per block
-    uint32_t tiles;  // blocks per run of planes
+    int L, background;  // QuadGeom's fields: set_quads and plan_quads fill them
+    int nx, ny, nz, Q, xc;
+    uint32_t tiles;
     int64_t gy, gz;
     double min_contrast;
 };
-
-template <class T>
-__device__ __forceinline__ void load4(const T *p, int nv, double fill, double out[4]);
-
-template <>
-__device__ __forceinline__ void load4<float>(const float *p, int nv, double fill, double out[4]) {
-    if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-        const float4 w = *reinterpret_cast<const float4 *>(p);
-        out[0] = (double)w.x;
-        out[1] = (double)w.y;
-        out[2] = (double)w.z;
-        out[3] = (double)w.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = j < nv ? (double)p[j] : fill;
-    }
-}
-
-template <>
-__device__ __forceinline__ void load4<double>(const double *p, int nv, double fill, double out[4]) {
-    if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-        const double2 a = *reinterpret_cast<const double2 *>(p), b = *reinterpret_cast<const double2 *>(p + 2);
-        out[0] = a.x;
-        out[1] = a.y;
-        out[2] = b.x;
-        out[3] = b.y;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = j < nv ? p[j] : fill;
-    }
-}
-
-template <>
-__device__ __forceinline__ void load4<uint8_t>(const uint8_t *p, int nv, double fill, double out[4]) {
-    if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
-        const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = (double)((w >> (8 * j)) & 255u);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = j < nv ? (double)p[j] : fill;
-    }
-}
 
 template <class TP, class TG>
 __global__ __launch_bounds__(kB) void eval_voxels_kernel(VoxArgs a, unsigned long long *__restrict__ counts,
@@ -236,51 +192,17 @@ __global__ __launch_bounds__(kB) void eval_count_kernel(const uint8_t *__restric
     if (threadIdx.x < 4 && s4[threadIdx.x] != 0u) atomicAdd(&counts[(int64_t)v * 4 + threadIdx.x], (unsigned long long)s4[threadIdx.x]);
 }
 
-// `steps` (1..kRound) steps of the cross on the bit planes, `in` -> `out` (two different buffers).  A block owns
-// kTR rows x kTW words of one picture: it loads them with a halo of `steps` rows above and below and one word left
-// and right (steps <= 32 < 64 bits), runs the steps in LDS (ping-pong) and writes its own part.  What is wrong at the
-// rim of the halo after k steps has moved k pixels inward: never into the block's own part.  Pixels outside the
-// picture are background after every step.
-constexpr int kTR = 32, kTW = 8, kLW = kTW + 2, kRound = 32;
-constexpr int kLRmax = kTR + 2 * kRound;
+// `steps` (1..kMaxSteps) steps of the cross on the bit planes, `in` -> `out` (two different buffers): the tiles of
+// sc_bitplane.h with the constant diamond as every step's footprint, which the compiler folds to the five-term cross.
+struct CrossFoot { __device__ constexpr uint32_t operator()(int) const { return kDiamond; } };
 
 __global__ __launch_bounds__(kB) void eval_dilate_kernel(const unsigned long long *__restrict__ in, int H, int W, int Wd, int tiles_x,
                                                          int tiles_y, int steps, unsigned long long *__restrict__ out) {
-    __shared__ unsigned long long buf[2][kLRmax * kLW];
+    __shared__ unsigned long long buf[2][kPlaneCells];
     const uint32_t per_pic = (uint32_t)tiles_x * (uint32_t)tiles_y;
     const int v = (int)(blockIdx.x / per_pic), t = (int)(blockIdx.x % per_pic);
     const int ty = t / tiles_x, tx = t % tiles_x;
-    const int r0 = ty * kTR - steps, w0 = tx * kTW - 1;  // picture row / word of LDS cell (0, 0)
-    const int LR = kTR + 2 * steps, cells = LR * kLW;
-    const unsigned long long *src = in + (int64_t)v * H * Wd;
-    const unsigned long long last_mask = (W & 63) ? (~0ull >> (64 - (W & 63))) : ~0ull;
-    for (int c = threadIdx.x; c < cells; c += kB) {
-        const int y = r0 + c / kLW, w = w0 + c % kLW;
-        buf[0][c] = (y >= 0 && y < H && w >= 0 && w < Wd) ? src[(int64_t)y * Wd + w] : 0ull;
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int k = 0; k < steps; ++k) {
-        const unsigned long long *a = buf[cur];
-        unsigned long long *o = buf[cur ^ 1];
-        for (int c = threadIdx.x; c < cells; c += kB) {
-            const int lr = c / kLW, lw = c % kLW;
-            const int y = r0 + lr, w = w0 + lw;
-            unsigned long long acc = 0ull;
-            if (y >= 0 && y < H && w >= 0 && w < Wd) {
-                const unsigned long long m = a[c];
-                const unsigned long long l = lw > 0 ? a[c - 1] : 0ull, r = lw < kLW - 1 ? a[c + 1] : 0ull;
-                acc = m | (m >> 1) | (r << 63) | (m << 1) | (l >> 63);
-                if (lr > 0) acc |= a[c - kLW];
-                if (lr < LR - 1) acc |= a[c + kLW];
-                if (w == Wd - 1) acc &= last_mask;
-            }
-            o[c] = acc;
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-    const unsigned long long *res = buf[cur];
+    const unsigned long long *res = buf[dilate_tile<kB>(buf, in + (int64_t)v * H * Wd, H, W, Wd, ty, tx, steps, CrossFoot())];
     unsigned long long *dst = out + (int64_t)v * H * Wd;
     for (int c = threadIdx.x; c < kTR * kTW; c += kB) {
         const int lr = c / kTW, lw = c % kTW;
@@ -293,8 +215,6 @@ __global__ __launch_bounds__(kB) void eval_dilate_kernel(const unsigned long lon
 // Work buffers (counters, projection, bit planes, the slabs of host inputs) are kept per device: the slot protocol
 // of sc_unit.h.
 WorkSlot g_slots[kUnitDevices];
-
-size_t dtype_bytes(int code) { return code == SC_EVAL_F32 ? 4 : code == SC_EVAL_F64 ? 8 : code == SC_EVAL_U8 ? 1 : 0; }
 
 template <class TP>
 void launch_voxels_gt(int gt_dtype, dim3 grid, hipStream_t stream, const VoxArgs &a, unsigned long long *counts, uint8_t *proj) {
@@ -309,15 +229,7 @@ void launch_voxels_gt(int gt_dtype, dim3 grid, hipStream_t stream, const VoxArgs
 // One launch over `planes` x-planes; a.pred / a.gt are device pointers to plane 0 of the launch.
 void launch_voxels(int pred_dtype, int gt_dtype, hipStream_t stream, VoxArgs a, int64_t planes, unsigned long long *counts,
                    uint8_t *proj) {
-    const int64_t tiles = ((int64_t)a.ny * a.Q + kB - 1) / kB;
-    // enough blocks to fill the device, at most 2^20 planes per block (the 32-bit counters in LDS)
-    int64_t runs = std::min<int64_t>(planes, std::max<int64_t>((4096 + tiles - 1) / tiles, (planes + (1 << 20) - 1) >> 20));
-    const int64_t xc = (planes + runs - 1) / runs;
-    runs = (planes + xc - 1) / xc;
-    a.nx = (int)planes;
-    a.xc = (int)xc;
-    a.tiles = (uint32_t)tiles;
-    const dim3 grid((uint32_t)(tiles * runs));
+    const dim3 grid = plan_quads(a, planes);
     if (pred_dtype == SC_EVAL_F32)
         launch_voxels_gt<float>(gt_dtype, grid, stream, a, counts, proj);
     else
@@ -330,7 +242,7 @@ extern "C" {
 
 const char *sc_eval_last_error(void) { return g_err.msg; }
 
-void sc_eval_set_chunk_bytes(int64_t bytes) { g_chunk_bytes.store(bytes > 0 ? bytes : (int64_t)256 << 20); }
+void sc_eval_set_chunk_bytes(int64_t bytes) { g_chunk.set(bytes); }
 
 int sc_eval_voxels(const void *const *pred, int pred_dtype, const void *const *gt, int gt_dtype, int L, int64_t nx, int64_t ny,
                    int64_t nz, int64_t gx, int64_t gy, int64_t gz, int background, double min_contrast, int on_device, int device,
@@ -351,28 +263,20 @@ int sc_eval_voxels(const void *const *pred, int pred_dtype, const void *const *g
     for (int c = 0; c < L; ++c)
         if (!pred[c] || (!gt[c] && c != background)) return g_err.fail(SC_ERR_INVALID, "null volume pointer");
     if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
-    const int Q = (int)((nz + 3) / 4);
-    const int64_t tiles = (ny * Q + kB - 1) / kB;
-    if (tiles * ((nx + (1 << 20) - 1) >> 20) > 0x7fffffffLL - 8192)  // the grid of launch_voxels
-        return g_err.fail(SC_ERR_INVALID, "volume too large for one launch");
+    if (!one_launch_holds(nx, ny, nz)) return g_err.fail(SC_ERR_INVALID, "volume too large for one launch");
 
     const size_t sp = dtype_bytes(pred_dtype), sg = dtype_bytes(gt_dtype);
     const size_t pplane = (size_t)ny * nz * sp, gplane = (size_t)gy * gz * sg;  // one x-plane of a volume
     const int Lg = L - (background >= 0 ? 1 : 0);
     const size_t projbytes = projection_out ? (size_t)L * ny * nz : 0;
 
-    WorkSlot &sl = g_slots[device];
-    std::lock_guard<std::mutex> lock(sl.mu);
     int rc = SC_OK;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    UnitCall call(g_err, g_slots, device, stream, rc);
     unsigned long long raw[kMaxL * 4];
     VoxArgs a;
     memset(&a, 0, sizeof a);
-    a.L = L;
-    a.background = background;
-    a.ny = (int)ny;
-    a.nz = (int)nz;
-    a.Q = Q;
+    set_quads(a, L, background, ny, nz);
     a.gy = gy;
     a.gz = gz;
     a.min_contrast = min_contrast;
@@ -383,22 +287,17 @@ int sc_eval_voxels(const void *const *pred, int pred_dtype, const void *const *g
     int64_t slab = nx;  // x-planes per slab
     size_t o_pred[kMaxL], o_gt[kMaxL];
     if (!on_device) {
-        const size_t limit = (size_t)g_chunk_bytes.load();
-        const size_t per_plane = (size_t)L * pplane + (size_t)Lg * gplane, pad = (size_t)(L + Lg) * 256;
-        const size_t room = limit > lay.total + pad ? limit - lay.total - pad : 0;
-        slab = std::min<int64_t>(nx, std::max<int64_t>(1, (int64_t)(room / per_plane)));  // one plane at least, whatever the limit
+        slab = std::min(nx, slab_planes(g_chunk.get(), lay.total, (size_t)L * pplane + (size_t)Lg * gplane, (size_t)(L + Lg) * 256));
         for (int c = 0; c < L; ++c) o_pred[c] = lay.take((size_t)slab * pplane);
         for (int c = 0; c < L; ++c) o_gt[c] = c == background ? 0 : lay.take((size_t)slab * gplane);
     }
 
-    UNIT_TRY(hipSetDevice(device));
-    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
-    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
+    if ((rc = call.open(lay.total)) != SC_OK) goto done;
     {
-        char *const w = sl.base;
+        char *const w = call.sl.base;
         unsigned long long *counts = reinterpret_cast<unsigned long long *>(w + o_cnt);
         uint8_t *proj = projection_out ? reinterpret_cast<uint8_t *>(w + o_proj) : nullptr;
-        UNIT_TRY(sl.wait(stream));
+        UNIT_TRY(call.sl.wait(stream));
         UNIT_TRY(hipMemsetAsync(counts, 0, sizeof raw, stream));
         if (proj) UNIT_TRY(hipMemsetAsync(proj, 0, projbytes, stream));
         if (on_device) {
@@ -427,7 +326,7 @@ int sc_eval_voxels(const void *const *pred, int pred_dtype, const void *const *g
         }
         UNIT_TRY(hipMemcpyAsync(raw, counts, sizeof raw, hipMemcpyDeviceToHost, stream));
         if (proj) UNIT_TRY(hipMemcpyAsync(projection_out, proj, projbytes, hipMemcpyDeviceToHost, stream));
-        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(call.sl.record(stream));
         UNIT_TRY(hipStreamSynchronize(stream));
         for (int c = 0; c < L; ++c) {  // {pos, neg, tp, fp} -> {tp, fp, tn, fn}
             const int64_t pos = (int64_t)raw[4 * c], neg = (int64_t)raw[4 * c + 1], tp = (int64_t)raw[4 * c + 2], fp = (int64_t)raw[4 * c + 3];
@@ -439,7 +338,6 @@ int sc_eval_voxels(const void *const *pred, int pred_dtype, const void *const *g
     }
 
 done:
-    if (rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);  // nothing of ours still reads host memory
     return rc;
 }
 
@@ -463,24 +361,21 @@ int sc_eval_masks(const void *gt, const void *pred, int on_device, int n, int H,
     const size_t planebytes = k > 0 ? (size_t)nseg * 8 : 0;
     const size_t per_pic = 32 + 2 * planebytes + (on_device ? 0 : 2 * (size_t)npix);
     int64_t nb = std::min<int64_t>(n, 0x7fffffffLL / std::max(sblocks, dblocks));
-    if (!on_device) nb = std::min<int64_t>(nb, std::max<int64_t>(1, (int64_t)((size_t)g_chunk_bytes.load() / per_pic)));
+    if (!on_device) nb = std::min<int64_t>(nb, std::max<int64_t>(1, (int64_t)(g_chunk.get() / per_pic)));
 
-    WorkSlot &sl = g_slots[device];
-    std::lock_guard<std::mutex> lock(sl.mu);
     int rc = SC_OK;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    UnitCall call(g_err, g_slots, device, stream, rc);
     Layout lay;
     const size_t o_cnt = lay.take((size_t)nb * 32), o_b0 = lay.take((size_t)nb * planebytes), o_b1 = lay.take((size_t)nb * planebytes);
     const size_t o_gt = lay.take(on_device ? 0 : (size_t)nb * npix), o_pr = lay.take(on_device ? 0 : (size_t)nb * npix);
 
-    UNIT_TRY(hipSetDevice(device));
-    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
-    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
+    if ((rc = call.open(lay.total)) != SC_OK) goto done;
     {
-        char *const w = sl.base;
+        char *const w = call.sl.base;
         unsigned long long *counts = reinterpret_cast<unsigned long long *>(w + o_cnt);
         unsigned long long *b0 = reinterpret_cast<unsigned long long *>(w + o_b0), *b1 = reinterpret_cast<unsigned long long *>(w + o_b1);
-        UNIT_TRY(sl.wait(stream));
+        UNIT_TRY(call.sl.wait(stream));
         for (int64_t v0 = 0; v0 < n; v0 += nb) {
             const int64_t m = std::min<int64_t>(nb, n - v0);
             const uint8_t *gt_d = static_cast<const uint8_t *>(gt) + (size_t)v0 * npix, *pr_d = static_cast<const uint8_t *>(pred) + (size_t)v0 * npix;
@@ -497,8 +392,8 @@ int sc_eval_masks(const void *gt, const void *pred, int on_device, int n, int H,
             } else {
                 hipLaunchKernelGGL(eval_pack_kernel, dim3((uint32_t)(sblocks * m)), dim3(kB), 0, stream, pr_d, H, W, Wd, (int)sblocks, b0);
                 unsigned long long *from = b0, *to = b1;
-                for (int64_t done_steps = 0; done_steps < k; done_steps += kRound) {
-                    const int steps = (int)std::min<int64_t>(kRound, k - done_steps);
+                for (int64_t done_steps = 0; done_steps < k; done_steps += kMaxSteps) {
+                    const int steps = (int)std::min<int64_t>(kMaxSteps, k - done_steps);
                     hipLaunchKernelGGL(eval_dilate_kernel, dim3((uint32_t)(dblocks * m)), dim3(kB), 0, stream, from, H, W, Wd, tiles_x,
                                        tiles_y, steps, to);
                     std::swap(from, to);
@@ -510,12 +405,11 @@ int sc_eval_masks(const void *gt, const void *pred, int on_device, int n, int H,
             // (the next batch's memset follows this copy on the stream)
             UNIT_TRY(hipMemcpyAsync(counts_out + 4 * v0, counts, (size_t)m * 32, hipMemcpyDeviceToHost, stream));
         }
-        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(call.sl.record(stream));
         UNIT_TRY(hipStreamSynchronize(stream));
     }
 
 done:
-    if (rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);  // nothing of ours still reads host memory
     return rc;
 }
 

@@ -70,6 +70,7 @@ int sc_label_points(const double *points, int64_t P, int L, int V, const double 
     if (P < 0 || L <= 0 || V < 0 || H <= 0 || W <= 0) return g_err.fail(SC_ERR_INVALID, "bad sizes");
     if (P == 0) return SC_OK;
     int rc = SC_OK;
+    CallerDevice caller(device);  // put back when the call ends
     double *pts_d = nullptr, *K_d = nullptr, *R_d = nullptr, *t_d = nullptr, *sc_d = nullptr;
     int32_t *lab_d = nullptr;
     void *m_d = nullptr;

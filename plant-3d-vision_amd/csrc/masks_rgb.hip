@@ -16,19 +16,20 @@
 //
 // Four launches per call: range (min / max per picture), table (the 256 normalised values of every picture),
 // filter (threshold -> 1 bit per pixel, a __ballot per 64 pixels of a row), dilate (the steps on 64-bit words in
-// LDS, then 0 / 255 bytes).  Stand-alone unit: nothing shared with the carve's engine.
+// LDS, then 0 / 255 bytes).  Stand-alone unit: nothing shared with the carve's engine; the dilation of bit planes in
+// LDS and the footprints are sc_bitplane.h, shared with evaluate.hip.
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
+#include "sc_bitplane.h"
 #include "sc_unit.h"
 
 namespace {
 
 constexpr int kB = 256;
-constexpr int kMaxSteps = 32;
 
 thread_local UnitError g_err;
 
@@ -150,16 +151,11 @@ __global__ __launch_bounds__(kB) void masks_filter_kernel(const uint8_t *__restr
 }
 
 // ---- dilate + expand -------------------------------------------------------------------------------------------
-// A block owns kTR rows x kTW words (512 pixels) of one picture.  It loads them with a halo of nsteps rows above
-// and below and one word left and right (nsteps <= 32 < 64 bits), runs the steps on the words in LDS (ping-pong),
-// and writes its own part as bytes.  What is wrong at the rim of the halo after k steps has moved k pixels inward:
-// never into the block's own part.  Pixels outside the picture are cleared after every step.
-constexpr int kTR = 32, kTW = 8, kLW = kTW + 2;
-constexpr int kLRmax = kTR + 2 * kMaxSteps;
-
+// The tiles of sc_bitplane.h with the call's table of footprints; the block writes its own part as bytes.
 struct Steps {
-    uint16_t foot[kMaxSteps];  // 9 bits: bit (dy + 1) * 3 + (dx + 1) = the footprint holds offset (dy, dx)
+    uint16_t foot[kMaxSteps];  // 9-bit sets (sc_bitplane.h)
     int n;
+    __device__ uint32_t operator()(int k) const { return foot[k]; }
 };
 
 __device__ __forceinline__ uint32_t spread4(uint32_t b4) {  // 4 bits -> 4 bytes of 0 / 255
@@ -168,51 +164,13 @@ __device__ __forceinline__ uint32_t spread4(uint32_t b4) {  // 4 bits -> 4 bytes
 
 __global__ __launch_bounds__(kB) void masks_dilate_kernel(const unsigned long long *__restrict__ bits, int H, int W, int Wd,
                                                           int tiles_x, int tiles_y, Steps steps, uint8_t *__restrict__ out) {
-    __shared__ unsigned long long buf[2][kLRmax * kLW];
+    __shared__ unsigned long long buf[2][kPlaneCells];
     const int n = steps.n;
     const uint32_t per_pic = (uint32_t)tiles_x * (uint32_t)tiles_y;
     const int v = (int)(blockIdx.x / per_pic), t = (int)(blockIdx.x % per_pic);
     const int ty = t / tiles_x, tx = t % tiles_x;
-    const int r0 = ty * kTR - n, w0 = tx * kTW - 1;  // picture row / word of LDS cell (0, 0)
-    const int LR = kTR + 2 * n, cells = LR * kLW;
-    const unsigned long long *src = bits + (int64_t)v * H * Wd;
-    const unsigned long long last_mask = (W & 63) ? (~0ull >> (64 - (W & 63))) : ~0ull;
-    for (int c = threadIdx.x; c < cells; c += kB) {
-        const int y = r0 + c / kLW, w = w0 + c % kLW;
-        buf[0][c] = (y >= 0 && y < H && w >= 0 && w < Wd) ? src[(int64_t)y * Wd + w] : 0ull;
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int k = 0; k < n; ++k) {
-        const uint32_t fp = steps.foot[k];
-        const unsigned long long *in = buf[cur];
-        unsigned long long *o = buf[cur ^ 1];
-        for (int c = threadIdx.x; c < cells; c += kB) {
-            const int lr = c / kLW, lw = c % kLW;
-            const int y = r0 + lr, w = w0 + lw;
-            unsigned long long acc = 0ull;
-            if (y >= 0 && y < H && w >= 0 && w < Wd) {
-#pragma unroll
-                for (int dy = -1; dy <= 1; ++dy) {
-                    const uint32_t f3 = (fp >> ((dy + 1) * 3)) & 7u;  // bit 0: dx = -1, bit 1: dx = 0, bit 2: dx = +1
-                    const int sr = lr - dy;                           // out[p] |= in[p - o]
-                    if (f3 == 0u || sr < 0 || sr >= LR) continue;
-                    const unsigned long long *row = in + sr * kLW;
-                    const unsigned long long m = row[lw];
-                    const unsigned long long l = lw > 0 ? row[lw - 1] : 0ull, r = lw < kLW - 1 ? row[lw + 1] : 0ull;
-                    if (f3 & 1u) acc |= (m >> 1) | (r << 63);  // dx = -1: in[x + 1]
-                    if (f3 & 2u) acc |= m;
-                    if (f3 & 4u) acc |= (m << 1) | (l >> 63);  // dx = +1: in[x - 1]
-                }
-                if (w == Wd - 1) acc &= last_mask;
-            }
-            o[c] = acc;
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
+    const unsigned long long *res = buf[dilate_tile<kB>(buf, bits + (int64_t)v * H * Wd, H, W, Wd, ty, tx, n, steps)];
     // expand the block's own kTR x kTW words: 16 pixels per thread and turn
-    const unsigned long long *res = buf[cur];
     uint8_t *dst = out + (int64_t)v * H * W;
     for (int c = threadIdx.x; c < kTR * kTW * 4; c += kB) {
         const int lr = c / (kTW * 4), q = c % (kTW * 4);
@@ -233,17 +191,6 @@ __global__ __launch_bounds__(kB) void masks_dilate_kernel(const unsigned long lo
 // ---- host side -------------------------------------------------------------------------------------------------
 // Work buffers (bits, tables, ranges) are kept per device: the slot protocol of sc_unit.h.
 WorkSlot g_slots[kUnitDevices];
-
-// footprints of masks2d._FOOTPRINTS as 9-bit sets, bit (dy + 1) * 3 + (dx + 1)
-constexpr uint16_t fbit(int dy, int dx) { return (uint16_t)(1u << ((dy + 1) * 3 + (dx + 1))); }
-const uint16_t kFoot[6] = {
-    (uint16_t)(fbit(-1, -1) | fbit(-1, 0) | fbit(-1, 1) | fbit(0, 0) | fbit(1, 0)),   // t0
-    (uint16_t)(fbit(1, -1) | fbit(0, -1) | fbit(-1, -1) | fbit(0, 0) | fbit(0, 1)),   // t90
-    (uint16_t)(fbit(1, 1) | fbit(1, 0) | fbit(1, -1) | fbit(0, 0) | fbit(-1, 0)),     // t180
-    (uint16_t)(fbit(-1, 1) | fbit(0, 1) | fbit(1, 1) | fbit(0, 0) | fbit(0, -1)),     // t270
-    (uint16_t)(fbit(-1, 0) | fbit(0, -1) | fbit(0, 0) | fbit(0, 1) | fbit(1, 0)),     // diamond
-    (uint16_t)0x1ff,                                                                  // square
-};
 
 }  // namespace
 
@@ -283,10 +230,9 @@ int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, i
     if (fblocks * V > 0x7fffffffLL || (int64_t)tiles_x * tiles_y * V > 0x7fffffffLL)
         return g_err.fail(SC_ERR_INVALID, "batch too large for one launch: split it");
 
-    WorkSlot &sl = g_slots[device];
-    std::lock_guard<std::mutex> lock(sl.mu);
     int rc = SC_OK;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    UnitCall call(g_err, g_slots, device, stream, rc);
     uint8_t *rgb_d = nullptr, *out_d = nullptr;  // staging of host pointers (this call's own)
     Layout lay;
     const size_t o_work = lay.take((size_t)V * 8), o_rng = lay.take((size_t)V * 8), o_tab = lay.take((size_t)V * 2048),
@@ -296,14 +242,13 @@ int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, i
     double *table;
     unsigned long long *bits;
     FilterArgs fa{coefs[0], coefs[1], coefs[2], threshold, filter};
+    call.sync_failures = !rgb_on_device || !out_on_device;  // nothing of ours may still use the staging buffers
 
-    UNIT_TRY(hipSetDevice(device));
-    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
-    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
-    work = reinterpret_cast<uint32_t *>(sl.base + o_work);
-    ranges = reinterpret_cast<int32_t *>(sl.base + o_rng);
-    table = reinterpret_cast<double *>(sl.base + o_tab);
-    bits = reinterpret_cast<unsigned long long *>(sl.base + o_bits);
+    if ((rc = call.open(lay.total)) != SC_OK) goto done;
+    work = reinterpret_cast<uint32_t *>(call.sl.base + o_work);
+    ranges = reinterpret_cast<int32_t *>(call.sl.base + o_rng);
+    table = reinterpret_cast<double *>(call.sl.base + o_tab);
+    bits = reinterpret_cast<unsigned long long *>(call.sl.base + o_bits);
     if (rgb_on_device) {
         rgb_d = static_cast<uint8_t *>(const_cast<void *>(rgb));
     } else {
@@ -315,7 +260,7 @@ int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, i
     } else {
         UNIT_TRY(hipMalloc(reinterpret_cast<void **>(&out_d), (size_t)V * npix));
     }
-    UNIT_TRY(sl.wait(stream));
+    UNIT_TRY(call.sl.wait(stream));
     UNIT_TRY(hipMemsetAsync(work, 0, (size_t)V * 8, stream));
     hipLaunchKernelGGL(masks_range_kernel, dim3((uint32_t)(rblocks * V)), dim3(kB), 0, stream, rgb_d, nbytes, (int)rblocks, work);
     hipLaunchKernelGGL(masks_table_kernel, dim3((uint32_t)V), dim3(kB), 0, stream, work, table, ranges);
@@ -330,15 +275,13 @@ int sc_masks_from_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, i
     UNIT_TRY(hipGetLastError());
     if (ranges_out) UNIT_TRY(hipMemcpyAsync(ranges_out, ranges, (size_t)V * 8, hipMemcpyDeviceToHost, stream));
     if (!out_on_device) UNIT_TRY(hipMemcpyAsync(masks_out, out_d, (size_t)V * npix, hipMemcpyDeviceToHost, stream));
-    UNIT_TRY(sl.record(stream));
+    UNIT_TRY(call.sl.record(stream));
     if (ranges_out || !out_on_device || !rgb_on_device) UNIT_TRY(hipStreamSynchronize(stream));
 
 done:
-    if (!rgb_on_device || !out_on_device) {
-        if (rc != SC_OK) (void)hipStreamSynchronize(stream);  // nothing of ours may still use the staging buffers
-        if (!rgb_on_device && rgb_d) (void)hipFree(rgb_d);
-        if (!out_on_device && out_d) (void)hipFree(out_d);
-    }
+    call.settle();
+    if (!rgb_on_device && rgb_d) (void)hipFree(rgb_d);
+    if (!out_on_device && out_d) (void)hipFree(out_d);
     return rc;
 }
 

@@ -17,7 +17,8 @@
 // [scan], scatter, rings, far, [sums, sums_final].  The grid is dense and bounded (sc_nearest.h: plan, cells, the
 // stop rule and its proof).  Every launch reads what an earlier launch wrote or writes its own query's words; the
 // only traffic between blocks inside a launch is integer atomics (the histogram, the cursors, the far list's
-// length, the confusion counts), and nothing depends on their order.  Stand-alone unit: nothing shared with the engine.
+// length, the confusion counts), and nothing depends on their order.  Stand-alone unit: nothing shared with the engine;
+// N1 (dist2), the finite launch and the host's judge of non-finite coordinates are sc_points.h, shared with dbscan.hip.
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -27,7 +28,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "sc_nearest.h"
+#include "sc_nearest.h"  // brings sc_points.h
 #include "sc_unit.h"
 
 namespace {
@@ -99,19 +100,6 @@ __global__ __launch_bounds__(kB) void nearest_box_final_kernel(const double *__r
         __syncthreads();
     }
     if (threadIdx.x < 6) box[threadIdx.x] = sh[threadIdx.x][0];
-}
-
-// flag: zeroed before the launch; one add per block that saw a NaN or an infinity
-__global__ __launch_bounds__(kB) void nearest_finite_kernel(const double *__restrict__ pts, int64_t n3, unsigned int *flag) {
-    __shared__ int sbad;
-    if (threadIdx.x == 0) sbad = 0;
-    __syncthreads();
-    int bad = 0;
-    for (int64_t k = (int64_t)blockIdx.x * kB + threadIdx.x; k < n3; k += (int64_t)gridDim.x * kB)
-        if (!(fabs(pts[k]) <= DBL_MAX)) bad = 1;
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&sbad, 1);
-    __syncthreads();
-    if (threadIdx.x == 0 && sbad) atomicAdd(flag, 1u);
 }
 
 // ---- counting sort of the targets by cell --------------------------------------------------------------------------
@@ -270,16 +258,6 @@ __global__ __launch_bounds__(kB) void nearest_confusion_kernel(const int32_t *__
 // Work buffers are kept per device: the slot protocol of sc_unit.h.  Both entries share the slot.
 WorkSlot g_slots[kUnitDevices];
 
-int first_non_finite(const double *p, int64_t n, const char *what) {
-    for (int64_t k = 0; k < 3 * n; ++k)
-        if (!std::isfinite(p[k])) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "non-finite coordinate in %s %lld", what, (long long)(k / 3));
-            return g_err.fail(SC_ERR_INVALID, msg);
-        }
-    return SC_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -300,14 +278,8 @@ int sc_nearest(const double *queries, int queries_on_device, int64_t Q, const do
     if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
     if (P == 0 && Q > 0 && out_on_device && (index_out || d2_out))
         return g_err.fail(SC_ERR_INVALID, "P == 0 makes no device call: device outputs cannot be filled");
-    if (!queries_on_device) {
-        const int rc = first_non_finite(queries, Q, "query");
-        if (rc != SC_OK) return rc;
-    }
-    if (!targets_on_device) {
-        const int rc = first_non_finite(targets, P, "target");
-        if (rc != SC_OK) return rc;
-    }
+    if (!queries_on_device && first_non_finite(g_err, queries, Q, "query") != SC_OK) return SC_ERR_INVALID;
+    if (!targets_on_device && first_non_finite(g_err, targets, P, "target") != SC_OK) return SC_ERR_INVALID;
     if (sums_out) sums_out[0] = sums_out[1] = sums_out[2] = 0.0;
     if (Q == 0) return SC_OK;
     if (P == 0) {  // N4
@@ -323,10 +295,9 @@ int sc_nearest(const double *queries, int queries_on_device, int64_t Q, const do
     const uint32_t qblocks = (uint32_t)((Q + kB - 1) / kB), pblocks = (uint32_t)((P + kB - 1) / kB);
     const int box_parts = (int)std::min<uint32_t>(pblocks, kPartials), sum_parts = (int)std::min<uint32_t>(qblocks, kPartials);
 
-    WorkSlot &sl = g_slots[device];
-    std::lock_guard<std::mutex> lock(sl.mu);
     int rc = SC_OK;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    UnitCall call(g_err, g_slots, device, stream, rc);
     size_t tmp = 0;
     Header hh;
     nn::Grid g;
@@ -340,14 +311,13 @@ int sc_nearest(const double *queries, int queries_on_device, int64_t Q, const do
     const size_t o_idx = lay.take(index_out && out_on_device ? 0 : (size_t)Q * 4), o_d2 = lay.take(d2_out && out_on_device ? 0 : (size_t)Q * 8);
     size_t o_tmp = 0;  // the scan's temporary storage: the last buffer, sized below
 
-    UNIT_TRY(hipSetDevice(device));
-    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
+    if ((rc = call.enter()) != SC_OK) goto done;
     // the scan's temporary storage for the largest table (a size query: no device work)
     UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(cap + 1), stream));
     o_tmp = lay.take(tmp);
-    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
+    if ((rc = call.grow(lay.total)) != SC_OK) goto done;
     {
-        char *const w = sl.base;
+        char *const w = call.sl.base;
         Header *hdr = reinterpret_cast<Header *>(w + o_hdr);
         double *partial = reinterpret_cast<double *>(w + o_part);
         uint32_t *count = reinterpret_cast<uint32_t *>(w + o_count), *start = reinterpret_cast<uint32_t *>(w + o_start),
@@ -360,16 +330,16 @@ int sc_nearest(const double *queries, int queries_on_device, int64_t Q, const do
         double *d2_d = d2_out && out_on_device ? d2_out : reinterpret_cast<double *>(w + o_d2);
         void *tmp_d = w + o_tmp;
 
-        UNIT_TRY(sl.wait(stream));
+        UNIT_TRY(call.sl.wait(stream));
         if (!queries_on_device) UNIT_TRY(hipMemcpyAsync(w + o_qs, queries, (size_t)Q * 24, hipMemcpyHostToDevice, stream));
         if (!targets_on_device) UNIT_TRY(hipMemcpyAsync(w + o_ts, targets, (size_t)P * 24, hipMemcpyHostToDevice, stream));
         UNIT_TRY(hipMemsetAsync(hdr, 0, sizeof(Header), stream));
         hipLaunchKernelGGL(nearest_box_kernel, dim3(box_parts), dim3(kB), 0, stream, ts_d, np, &hdr->bad_targets, partial);
         hipLaunchKernelGGL(nearest_box_final_kernel, dim3(1), dim3(kB), 0, stream, partial, box_parts, hdr->box);
-        hipLaunchKernelGGL(nearest_finite_kernel, dim3(std::min<uint32_t>(qblocks, 1024u)), dim3(kB), 0, stream, qs_d, 3 * Q, &hdr->bad_queries);
+        launch_points_finite(stream, qs_d, Q, &hdr->bad_queries);
         UNIT_TRY(hipGetLastError());
         UNIT_TRY(hipMemcpyAsync(&hh, hdr, sizeof(Header), hipMemcpyDeviceToHost, stream));
-        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(call.sl.record(stream));
         UNIT_TRY(hipStreamSynchronize(stream));  // the call's one mid-way wait
         if (hh.bad_queries != 0u || hh.bad_targets != 0u) {  // device points: the first kernels are the judge
             rc = g_err.fail(SC_ERR_INVALID, hh.bad_queries ? "non-finite coordinate in the device queries" : "non-finite coordinate in the device targets");
@@ -394,7 +364,7 @@ int sc_nearest(const double *queries, int queries_on_device, int64_t Q, const do
         if (index_out && !out_on_device) UNIT_TRY(hipMemcpyAsync(index_out, idx_d, (size_t)Q * 4, hipMemcpyDeviceToHost, stream));
         if (d2_out && !out_on_device) UNIT_TRY(hipMemcpyAsync(d2_out, d2_d, (size_t)Q * 8, hipMemcpyDeviceToHost, stream));
         if (sums_out) UNIT_TRY(hipMemcpyAsync(hh.sums, hdr->sums, sizeof hh.sums, hipMemcpyDeviceToHost, stream));
-        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(call.sl.record(stream));
         if (sums_out || ((index_out || d2_out) && !out_on_device)) {
             UNIT_TRY(hipStreamSynchronize(stream));
             if (sums_out)
@@ -403,7 +373,6 @@ int sc_nearest(const double *queries, int queries_on_device, int64_t Q, const do
     }
 
 done:
-    if (rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);  // nothing of ours still reads host memory
     return rc;
 }
 
@@ -439,10 +408,9 @@ int sc_nearest_confusion(const int32_t *index, const int32_t *query_labels, int 
     if (Q == 0 || P == 0) return SC_OK;  // with no target every index is -1: nothing is counted
 
     const uint32_t blocks = (uint32_t)std::min<int64_t>((std::max(Q, P) + kB - 1) / kB, 1024);
-    WorkSlot &sl = g_slots[device];
-    std::lock_guard<std::mutex> lock(sl.mu);
     int rc = SC_OK;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    UnitCall call(g_err, g_slots, device, stream, rc);
     unsigned int bad = 0;
 
     Layout lay;
@@ -450,18 +418,16 @@ int sc_nearest_confusion(const int32_t *index, const int32_t *query_labels, int 
     const size_t o_idx = lay.take(on_device ? 0 : (size_t)Q * 4), o_ql = lay.take(on_device ? 0 : (size_t)Q * 4);
     const size_t o_tl = lay.take(target_labels_on_device ? 0 : (size_t)P * 4);
 
-    UNIT_TRY(hipSetDevice(device));
-    if ((rc = sl.first_use(g_err, device, stream)) != SC_OK) goto done;
-    if ((rc = sl.grow(g_err, lay.total)) != SC_OK) goto done;
+    if ((rc = call.open(lay.total)) != SC_OK) goto done;
     {
-        char *const w = sl.base;
+        char *const w = call.sl.base;
         Header *hdr = reinterpret_cast<Header *>(w + o_hdr);
         unsigned long long *counts = reinterpret_cast<unsigned long long *>(w + o_counts);
         const int32_t *idx_d = on_device ? index : reinterpret_cast<const int32_t *>(w + o_idx);
         const int32_t *ql_d = on_device ? query_labels : reinterpret_cast<const int32_t *>(w + o_ql);
         const int32_t *tl_d = target_labels_on_device ? target_labels : reinterpret_cast<const int32_t *>(w + o_tl);
 
-        UNIT_TRY(sl.wait(stream));
+        UNIT_TRY(call.sl.wait(stream));
         if (!on_device) {
             UNIT_TRY(hipMemcpyAsync(w + o_idx, index, (size_t)Q * 4, hipMemcpyHostToDevice, stream));
             UNIT_TRY(hipMemcpyAsync(w + o_ql, query_labels, (size_t)Q * 4, hipMemcpyHostToDevice, stream));
@@ -477,7 +443,7 @@ int sc_nearest_confusion(const int32_t *index, const int32_t *query_labels, int 
         UNIT_TRY(hipGetLastError());
         UNIT_TRY(hipMemcpyAsync(&bad, &hdr->bad_labels, 4, hipMemcpyDeviceToHost, stream));
         UNIT_TRY(hipMemcpyAsync(counts_out, counts, cells * 8, hipMemcpyDeviceToHost, stream));
-        UNIT_TRY(sl.record(stream));
+        UNIT_TRY(call.sl.record(stream));
         UNIT_TRY(hipStreamSynchronize(stream));
         if (bad != 0u) {  // device arrays: the labels launch is the judge
             for (size_t k = 0; k < cells; ++k) counts_out[k] = 0;
@@ -486,7 +452,6 @@ int sc_nearest_confusion(const int32_t *index, const int32_t *query_labels, int 
     }
 
 done:
-    if (rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);  // nothing of ours still reads host memory
     return rc;
 }
 

@@ -1,5 +1,6 @@
 // sc_nearest.h -- the arithmetic of nearest.hip that does not depend on how threads are laid out: the
 // plan of the dense grid over the targets, the cell of a coordinate, the ring walk of one query with its stop rule.
+// (N1's dist2 is sc_points.h's, shared with dbscan.hip.)
 // Host and device: nearest.hip runs it one thread per query; tools/nearest_rehearsal.cpp runs the same text on the
 // CPU, one query after the other, against all pairs.
 #pragma once
@@ -8,13 +9,11 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define NN_HD __host__ __device__ __forceinline__
-#else
-#define NN_HD inline
-#endif
+#include "sc_points.h"
 
 namespace nn {
+
+using ::dist2;  // N1
 
 constexpr int64_t kMaxCells = (int64_t)1 << 22;  // cap on nx * ny * nz: three 16 MiB tables at most
 constexpr int kNearRings = 3;                    // rings 0..3 (at most 7^3 cells) per thread; what is left goes to the far pass
@@ -37,7 +36,7 @@ inline int64_t cell_cap(int64_t P) {
 
 // u(x) = fl(fl(x - lo) / h): the cell coordinate before the floor.  x - lo may overflow to an infinity (the clamp
 // takes it); it is never NaN for finite x and lo, and h is a normal number.
-NN_HD int cell_of(double x, double lo, double h, int n) {
+SC_HD int cell_of(double x, double lo, double h, int n) {
     const double u = floor((x - lo) / h);
     return (int)fmin(fmax(u, 0.0), (double)(n - 1));
 }
@@ -85,16 +84,11 @@ inline void plan_grid(const double lo[3], const double hi[3], int64_t P, double 
     }
 }
 
-NN_HD double dist2(double ax, double ay, double az, double bx, double by, double bz) {
-    const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
-
 // N2: the pair (d2, index) is kept lexicographically.
 struct Best {
     double d2;
     int idx;
-    NN_HD void take(double d, int i) {
+    SC_HD void take(double d, int i) {
         if (d < d2 || (d == d2 && i < idx)) {
             d2 = d;
             idx = i;
@@ -130,14 +124,14 @@ struct Best {
 // sit in the next ring (N2) -- or when ring_bound >= md2: nothing unvisited can be matched (N3).  It also stops when
 // ring r reached the grid's far faces on every axis: nothing is unvisited then, whatever the numbers are.  After
 // ring 0 the bound is 0 and stops nobody.
-NN_HD double ring_bound(double h, int r) {
+SC_HD double ring_bound(double h, int r) {
     const double hr = h * (double)r;
     return (hr * hr) * kShrink;
 }
 
 // Visits ring r of the query cell (cx, cy, cz).  Cells are numbered (z ny + y) nx + x, so a run of cells along x is
 // a run of sorted slots: start[first cell] .. start[last cell + 1].  Every loop is bounded by the cell counts or P.
-NN_HD void visit_ring(const Grid &g, int cx, int cy, int cz, int r, const uint32_t *__restrict__ start,
+SC_HD void visit_ring(const Grid &g, int cx, int cy, int cz, int r, const uint32_t *__restrict__ start,
                       const double *__restrict__ spts, const int *__restrict__ sidx, double qx, double qy, double qz, Best &best) {
     const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
     const int x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < nx - 1 ? cx + r : nx - 1;
@@ -167,7 +161,7 @@ NN_HD void visit_ring(const Grid &g, int cx, int cy, int cz, int r, const uint32
 
 // The ring walk of one query.  Returns true when the answer is final (best holds it, before N3's test); false when
 // kNearRings rings did not settle it: the far pass then searches all P targets.
-NN_HD bool ring_search(const Grid &g, const uint32_t *__restrict__ start, const double *__restrict__ spts,
+SC_HD bool ring_search(const Grid &g, const uint32_t *__restrict__ start, const double *__restrict__ spts,
                        const int *__restrict__ sidx, double qx, double qy, double qz, Best &best) {
     const int cx = cell_of(qx, g.lo[0], g.h, g.n[0]), cy = cell_of(qy, g.lo[1], g.h, g.n[1]), cz = cell_of(qz, g.lo[2], g.h, g.n[2]);
     int last = cx > g.n[0] - 1 - cx ? cx : g.n[0] - 1 - cx;  // the ring that reaches the far faces on every axis

@@ -1,5 +1,6 @@
 // sc_unit.h -- the host scaffold of the stand-alone device units (vol2pcd, label_points, masks_rgb, dbscan, evaluate, class_select, nearest): the
-// "last error" of a unit, the layout of a work buffer, and the per-device work-buffer slot of DESIGN.md 12.
+// "last error" of a unit, the layout of a work buffer, the per-device work-buffer slot of DESIGN.md 12 and the scope
+// of one call on it.  (Device text that units share: sc_quads.h, sc_bitplane.h, sc_points.h.)
 // Host only, internal linkage: every unit that includes it has its own copy and its own state.
 #pragma once
 
@@ -46,19 +47,26 @@ struct Layout {
     }
 };
 
+// Remembers the caller's current device and puts it back when the scope ends: no runtime call then where the scope
+// only ever went to `going`, the caller's own device.
+struct CallerDevice {
+    int was = -1;
+    const int going;
+    explicit CallerDevice(int going_to = -1) : going(going_to) { if (hipGetDevice(&was) != hipSuccess) was = -1; }
+    ~CallerDevice() { if (was >= 0 && was != going) (void)hipSetDevice(was); }
+};
+
 // f(d) for every device ordinal; the caller's current device stays what it was.
 template <class F>
 void on_each_device(F f) {
-    int current = -1;
-    const bool restore = hipGetDevice(&current) == hipSuccess;
+    CallerDevice keep;
     for (int d = 0; d < kUnitDevices; ++d) f(d);
-    if (restore) (void)hipSetDevice(current);
 }
 
 // The work buffers a unit keeps per device; they grow as needed.  Calls are serialised by `mu` while they ENQUEUE; a
 // call waits (on the device, through `last`) for the previous call's work before it touches the buffers, so calls on
-// different streams of one device never overlap in them.  An entry point, in this order: judges its arguments,
-// locks mu, hipSetDevice, first_use, grow, [its own staging], wait, its work, record, [hipStreamSynchronize].
+// different streams of one device never overlap in them.  An entry point judges its arguments, then opens a UnitCall
+// (below), which fixes the order of the rest.
 struct WorkSlot {
     std::mutex mu;
     char *base = nullptr;
@@ -96,6 +104,37 @@ struct WorkSlot {
 
     hipError_t wait(hipStream_t stream) { return hipStreamWaitEvent(stream, last, 0); }  // behind the previous call, whatever its stream was
     hipError_t record(hipStream_t stream) { return hipEventRecord(last, stream); }
+};
+
+// One call of an entry point on its device's slot; declared after `int rc` and before the first `goto done`.  The
+// constructor locks the slot and remembers the caller's device.  enter: hipSetDevice, first_use; grow: the buffers
+// (open is both; a unit that asks the device for a size in between calls the two).  The unit's staging, sl.wait, its
+// work, sl.record and its own hipStreamSynchronize stay explicit.  When the scope ends -- rc is the entry's result
+// by then -- a call that failed on the device waits for the stream (settle: nothing of ours still touches the
+// caller's memory or the unit's staging), then the caller's device is put back and the slot unlocked.
+struct UnitCall {
+    CallerDevice caller;
+    WorkSlot &sl;
+    std::lock_guard<std::mutex> lock;
+    UnitError &err;
+    const int device;
+    const hipStream_t stream;
+    const int &rc;
+    bool sync_failures = true;  // masks_rgb: only while it holds staging buffers
+
+    UnitCall(UnitError &e, WorkSlot *slots, int dev, hipStream_t st, const int &result)
+        : caller(dev), sl(slots[dev]), lock(sl.mu), err(e), device(dev), stream(st), rc(result) {}
+    ~UnitCall() { settle(); }
+
+    int enter() {
+        const hipError_t e = hipSetDevice(device);
+        return e != hipSuccess ? err.hip(e) : sl.first_use(err, device, stream);
+    }
+    int grow(size_t need) { return sl.grow(err, need); }
+    int open(size_t need) { const int r = enter(); return r != SC_OK ? r : grow(need); }
+    void settle() {  // (a second wait on a drained stream costs nothing)
+        if (sync_failures && rc != SC_OK && rc != SC_ERR_INVALID) (void)hipStreamSynchronize(stream);
+    }
 };
 
 void release_slots(WorkSlot *slots) {

@@ -835,6 +835,7 @@ static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t 
     if (!(std::fabs(level_set_value) < 200.0)) return g_err.fail(SC_ERR_INVALID, "level_set_value out of range");
     *points_out = *normals_out = nullptr;
     *count = 0;
+    CallerDevice caller(device);  // put back when the call ends
     const int64_t limit = g_scratch_limit;
     const int H = reach_of(level_set_value) + 8;
     int64_t planes = nx;

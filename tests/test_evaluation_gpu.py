@@ -143,7 +143,8 @@ def test_slabs_equal_one_piece_and_calls_repeat(gpu_device):
 
 
 # ---- masks ------------------------------------------------------------------------------------------------------
-PICTURES = [(1, 1, 1), (3, 1, 1), (1, 37, 41), (3, 37, 41), (1, 64, 130), (3, 64, 130)]
+# (n, 33, 577): two tile rows (a tile has 32) and two tile columns (10 words against a tile's 8), a last word of one bit
+PICTURES = [(1, 1, 1), (3, 1, 1), (1, 37, 41), (3, 37, 41), (1, 64, 130), (3, 64, 130), (1, 33, 577), (2, 33, 577)]
 
 
 @pytest.fixture(scope="module")

@@ -1,9 +1,12 @@
 #!/bin/bash
-# Per-kernel register / LDS / occupancy table of the engine (compile only; no GPU needed).
+# Per-kernel register / LDS / occupancy table (compile only; no GPU needed) of the files of csrc/ named as
+# arguments, e.g. `evaluate.hip nearest.hip`; without arguments, of the engine (spacecarve.hip).
 cd "$(dirname "$0")/../plant-3d-vision_amd/csrc" || exit 1
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-  -fno-gpu-flush-denormals-to-zero -fno-slp-vectorize -I../../include -c --cuda-device-only \
-  -Rpass-analysis=kernel-resource-usage spacecarve.hip -o /dev/null 2>&1 |
+for unit in "${@:-spacecarve.hip}"; do
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
+    -fno-gpu-flush-denormals-to-zero -fno-slp-vectorize -I../../include -c --cuda-device-only \
+    -Rpass-analysis=kernel-resource-usage "$unit" -o /dev/null 2>&1
+done |
 python3 -c '
 import re, sys, subprocess
 cur = None
