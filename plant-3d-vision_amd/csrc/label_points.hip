@@ -71,28 +71,32 @@ int sc_label_points(const double *points, int64_t P, int L, int V, const double 
     if (P == 0) return SC_OK;
     int rc = SC_OK;
     CallerDevice caller(device);  // put back when the call ends
+    const size_t mbytes = (size_t)L * V * H * W, views = (size_t)(V ? V : 1);
+    Layout lay;  // one allocation: points | K | R | t | scores | labels | the masks, where they come from the host
+    const size_t pts_at = lay.take((size_t)P * 24), K_at = lay.take(views * 32), R_at = lay.take(views * 72),
+                 t_at = lay.take(views * 24), sc_at = lay.take((size_t)L * P * 8), lab_at = lay.take((size_t)P * 4),
+                 m_at = masks_on_device ? 0 : lay.take(mbytes ? mbytes : 1);
+    char *base = nullptr;
     double *pts_d = nullptr, *K_d = nullptr, *R_d = nullptr, *t_d = nullptr, *sc_d = nullptr;
     int32_t *lab_d = nullptr;
-    void *m_d = nullptr;
-    const size_t mbytes = (size_t)L * V * H * W;
+    const void *m_d = masks;
     UNIT_TRY(hipSetDevice(device));
-    UNIT_TRY(hipMalloc(&pts_d, (size_t)P * 24));
-    UNIT_TRY(hipMalloc(&K_d, (size_t)(V ? V : 1) * 32));
-    UNIT_TRY(hipMalloc(&R_d, (size_t)(V ? V : 1) * 72));
-    UNIT_TRY(hipMalloc(&t_d, (size_t)(V ? V : 1) * 24));
-    UNIT_TRY(hipMalloc(&sc_d, (size_t)L * P * 8));
-    UNIT_TRY(hipMalloc(&lab_d, (size_t)P * 4));
+    UNIT_TRY(hipMalloc(reinterpret_cast<void **>(&base), lay.total));
+    pts_d = reinterpret_cast<double *>(base + pts_at);
+    K_d = reinterpret_cast<double *>(base + K_at);
+    R_d = reinterpret_cast<double *>(base + R_at);
+    t_d = reinterpret_cast<double *>(base + t_at);
+    sc_d = reinterpret_cast<double *>(base + sc_at);
+    lab_d = reinterpret_cast<int32_t *>(base + lab_at);
     UNIT_TRY(hipMemcpy(pts_d, points, (size_t)P * 24, hipMemcpyHostToDevice));
     if (V) {
         UNIT_TRY(hipMemcpy(K_d, K, (size_t)V * 32, hipMemcpyHostToDevice));
         UNIT_TRY(hipMemcpy(R_d, R, (size_t)V * 72, hipMemcpyHostToDevice));
         UNIT_TRY(hipMemcpy(t_d, t, (size_t)V * 24, hipMemcpyHostToDevice));
     }
-    if (masks_on_device) {
-        m_d = const_cast<void *>(masks);
-    } else {
-        UNIT_TRY(hipMalloc(&m_d, mbytes ? mbytes : 1));
-        if (mbytes) UNIT_TRY(hipMemcpy(m_d, masks, mbytes, hipMemcpyHostToDevice));
+    if (!masks_on_device) {
+        m_d = base + m_at;
+        if (mbytes) UNIT_TRY(hipMemcpy(base + m_at, masks, mbytes, hipMemcpyHostToDevice));
     }
     hipLaunchKernelGGL(label_points_kernel, dim3((uint32_t)((P + kB - 1) / kB)), dim3(kB), 0, nullptr, pts_d, P,
                        L, V, K_d, R_d, t_d, static_cast<const uint8_t *>(m_d), H, W, sc_d, lab_d);
@@ -101,10 +105,7 @@ int sc_label_points(const double *points, int64_t P, int L, int V, const double 
     UNIT_TRY(hipMemcpy(labels_out, lab_d, (size_t)P * 4, hipMemcpyDeviceToHost));
 done:
     (void)hipDeviceSynchronize();
-    if (!masks_on_device && m_d) (void)hipFree(m_d);
-    void *bufs[] = {pts_d, K_d, R_d, t_d, sc_d, lab_d};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    if (base) (void)hipFree(base);
     return rc;
 }
 

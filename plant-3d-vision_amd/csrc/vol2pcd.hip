@@ -38,59 +38,62 @@ constexpr int kBlk = 8;  // activity is tracked per 8x8x8 block of voxels
 
 thread_local UnitError g_err;
 
-// The work buffers (49 bytes per voxel) are kept between calls while they are small (up to 1 GiB: volumes up
-// to ~280^3) -- allocating and freeing them was 2.8 of a call's 4.6 ms -- one per device, handed out to one
-// caller at a time (a second caller on the same device takes its own, freed at the end of the call).
-// sc_vol2pcd_release() gives them back.
-struct ScratchSlot { char *base = nullptr; size_t cap = 0; bool busy = false; };
+// The work buffers (49 bytes per voxel) are kept between calls while they are small (up to 1 GiB: volumes up to
+// ~280^3) -- allocating and freeing them was 2.8 of a call's 4.6 ms -- one per device, handed to one caller at a time
+// (a second caller on the device takes its own, freed when its call ends); sc_vol2pcd_release() gives them back.
+// Larger ones go back when the call ends: 6.6 GB at 512^3 and 52 GB at 1024^3 are HBM that later engines, survivor
+// lists and two-engine runs need -- against 1 ms of a 4.6 ms call saved by keeping them.  (Not sc_unit.h's WorkSlot, on
+// purpose: that one serialises its callers and orders them by an event on their streams; this unit stays on the null
+// stream, waits for the device before a call ends, and lets a second caller work beside the first.)
+struct ScratchSlot {
+    char *base = nullptr; size_t cap = 0; bool busy = false;
+    void drop() { if (base) (void)hipFree(base); base = nullptr; cap = 0; }
+};
 std::mutex g_scratch_mu;
 ScratchSlot g_scratch[kUnitDevices];
-
-char *scratch_take(int device, size_t bytes, bool *cached) {
-    *cached = false;
-    if (device >= 0 && device < kUnitDevices) {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        ScratchSlot &sl = g_scratch[device];
-        if (!sl.busy) {
-            if (sl.cap < bytes) {
-                if (sl.base) (void)hipFree(sl.base);
-                sl.base = nullptr;
-                sl.cap = 0;
-                char *p = nullptr;
-                if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess) return nullptr;
-                sl.base = p;
-                sl.cap = bytes;
-            }
-            sl.busy = true;
-            *cached = true;
-            return sl.base;
-        }
-    }
-    char *p = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess) return nullptr;
-    return p;
-}
-
-// Buffers above this size go back to the device when the call ends: 49 bytes per voxel is 6.6 GB at 512^3 and
-// 52 GB at 1024^3 -- HBM a Voxels -> PointCloud worker would hold while later engines, survivor lists and
-// two-engine runs allocate -- against 1 ms of a 4.6 ms call saved by keeping them.
 constexpr size_t kScratchKeepMax = (size_t)1 << 30;
 
-void scratch_give(int device, char *p, bool cached) {
-    if (!p) return;
-    if (cached) {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        ScratchSlot &sl = g_scratch[device];
-        sl.busy = false;
-        if (sl.cap > kScratchKeepMax) {
-            (void)hipFree(sl.base);
-            sl.base = nullptr;
-            sl.cap = 0;
+// What one call holds on the device: the work buffers (the device's slot if it is free, else its own allocation), the
+// staged copy of a host volume, the points.  The end of the scope WAITS for the device, then frees or gives back.
+struct Held {
+    char *work = nullptr;
+    ScratchSlot *slot = nullptr;  // the device's, where `work` is its cached buffer
+    void *staged = nullptr, *points = nullptr;
+
+    bool take_work(int device, size_t bytes) {
+        if (device >= 0 && device < kUnitDevices) {
+            std::lock_guard<std::mutex> lock(g_scratch_mu);
+            ScratchSlot &sl = g_scratch[device];
+            if (!sl.busy) {
+                if (sl.cap < bytes) {
+                    sl.drop();
+                    char *p = nullptr;
+                    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess) return false;
+                    sl.base = p;
+                    sl.cap = bytes;
+                }
+                sl.busy = true;
+                slot = &sl;
+                work = sl.base;
+                return true;
+            }
         }
-    } else {
-        (void)hipFree(p);
+        return hipMalloc(reinterpret_cast<void **>(&work), bytes) == hipSuccess;
     }
-}
+    ~Held() {
+        (void)hipDeviceSynchronize();
+        if (staged) (void)hipFree(staged);
+        if (points) (void)hipFree(points);
+        if (work && !slot) (void)hipFree(work);
+        if (!slot) return;
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        slot->busy = false;
+        if (slot->cap > kScratchKeepMax) slot->drop();
+    }
+};
+
+// Where a Held owns what is allocated, a failed runtime call is the function's result.
+#define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return g_err.hip(_e); } while (0)
 
 // Geometry shared by the per-voxel kernels.  They run on the ACTIVE 8^3 blocks only (a list built
 // on the device: a few per cent of a plant's volume): thread block b takes list entry b, thread t
@@ -105,43 +108,69 @@ struct Vol {
     int cx0, cx1;            // only shell voxels of planes [cx0, cx1) at hand are put out (the slab without its halo)
 };
 
+// linear block id -> block coordinates, in I's arithmetic (the lists hold 32-bit ids, the block maps are walked in 64)
+struct Blk { int z, y, x; };
+template <typename I>
+__device__ __forceinline__ Blk block_split(I b, I nby, I nbz) {
+    return Blk{(int)(b % nbz), (int)((b / nbz) % nby), (int)(b / (nbz * nby))};
+}
+
+// OR of a block map over the blocks within rb of block k, clipped to the map
+__device__ __forceinline__ uint32_t near_or(const uint8_t *__restrict__ map, Blk k, int rb, int nbx, int nby, int nbz) {
+    uint32_t near = 0;
+    for (int x = max(0, k.x - rb); x <= min(nbx - 1, k.x + rb); ++x)
+        for (int y = max(0, k.y - rb); y <= min(nby - 1, k.y + rb); ++y)
+            for (int z = max(0, k.z - rb); z <= min(nbz - 1, k.z + rb); ++z)
+                near |= map[((int64_t)x * nby + y) * nbz + z];
+    return near;
+}
+
+// list[*count ...] takes `value` of the lanes with `mine`, in lane order: one atomic per wavefront; all lanes call it
+__device__ __forceinline__ void wave_append(bool mine, uint32_t value, uint32_t *__restrict__ list,
+                                            uint32_t *__restrict__ count) {
+    const uint32_t lane = threadIdx.x & 63;
+    const unsigned long long m = __ballot(mine), below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    uint32_t base = 0;
+    if (lane == 0 && m) base = atomicAdd(count, (uint32_t)__popcll(m));
+    base = __shfl(base, 0);
+    if (mine) list[base + (uint32_t)__popcll(m & below)] = value;
+}
+
+// Sum over the 256 threads of a block through s[kB / 64] in LDS; every thread calls it (one barrier) and gets the sum.
+template <typename T>
+__device__ __forceinline__ T block_sum(T mine, T *s) {
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    return s[0] + s[1] + s[2] + s[3];
+}
+
 __device__ __forceinline__ bool voxel(const Vol &v, int q, int &x, int &y, int &z, int64_t &i) {
-    const uint32_t b = v.list[blockIdx.x];
-    const int bz = (int)(b % (uint32_t)v.nbz), by = (int)((b / (uint32_t)v.nbz) % (uint32_t)v.nby),
-              bx = (int)(b / ((uint32_t)v.nbz * (uint32_t)v.nby));
+    const Blk k = block_split<uint32_t>(v.list[blockIdx.x], v.nby, v.nbz);
     const int l = (int)threadIdx.x + q * kB;  // 0..511: dx = l >> 6, dy = (l >> 3) & 7, dz = l & 7
-    x = bx * kBlk + (l >> 6);
-    y = by * kBlk + ((l >> 3) & 7);
-    z = bz * kBlk + (l & 7);
+    x = k.x * kBlk + (l >> 6);
+    y = k.y * kBlk + ((l >> 3) & 7);
+    z = k.z * kBlk + (l & 7);
     if (x >= v.nx || y >= v.ny || z >= v.nz) return false;
     i = ((int64_t)x * v.ny + y) * v.nz + z;
     return true;
 }
 
-// binarise (proc3d.py:515): 16 voxels per thread, one 16-byte store
-template <typename T>
-__global__ __launch_bounds__(kB) void occ_kernel(const T *__restrict__ vol, uint8_t *__restrict__ occ,
-                                                 int64_t n) {
-    int64_t i0 = ((int64_t)blockIdx.x * kB + threadIdx.x) * 16;
-    if (i0 >= n) return;
-    if (i0 + 16 <= n && (reinterpret_cast<uintptr_t>(occ) & 15) == 0) {
-        uint32_t w[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            uint32_t bits = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bits |= ((double)vol[i0 + q * 4 + e] > 0.5 ? 1u : 0u) << (8 * e);
-            w[q] = bits;
-        }
-        *reinterpret_cast<uint4 *>(occ + i0) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-        for (int64_t i = i0; i < min(n, i0 + 16); ++i) occ[i] = (double)vol[i] > 0.5 ? 1 : 0;
-    }
-}
+// binarise (proc3d.py:515), occ[i] = on(in[i]): 16 voxels per thread, one 16-byte store.  The predicates: a value above
+// one half, compared in float64 like the reference's `volume > 0.5`; a class of a winner volume (class_select.hip;
+// DESIGN.md 15), winner == cls.
+struct Above {
+    template <typename T>
+    __device__ __forceinline__ bool operator()(T value) const { return (double)value > 0.5; }
+};
 
-// a class of a winner volume (class_select.hip): occ = winner == cls, the same 16 voxels per thread
-__global__ __launch_bounds__(kB) void occ_class_kernel(const uint8_t *__restrict__ winner, uint8_t *__restrict__ occ, int64_t n,
-                                                       uint32_t cls) {
+struct IsClass {
+    uint32_t cls;
+    __device__ __forceinline__ bool operator()(uint8_t winner) const { return (uint32_t)winner == cls; }
+};
+
+template <typename T, class On>
+__global__ __launch_bounds__(kB) void occ_kernel(const T *__restrict__ in, uint8_t *__restrict__ occ, int64_t n, On on) {
     int64_t i0 = ((int64_t)blockIdx.x * kB + threadIdx.x) * 16;
     if (i0 >= n) return;
     if (i0 + 16 <= n && (reinterpret_cast<uintptr_t>(occ) & 15) == 0) {
@@ -150,12 +179,12 @@ __global__ __launch_bounds__(kB) void occ_class_kernel(const uint8_t *__restrict
         for (int q = 0; q < 4; ++q) {
             uint32_t bits = 0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) bits |= ((uint32_t)winner[i0 + q * 4 + e] == cls ? 1u : 0u) << (8 * e);
+            for (int e = 0; e < 4; ++e) bits |= (on(in[i0 + q * 4 + e]) ? 1u : 0u) << (8 * e);
             w[q] = bits;
         }
         *reinterpret_cast<uint4 *>(occ + i0) = make_uint4(w[0], w[1], w[2], w[3]);
     } else {
-        for (int64_t i = i0; i < min(n, i0 + 16); ++i) occ[i] = (uint32_t)winner[i] == cls ? 1 : 0;
+        for (int64_t i = i0; i < min(n, i0 + 16); ++i) occ[i] = on(in[i]) ? 1 : 0;
     }
 }
 
@@ -171,6 +200,9 @@ struct PackedIn {
     int32_t cyclic, bits;
 };
 
+// A kernel of its own for the word-at-once path: where a plane is whole words, a thread's 16 voxels share a plane and a
+// word, located once.  (It repeats occ_kernel's assemble-and-store and tail: with those shared through helpers the
+// compiler changed the instructions of every occupancy kernel, the four threshold instances included.)
 template <int BITS>
 __global__ __launch_bounds__(kB) void occ_packed_kernel(PackedIn pk, uint8_t *__restrict__ occ, int64_t n, uint64_t plane,
                                                         uint32_t x0) {
@@ -227,17 +259,17 @@ __global__ __launch_bounds__(kB) void block_class_kernel(const uint8_t *__restri
                                                          uint8_t *__restrict__ cls) {
     int64_t b = (int64_t)blockIdx.x * kB + threadIdx.x;
     if (b >= (int64_t)nbx * nby * nbz) return;
-    int bz = (int)(b % nbz), by = (int)((b / nbz) % nby), bx = (int)(b / ((int64_t)nbz * nby));
+    const Blk k = block_split<int64_t>(b, nby, nbz);
     uint32_t fg = 0, bg = 0;
     for (int dx = 0; dx < kBlk; ++dx) {
-        int x = bx * kBlk + dx;
+        int x = k.x * kBlk + dx;
         if (x >= nx) break;
         for (int dy = 0; dy < kBlk; ++dy) {
-            int y = by * kBlk + dy;
+            int y = k.y * kBlk + dy;
             if (y >= ny) break;
             const uint8_t *row = occ + ((int64_t)x * ny + y) * nz;
             for (int dz = 0; dz < kBlk; ++dz) {
-                int z = bz * kBlk + dz;
+                int z = k.z * kBlk + dz;
                 if (z >= nz) break;
                 uint8_t o = row[z];
                 fg |= o;
@@ -255,12 +287,8 @@ __global__ __launch_bounds__(kB) void block_active_kernel(const uint8_t *__restr
                                                           int nbz, int rb, uint8_t *__restrict__ active) {
     int64_t b = (int64_t)blockIdx.x * kB + threadIdx.x;
     if (b >= (int64_t)nbx * nby * nbz) return;
-    int bz = (int)(b % nbz), by = (int)((b / nbz) % nby), bx = (int)(b / ((int64_t)nbz * nby));
-    uint32_t near = 0;
-    for (int x = max(0, bx - rb); x <= min(nbx - 1, bx + rb); ++x)
-        for (int y = max(0, by - rb); y <= min(nby - 1, by + rb); ++y)
-            for (int z = max(0, bz - rb); z <= min(nbz - 1, bz + rb); ++z)
-                near |= cls[((int64_t)x * nby + y) * nbz + z];
+    const Blk k = block_split<int64_t>(b, nby, nbz);
+    const uint32_t near = near_or(cls, k, rb, nbx, nby, nbz);
     uint32_t own = cls[b];
     // own has fg and a bg block is near, or own has bg and an fg block is near
     active[b] = (uint8_t)((((own & 1u) && (near & 2u)) || ((own & 2u) && (near & 1u))) ? 1 : 0);
@@ -278,27 +306,11 @@ __global__ __launch_bounds__(kB) void block_lists_kernel(const uint8_t *__restri
     if (b < (int64_t)nbx * nby * nbz) {
         is_act = active[b] != 0;
         if (!is_act) {
-            int bz = (int)(b % nbz), by = (int)((b / nbz) % nby), bx = (int)(b / ((int64_t)nbz * nby));
-            uint32_t near = 0;
-            for (int x = max(0, bx - rb); x <= min(nbx - 1, bx + rb); ++x)
-                for (int y = max(0, by - rb); y <= min(nby - 1, by + rb); ++y)
-                    for (int z = max(0, bz - rb); z <= min(nbz - 1, bz + rb); ++z)
-                        near |= active[((int64_t)x * nby + y) * nbz + z];
-            is_halo = near != 0;
+            is_halo = near_or(active, block_split<int64_t>(b, nby, nbz), rb, nbx, nby, nbz) != 0;
         }
     }
-    const uint32_t lane = threadIdx.x & 63;
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    unsigned long long ma = __ballot(is_act), mh = __ballot(is_halo);
-    uint32_t ba = 0, bh = 0;
-    if (lane == 0) {
-        if (ma) ba = atomicAdd(&counts[0], (uint32_t)__popcll(ma));
-        if (mh) bh = atomicAdd(&counts[1], (uint32_t)__popcll(mh));
-    }
-    ba = __shfl(ba, 0);
-    bh = __shfl(bh, 0);
-    if (is_act) act_list[ba + (uint32_t)__popcll(ma & below)] = (uint32_t)b;
-    if (is_halo) halo_list[bh + (uint32_t)__popcll(mh & below)] = (uint32_t)b;
+    wave_append(is_act, (uint32_t)b, act_list, &counts[0]);
+    wave_append(is_halo, (uint32_t)b, halo_list, &counts[1]);
 }
 
 // halo blocks: (far, far) in both EDT buffers
@@ -321,12 +333,7 @@ __global__ __launch_bounds__(kB) void column_list_kernel(const uint8_t *__restri
     bool any = false;
     if (c < ncols)
         for (int bz = 0; bz < nbz; ++bz) any |= active[(int64_t)c * nbz + bz] != 0;
-    const uint32_t lane = threadIdx.x & 63;
-    const unsigned long long m = __ballot(any), below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    uint32_t base = 0;
-    if (lane == 0 && m) base = atomicAdd(count, (uint32_t)__popcll(m));
-    base = __shfl(base, 0);
-    if (any) col_list[base + (uint32_t)__popcll(m & below)] = (uint32_t)c;
+    wave_append(any, (uint32_t)c, col_list, count);
 }
 
 // EDT pass along z (the contiguous axis).  Two channels per voxel, packed lo/hi 16 bits:
@@ -499,11 +506,8 @@ __global__ __launch_bounds__(kB) void shell_count_kernel(const double *__restric
         double d;
         c += on_shell(sd, v, x, y, z, lo, hi, i, d) ? 1u : 0u;
     }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        counts[((int64_t)x * v.ny + y) * gridDim.y + blockIdx.y] = s[0] + s[1] + s[2] + s[3];
+    c = block_sum(c, s);
+    if (threadIdx.x == 0) counts[((int64_t)x * v.ny + y) * gridDim.y + blockIdx.y] = c;
 }
 
 // C-order compaction of the shell + the per-point step of proc3d.py:539-553,563
@@ -572,10 +576,8 @@ __global__ __launch_bounds__(kB) void plane_sums_kernel(const uint32_t *__restri
     const uint32_t *c = counts + (int64_t)blockIdx.x * per_plane;
     uint64_t sum = 0;
     for (int64_t i = threadIdx.x; i < per_plane; i += kB) sum += c[i];
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) plane_sum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    sum = block_sum(sum, s);
+    if (threadIdx.x == 0) plane_sum[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(kB) void chunk_offsets_kernel(const uint32_t *__restrict__ counts, int64_t per_plane,
@@ -587,10 +589,8 @@ __global__ __launch_bounds__(kB) void chunk_offsets_kernel(const uint32_t *__res
     // base of this plane = sum of the planes before it
     uint64_t before = 0;
     for (uint32_t x = threadIdx.x; x < blockIdx.x; x += kB) before += plane_sum[x];
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = before;
-    __syncthreads();
-    if (threadIdx.x == 0) carry = s[0] + s[1] + s[2] + s[3];
+    before = block_sum(before, s);
+    if (threadIdx.x == 0) carry = before;
     __syncthreads();
     const uint32_t *c = counts + (int64_t)blockIdx.x * per_plane;
     uint64_t *o = offsets + (int64_t)blockIdx.x * per_plane;
@@ -617,197 +617,189 @@ __global__ __launch_bounds__(kB) void chunk_offsets_kernel(const uint32_t *__res
 
 inline uint32_t blocks_for(int64_t n) { return (uint32_t)((n + kB - 1) / kB); }
 
-}  // namespace
-
-extern "C" {
-
-const char *sc_vol2pcd_last_error(void) { return g_err.msg; }
-
-void sc_free_host(void *p) { free(p); }
+// Every launch of this unit: blocks of kB threads on the null stream.
+template <class... P, class... A>
+void launch(void (*kernel)(P...), dim3 grid, A... args) { hipLaunchKernelGGL(kernel, grid, dim3(kB), 0, nullptr, args...); }
 
 // What can reach a shell voxel: |d| <= |lsv| + sqrt(3) there, gradient 1 + Gaussian 4 per axis.
-static int reach_of(double level_set_value) {
+int reach_of(double level_set_value) {
     return (int)std::ceil(std::fabs(level_set_value) + 1.7321 + 5.0 * 1.7321 + 3.0);
 }
 
-// The work buffers for `planes` x-planes of ny x nz voxels, one allocation of `bytes`: the offsets of
-// occ | cls | active | block lists (active, halo, columns) | their lengths + shell total | plane sums | counts |
-// offsets | sd | A (g0, g1 then ga) | gb | gx | gy | gz
+// The constants of one call: an entry's arguments as they came and, once the driver has judged them, what they imply.
+struct Call {
+    const double *origin;  // [3]
+    double voxel_size, level_set_value;
+    const double *gauss_w;  // [5]
+    int device;
+    int R = 0, rb = 0;          // derived: the reach in voxels and in blocks,
+    double lo = 0.0, hi = 0.0;  // the shell lo < d <= hi
+    void derive() {
+        R = reach_of(level_set_value), rb = (R + kBlk - 1) / kBlk;
+        lo = -level_set_value, hi = -level_set_value + std::sqrt(3.0);
+    }
+};
+
+// The planes at hand as the driver names them: a Vol whose buffers vol2pcd_range fills in.
+Vol planes_at_hand(int64_t nx, int64_t ny, int64_t nz, int xoff, int cx0, int cx1) {
+    const int nby = (int)((ny + kBlk - 1) / kBlk), nbz = (int)((nz + kBlk - 1) / kBlk);
+    return Vol{(int)nx, (int)ny, (int)nz, nby, nbz, nullptr, nullptr, nullptr, xoff, cx0, cx1};
+}
+
+// The work buffers for `planes` x-planes of ny x nz voxels in one allocation of `bytes`, each on a 256-byte boundary:
+// one statement per buffer gives its place and its pointer (null without a `base`: the driver only asks for `bytes`).
 struct ScratchLayout {
-    size_t occ, cls, act, la, lh, lc, ln, pl, cnt, off, sd, a, b, gx, gy, gz, bytes;
-    ScratchLayout(int64_t planes, int64_t ny, int64_t nz) {
-        const size_t n = (size_t)(planes * ny * nz);
-        const size_t nbxy = (size_t)(((planes + kBlk - 1) / kBlk) * ((ny + kBlk - 1) / kBlk)), nb = nbxy * (size_t)((nz + kBlk - 1) / kBlk);
-        const size_t nchunks = (size_t)(planes * ny * ((nz + kChunk - 1) / kChunk));
+    uint8_t *occ, *cls, *act;                             // the occupancy per voxel; class bits and activity per block
+    uint32_t *list_act, *list_halo, *list_cols, *list_n;  // the lists of blocks and columns, their three lengths
+    uint64_t *total, *plane_sum, *offsets;                // the shell's voxels: all, per x-plane, before each chunk
+    uint32_t *counts, *g0, *g1;                           // ... in each chunk; the EDT's two buffers
+    double *sd, *ga, *gb, *gx, *gy, *gz;                  // signed distance, two intermediates, the smoothed gradient
+    size_t bytes;
+
+    ScratchLayout(int64_t planes, int64_t ny, int64_t nz, char *base = nullptr) {
+        const size_t n = (size_t)(planes * ny * nz), nchunks = (size_t)(planes * ny * ((nz + kChunk - 1) / kChunk));
+        const size_t nbxy = (size_t)(((planes + kBlk - 1) / kBlk) * ((ny + kBlk - 1) / kBlk));
+        const size_t nb = nbxy * (size_t)((nz + kBlk - 1) / kBlk);
         Layout lay;
-        occ = lay.take(n);
-        cls = lay.take(nb);
-        act = lay.take(nb);
-        la = lay.take(nb * 4);
-        lh = lay.take(nb * 4);
-        lc = lay.take(nbxy * 4);
-        ln = lay.take(64);
-        pl = lay.take((size_t)planes * 8);
-        cnt = lay.take(nchunks * 4);
-        off = lay.take(nchunks * 8);
-        sd = lay.take(n * 8);
-        a = lay.take(n * 8);
-        b = lay.take(n * 8);
-        gx = lay.take(n * 8);
-        gy = lay.take(n * 8);
-        gz = lay.take(n * 8);
+        auto put = [base](auto *&p, size_t at) { p = base ? reinterpret_cast<decltype(+p)>(base + at) : nullptr; };
+        size_t at;
+        put(occ, lay.take(n));
+        put(cls, lay.take(nb));
+        put(act, lay.take(nb));
+        put(list_act, lay.take(nb * 4));
+        put(list_halo, lay.take(nb * 4));
+        put(list_cols, lay.take(nbxy * 4));
+        put(list_n, at = lay.take(64));
+        put(total, at + 16);  // ALIAS: the total lies in list_n's 64 bytes, behind the three lengths (one memset)
+        put(plane_sum, lay.take((size_t)planes * 8));
+        put(counts, lay.take(nchunks * 4));
+        put(offsets, lay.take(nchunks * 8));
+        put(sd, lay.take(n * 8));
+        put(ga, at = lay.take(n * 8));
+        put(g0, at);          // ALIAS: the EDT's two 4-byte buffers are the halves of ga's 8 n bytes; its last pass has
+        put(g1, at + n * 4);  // read them before the first gradient is written there
+        put(gb, lay.take(n * 8));
+        put(gx, lay.take(n * 8));
+        put(gy, lay.take(n * 8));
+        put(gz, lay.take(n * 8));
         bytes = lay.total;
     }
 };
 
-// The pipeline on x-planes [0, nx) AT HAND -- the whole volume, or a slab of it with its halo: `volume` points at
-// plane `xoff` of the volume, and only the shell voxels of planes [cx0, cx1) at hand are put out.
-static int vol2pcd_range(const void *volume, int on_device, int dtype, int64_t nx, int64_t ny, int64_t nz, int xoff,
-                         int cx0, int cx1, const double origin[3], double voxel_size, double level_set_value,
-                         const double gauss_w[5], int device, double **points_out, double **normals_out,
-                         int64_t *count, const PackedIn *pk = nullptr,  // pk: packed labels instead of `volume`
-                         int sel = -1) {  // sel >= 0: `volume` is a winner volume (uint8), the occupancy is winner == sel
-    *points_out = *normals_out = nullptr;
-    *count = 0;
-    const int64_t n = nx * ny * nz;
-    const size_t esz = dtype == 0 ? 4 : dtype == 1 ? 4 : dtype == 2 ? 8 : 1;
-    const int R = reach_of(level_set_value);
-    const int rb = (R + kBlk - 1) / kBlk;
-    const int nbx = (int)((nx + kBlk - 1) / kBlk), nby = (int)((ny + kBlk - 1) / kBlk),
-              nbz = (int)((nz + kBlk - 1) / kBlk);
-    const int64_t nb = (int64_t)nbx * nby * nbz;
-    const uint32_t nzseg = (uint32_t)((nz + kChunk - 1) / kChunk);
-    const int64_t nchunks = nx * ny * (int64_t)nzseg;
-    const double lo = -level_set_value, hi = -level_set_value + std::sqrt(3.0);
-    int rc = SC_OK;
-    void *vol_d = nullptr;
-    char *scratch = nullptr;
-    bool scratch_cached = false;
-    double *pts_d = nullptr, *nrm_d = nullptr;
-    GaussW gw;
-    memcpy(gw.w, gauss_w, sizeof gw.w);
-    uint64_t total = 0;
-    uint32_t nlist[3] = {0, 0, 0};
-    hipStream_t st = nullptr;
-    const ScratchLayout at(nx, ny, nz);
-    uint8_t *occ, *cls, *act;
-    uint32_t *counts, *g0, *g1, *list_act, *list_halo, *list_cols, *list_n;
-    uint64_t *offs_d, *total_d, *plane_d;
-    double *sd, *ga, *gb, *gx, *gy, *gz;
-    Vol v, vh;
-    dim3 block(kB);
+// What a call makes the occupancy from: a volume to compare with one half (four dtypes; host or device memory), a
+// class of a winner volume (likewise), or the packed labels of a sharded run.
+struct Input {
+    enum Form { kDense, kWinner, kPacked } form;
+    const char *volume = nullptr;  // kDense, kWinner: plane 0 of [nx][ny][nz] ...
+    bool on_device = false;        // ... in the memory of the call's device, else in the host's
+    int dtype = 3;                 // 0 int32, 1 float32, 2 float64, 3 uint8 (a winner volume's)
+    uint32_t cls = 0;              // kWinner
+    PackedIn pk = {};              // kPacked
 
+    size_t elem() const { return dtype == 3 ? 1 : dtype == 2 ? 8 : 4; }  // bytes per voxel of `volume`
+
+    // occ = the occupancy of planes [a, b) of `plane` voxels each; a host volume's go to the device through `staged`
+    int occupancy(int64_t a, int64_t b, uint64_t plane, void *&staged, uint8_t *occ) const {
+        const int64_t n = (b - a) * (int64_t)plane;
+        const dim3 grid(blocks_for((n + 15) / 16));
+        if (form == kPacked) {
+            if (pk.bits == 2) launch(occ_packed_kernel<2>, grid, pk, occ, n, plane, (uint32_t)a);
+            else launch(occ_packed_kernel<1>, grid, pk, occ, n, plane, (uint32_t)a);
+            return SC_OK;
+        }
+        const void *at = volume + (size_t)a * plane * elem();
+        if (!on_device) {
+            HIP_TRY(hipMalloc(&staged, (size_t)n * elem()));
+            HIP_TRY(hipMemcpy(staged, at, (size_t)n * elem(), hipMemcpyHostToDevice));
+            at = staged;
+        }
+        if (form == kWinner) launch(occ_kernel<uint8_t, IsClass>, grid, (const uint8_t *)at, occ, n, IsClass{cls});
+        else if (dtype == 0) launch(occ_kernel<int32_t, Above>, grid, (const int32_t *)at, occ, n, Above{});
+        else if (dtype == 1) launch(occ_kernel<float, Above>, grid, (const float *)at, occ, n, Above{});
+        else if (dtype == 2) launch(occ_kernel<double, Above>, grid, (const double *)at, occ, n, Above{});
+        else launch(occ_kernel<uint8_t, Above>, grid, (const uint8_t *)at, occ, n, Above{});
+        return SC_OK;
+    }
+};
+
+// The pipeline on the planes at hand (`v` comes without its buffers), in four stages; a failure simply returns.
+int vol2pcd_range(const Input &in, const Call &c, Vol v, double **points_out, double **normals_out, int64_t *count) {
+    *points_out = *normals_out = nullptr, *count = 0;
+    const int nbx = (v.nx + kBlk - 1) / kBlk, nby = v.nby, nbz = v.nbz;
+    const uint32_t nzseg = (uint32_t)((v.nz + kChunk - 1) / kChunk);
+    const int64_t nb = (int64_t)nbx * nby * nbz, per_plane = v.ny * (int64_t)nzseg, nchunks = v.nx * per_plane;
     if (nb > 0xffffffffLL || nchunks > 0x7fffffffLL) return g_err.fail(SC_ERR_INVALID, "volume too large");
-    UNIT_TRY(hipSetDevice(device));
-    scratch = scratch_take(device, at.bytes, &scratch_cached);
-    if (!scratch) { rc = g_err.fail(SC_ERR_NOMEM, "device allocation of the work buffers failed"); goto done; }
-    occ = reinterpret_cast<uint8_t *>(scratch + at.occ);
-    cls = reinterpret_cast<uint8_t *>(scratch + at.cls);
-    act = reinterpret_cast<uint8_t *>(scratch + at.act);
-    list_act = reinterpret_cast<uint32_t *>(scratch + at.la);
-    list_halo = reinterpret_cast<uint32_t *>(scratch + at.lh);
-    list_cols = reinterpret_cast<uint32_t *>(scratch + at.lc);
-    list_n = reinterpret_cast<uint32_t *>(scratch + at.ln);
-    total_d = reinterpret_cast<uint64_t *>(scratch + at.ln + 16);
-    plane_d = reinterpret_cast<uint64_t *>(scratch + at.pl);
-    counts = reinterpret_cast<uint32_t *>(scratch + at.cnt);
-    offs_d = reinterpret_cast<uint64_t *>(scratch + at.off);
-    sd = reinterpret_cast<double *>(scratch + at.sd);
-    ga = reinterpret_cast<double *>(scratch + at.a);
-    g0 = reinterpret_cast<uint32_t *>(scratch + at.a);
-    g1 = g0 + n;
-    gb = reinterpret_cast<double *>(scratch + at.b);
-    gx = reinterpret_cast<double *>(scratch + at.gx);
-    gy = reinterpret_cast<double *>(scratch + at.gy);
-    gz = reinterpret_cast<double *>(scratch + at.gz);
-    v = Vol{(int)nx, (int)ny, (int)nz, nby, nbz, act, list_act, list_cols, xoff, cx0, cx1};
-    vh = Vol{(int)nx, (int)ny, (int)nz, nby, nbz, act, list_halo, list_cols, xoff, cx0, cx1};
-    if (pk != nullptr) {
-        on_device = 1;  // (nothing of ours to free)
-    } else if (on_device) {
-        vol_d = const_cast<void *>(volume);
-    } else {
-        UNIT_TRY(hipMalloc(&vol_d, (size_t)n * esz));
-        UNIT_TRY(hipMemcpy(vol_d, volume, (size_t)n * esz, hipMemcpyHostToDevice));
-    }
-    if (pk != nullptr) {
-        if (pk->bits == 2) hipLaunchKernelGGL(occ_packed_kernel<2>, dim3(blocks_for((n + 15) / 16)), block, 0, st, *pk, occ, n, (uint64_t)ny * (uint64_t)nz, (uint32_t)xoff);
-        else hipLaunchKernelGGL(occ_packed_kernel<1>, dim3(blocks_for((n + 15) / 16)), block, 0, st, *pk, occ, n, (uint64_t)ny * (uint64_t)nz, (uint32_t)xoff);
-    } else if (sel >= 0) {
-        hipLaunchKernelGGL(occ_class_kernel, dim3(blocks_for((n + 15) / 16)), block, 0, st, (const uint8_t *)vol_d, occ, n, (uint32_t)sel);
-    } else
-    switch (dtype) {
-        case 0: hipLaunchKernelGGL(occ_kernel<int32_t>, dim3(blocks_for((n + 15) / 16)), block, 0, st, (const int32_t *)vol_d, occ, n); break;
-        case 1: hipLaunchKernelGGL(occ_kernel<float>, dim3(blocks_for((n + 15) / 16)), block, 0, st, (const float *)vol_d, occ, n); break;
-        case 2: hipLaunchKernelGGL(occ_kernel<double>, dim3(blocks_for((n + 15) / 16)), block, 0, st, (const double *)vol_d, occ, n); break;
-        default: hipLaunchKernelGGL(occ_kernel<uint8_t>, dim3(blocks_for((n + 15) / 16)), block, 0, st, (const uint8_t *)vol_d, occ, n); break;
-    }
-    hipLaunchKernelGGL(block_class_kernel, dim3(blocks_for(nb)), block, 0, st, occ, (int)nx, (int)ny, (int)nz, nbx, nby, nbz, cls);
-    hipLaunchKernelGGL(block_active_kernel, dim3(blocks_for(nb)), block, 0, st, cls, nbx, nby, nbz, rb, act);
-    UNIT_TRY(hipMemsetAsync(list_n, 0, 64, st));
-    hipLaunchKernelGGL(block_lists_kernel, dim3(blocks_for(nb)), block, 0, st, act, nbx, nby, nbz, rb, list_act,
-                       list_halo, list_n);
-    hipLaunchKernelGGL(column_list_kernel, dim3(blocks_for((int64_t)nbx * nby)), block, 0, st, act, nbx * nby, nbz,
-                       list_cols, list_n + 2);
-    UNIT_TRY(hipMemsetAsync(counts, 0, (size_t)nchunks * 4, st));  // rows the shell kernels skip count nothing
-    UNIT_TRY(hipGetLastError());
-    // the only host round trip before the result: how many blocks the per-voxel kernels walk
-    UNIT_TRY(hipMemcpy(nlist, list_n, sizeof nlist, hipMemcpyDeviceToHost));
-    if (nlist[0] > 0) {
-        const dim3 ga_(nlist[0]);
-        // halo blocks hold (far, far) in both EDT buffers; other inactive voxels are never read
-        if (nlist[1] > 0) hipLaunchKernelGGL(halo_fill_kernel, dim3(nlist[1]), block, 0, st, g0, g1, vh);
-        hipLaunchKernelGGL(edt_z_kernel, ga_, block, 0, st, occ, g0, v, R);
-        hipLaunchKernelGGL(edt_y_kernel, ga_, block, 0, st, g0, g1, v, R);
-        hipLaunchKernelGGL(edt_x_kernel, ga_, block, 0, st, g1, occ, sd, v, R);
-        UNIT_TRY(hipGetLastError());
-        // gradient along each axis, then gaussian_filter: axes 0, 1, 2 in turn (proc3d.py:525-531)
-        hipLaunchKernelGGL(gradient_kernel<0>, ga_, block, 0, st, sd, ga, v);
-        hipLaunchKernelGGL(gauss_kernel<0>, ga_, block, 0, st, ga, gb, v, gw);
-        hipLaunchKernelGGL(gauss_kernel<1>, ga_, block, 0, st, gb, ga, v, gw);
-        hipLaunchKernelGGL(gauss_kernel<2>, ga_, block, 0, st, ga, gx, v, gw);
-        hipLaunchKernelGGL(gradient_kernel<1>, ga_, block, 0, st, sd, ga, v);
-        hipLaunchKernelGGL(gauss_kernel<0>, ga_, block, 0, st, ga, gb, v, gw);
-        hipLaunchKernelGGL(gauss_kernel<1>, ga_, block, 0, st, gb, ga, v, gw);
-        hipLaunchKernelGGL(gauss_kernel<2>, ga_, block, 0, st, ga, gy, v, gw);
-        hipLaunchKernelGGL(gradient_kernel<2>, ga_, block, 0, st, sd, ga, v);
-        hipLaunchKernelGGL(gauss_kernel<0>, ga_, block, 0, st, ga, gb, v, gw);
-        hipLaunchKernelGGL(gauss_kernel<1>, ga_, block, 0, st, gb, ga, v, gw);
-        hipLaunchKernelGGL(gauss_kernel<2>, ga_, block, 0, st, ga, gz, v, gw);
-        UNIT_TRY(hipGetLastError());
-        const dim3 rows(nlist[2] * 64u, nzseg);
-        hipLaunchKernelGGL(shell_count_kernel, rows, block, 0, st, sd, v, lo, hi, counts);
-        hipLaunchKernelGGL(plane_sums_kernel, dim3((uint32_t)nx), block, 0, st, counts, ny * (int64_t)nzseg, plane_d);
-        hipLaunchKernelGGL(chunk_offsets_kernel, dim3((uint32_t)nx), block, 0, st, counts, ny * (int64_t)nzseg, plane_d,
-                           offs_d, total_d);
-        UNIT_TRY(hipGetLastError());
-        UNIT_TRY(hipMemcpy(&total, total_d, sizeof total, hipMemcpyDeviceToHost));
-    }
-    if (total > 0) {
-        UNIT_TRY(hipMalloc(reinterpret_cast<void **>(&pts_d), (size_t)total * 48));
-        nrm_d = pts_d + total * 3;
-        hipLaunchKernelGGL(shell_points_kernel, dim3(nlist[2] * 64u, nzseg), block, 0, st, sd, gx, gy, gz, v, lo, hi, level_set_value,
-                           origin[0], origin[1], origin[2], voxel_size, counts, offs_d, pts_d, nrm_d);
-        UNIT_TRY(hipGetLastError());
-        *points_out = static_cast<double *>(malloc((size_t)total * 24));
-        *normals_out = static_cast<double *>(malloc((size_t)total * 24));
-        if (!*points_out || !*normals_out) { rc = g_err.fail(SC_ERR_NOMEM, "host allocation failed"); goto done; }
-        UNIT_TRY(hipMemcpy(*points_out, pts_d, (size_t)total * 24, hipMemcpyDeviceToHost));
-        UNIT_TRY(hipMemcpy(*normals_out, nrm_d, (size_t)total * 24, hipMemcpyDeviceToHost));
-    }
-    *count = (int64_t)total;
+    Held held;  // waits for the device, then frees, however the function is left
+    HIP_TRY(hipSetDevice(c.device));
+    if (!held.take_work(c.device, ScratchLayout(v.nx, v.ny, v.nz).bytes))
+        return g_err.fail(SC_ERR_NOMEM, "device allocation of the work buffers failed");
+    const ScratchLayout at(v.nx, v.ny, v.nz, held.work);
+    v.active = at.act, v.list = at.list_act, v.cols = at.list_cols;
 
-done:
-    if (rc != SC_OK) {
-        free(*points_out); free(*normals_out);
-        *points_out = *normals_out = nullptr;
-        *count = 0;
+    // 1: the occupancy, the block map, the lists of active blocks, halo blocks and active columns, and their lengths
+    const dim3 per_block(blocks_for(nb));
+    const int rc = in.occupancy(v.xoff, v.xoff + v.nx, (uint64_t)v.ny * (uint64_t)v.nz, held.staged, at.occ);
+    if (rc != SC_OK) return rc;
+    launch(block_class_kernel, per_block, at.occ, v.nx, v.ny, v.nz, nbx, nby, nbz, at.cls);
+    launch(block_active_kernel, per_block, at.cls, nbx, nby, nbz, c.rb, at.act);
+    HIP_TRY(hipMemsetAsync(at.list_n, 0, 64, nullptr));
+    launch(block_lists_kernel, per_block, at.act, nbx, nby, nbz, c.rb, at.list_act, at.list_halo, at.list_n);
+    launch(column_list_kernel, dim3(blocks_for((int64_t)nbx * nby)), at.act, nbx * nby, nbz, at.list_cols, at.list_n + 2);
+    HIP_TRY(hipMemsetAsync(at.counts, 0, (size_t)nchunks * 4, nullptr));  // rows the shell kernels skip count nothing
+    HIP_TRY(hipGetLastError());
+    uint32_t nlist[3] = {0, 0, 0};  // blocks in the active list, in the halo list; columns in the column list
+    // the only host round trip before the result: how many blocks the per-voxel kernels walk
+    HIP_TRY(hipMemcpy(nlist, at.list_n, sizeof nlist, hipMemcpyDeviceToHost));
+    if (nlist[0] == 0) return SC_OK;
+
+    // 2: the signed distance; per axis its gradient, then gaussian_filter over axes 0, 1, 2 in turn (proc3d.py:525-531)
+    const dim3 active(nlist[0]);
+    Vol halo = v;  // halo blocks hold (far, far) in both EDT buffers; other inactive voxels are never read
+    halo.list = at.list_halo;
+    if (nlist[1] > 0) launch(halo_fill_kernel, dim3(nlist[1]), at.g0, at.g1, halo);
+    launch(edt_z_kernel, active, at.occ, at.g0, v, c.R);
+    launch(edt_y_kernel, active, at.g0, at.g1, v, c.R);
+    launch(edt_x_kernel, active, at.g1, at.occ, at.sd, v, c.R);
+    HIP_TRY(hipGetLastError());
+    decltype(&gradient_kernel<0>) const gradient[3] = {gradient_kernel<0>, gradient_kernel<1>, gradient_kernel<2>};
+    double *const smoothed[3] = {at.gx, at.gy, at.gz};
+    GaussW gw;
+    memcpy(gw.w, c.gauss_w, sizeof gw.w);
+    for (int axis = 0; axis < 3; ++axis) {
+        launch(gradient[axis], active, at.sd, at.ga, v);
+        launch(gauss_kernel<0>, active, at.ga, at.gb, v, gw);
+        launch(gauss_kernel<1>, active, at.gb, at.ga, v, gw);
+        launch(gauss_kernel<2>, active, at.ga, smoothed[axis], v, gw);
     }
-    (void)hipDeviceSynchronize();
-    if (!on_device && vol_d) (void)hipFree(vol_d);
-    scratch_give(device, scratch, scratch_cached);
-    if (pts_d) (void)hipFree(pts_d);
-    return rc;
+    HIP_TRY(hipGetLastError());
+
+    // 3: the shell's voxels per chunk, their C-order offsets, the total
+    const dim3 rows(nlist[2] * 64u, nzseg), per_x((uint32_t)v.nx);
+    uint64_t total = 0;
+    launch(shell_count_kernel, rows, at.sd, v, c.lo, c.hi, at.counts);
+    launch(plane_sums_kernel, per_x, at.counts, per_plane, at.plane_sum);
+    launch(chunk_offsets_kernel, per_x, at.counts, per_plane, at.plane_sum, at.offsets, at.total);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&total, at.total, sizeof total, hipMemcpyDeviceToHost));
+    if (total == 0) return SC_OK;
+
+    // 4: the points and normals, on the device and then in malloc'ed host arrays
+    const size_t bytes = (size_t)total * 24;
+    HIP_TRY(hipMalloc(&held.points, 2 * bytes));
+    double *const pts_d = static_cast<double *>(held.points), *const nrm_d = pts_d + total * 3;
+    launch(shell_points_kernel, rows, at.sd, at.gx, at.gy, at.gz, v, c.lo, c.hi, c.level_set_value, c.origin[0],
+           c.origin[1], c.origin[2], c.voxel_size, at.counts, at.offsets, pts_d, nrm_d);
+    hipError_t e = hipGetLastError();
+    double *P = static_cast<double *>(malloc(bytes)), *N = static_cast<double *>(malloc(bytes));
+    const bool have = P && N;
+    if (have && e == hipSuccess) e = hipMemcpy(P, pts_d, bytes, hipMemcpyDeviceToHost);
+    if (have && e == hipSuccess) e = hipMemcpy(N, nrm_d, bytes, hipMemcpyDeviceToHost);
+    if (!have || e != hipSuccess) {
+        free(P); free(N);
+        return e != hipSuccess ? g_err.hip(e) : g_err.fail(SC_ERR_NOMEM, "host allocation failed");
+    }
+    *points_out = P, *normals_out = N, *count = (int64_t)total;
+    return SC_OK;
 }
 
 // Largest work buffers a call may take (0: no limit).  49 bytes per voxel is 6.6 GB at 512^3 and 52 GB at
@@ -818,36 +810,30 @@ done:
 // reflections at a slab's artificial ends stay inside the halo.  Slabs come in x order, which is the order of
 // the output (C order of the shell voxels).
 // (Default 8 GiB: a 512^3 volume still goes through in one piece, 4.6 ms against 7.5 in 1 GiB slabs; buffers above
-// 1 GiB are given back when the call ends either way, see scratch_give.)
-static int64_t g_scratch_limit = (int64_t)8 << 30;
+// 1 GiB are given back when the call ends either way, see ScratchLease.)
+int64_t g_scratch_limit = (int64_t)8 << 30;
 
-void sc_vol2pcd_set_scratch_limit(int64_t bytes) { g_scratch_limit = bytes < 0 ? 0 : bytes; }
-
-static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t nx, int64_t ny, int64_t nz,
-                          const double origin[3], double voxel_size, double level_set_value,
-                          const double gauss_w[5], int device, double **points_out, double **normals_out,
-                          int64_t *count, const PackedIn *pk, int sel = -1) {
-    if ((!volume && !pk) || !origin || !gauss_w || !points_out || !normals_out || !count)
+int vol2pcd_driver(const Input &in, int64_t nx, int64_t ny, int64_t nz, Call c, double **points_out,
+                   double **normals_out, int64_t *count) {
+    if ((in.form != Input::kPacked && !in.volume) || !c.origin || !c.gauss_w || !points_out || !normals_out || !count)
         return g_err.fail(SC_ERR_INVALID, "null argument");
     if (nx < 2 || ny < 2 || nz < 2) return g_err.fail(SC_ERR_INVALID, "np.gradient needs at least 2 voxels per axis");
     if (nx > 65535 || ny > 65535) return g_err.fail(SC_ERR_INVALID, "x and y are limited to 65535 voxels");
-    if (dtype < 0 || dtype > 3) return g_err.fail(SC_ERR_INVALID, "volume dtype: 0 int32, 1 float32, 2 float64, 3 uint8");
-    if (!(std::fabs(level_set_value) < 200.0)) return g_err.fail(SC_ERR_INVALID, "level_set_value out of range");
-    *points_out = *normals_out = nullptr;
-    *count = 0;
-    CallerDevice caller(device);  // put back when the call ends
+    if (in.dtype < 0 || in.dtype > 3) return g_err.fail(SC_ERR_INVALID, "volume dtype: 0 int32, 1 float32, 2 float64, 3 uint8");
+    if (!(std::fabs(c.level_set_value) < 200.0)) return g_err.fail(SC_ERR_INVALID, "level_set_value out of range");
+    *points_out = *normals_out = nullptr, *count = 0;
+    c.derive();
+    CallerDevice caller(c.device);  // put back when the call ends
     const int64_t limit = g_scratch_limit;
-    const int H = reach_of(level_set_value) + 8;
+    const int H = c.R + 8;
     int64_t planes = nx;
     if (limit > 0 && ScratchLayout(nx, ny, nz).bytes > (size_t)limit) {
         const size_t per_plane = ScratchLayout(64, ny, nz).bytes / 64 + 1;
         planes = std::max<int64_t>((int64_t)((size_t)limit / per_plane), 2 * H + 8);  // at least 8 planes of its own per slab
     }
     if (planes >= nx)
-        return vol2pcd_range(volume, on_device, dtype, nx, ny, nz, 0, 0, (int)nx, origin, voxel_size, level_set_value,
-                             gauss_w, device, points_out, normals_out, count, pk, sel);
+        return vol2pcd_range(in, c, planes_at_hand(nx, ny, nz, 0, 0, (int)nx), points_out, normals_out, count);
     const int64_t S = planes - 2 * H;
-    const size_t esz = dtype == 0 ? 4 : dtype == 1 ? 4 : dtype == 2 ? 8 : 1;
     std::vector<double *> ps, ns;
     std::vector<int64_t> cs;
     int rc = SC_OK;
@@ -855,11 +841,10 @@ static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t 
     for (int64_t c0 = 0; c0 < nx && rc == SC_OK; c0 += S) {
         const int64_t c1 = std::min(nx, c0 + S), a = std::max<int64_t>(0, c0 - H), b = std::min(nx, c1 + H);
         double *p = nullptr, *q = nullptr;
-        int64_t c = 0;
-        rc = vol2pcd_range(pk ? nullptr : static_cast<const char *>(volume) + (size_t)a * ny * nz * esz, on_device, dtype, b - a, ny, nz,
-                           (int)a, (int)(c0 - a), (int)(c1 - a), origin, voxel_size, level_set_value, gauss_w, device, &p, &q, &c, pk, sel);
-        ps.push_back(p); ns.push_back(q); cs.push_back(c);
-        total += c;
+        int64_t got = 0;
+        rc = vol2pcd_range(in, c, planes_at_hand(b - a, ny, nz, (int)a, (int)(c0 - a), (int)(c1 - a)), &p, &q, &got);
+        ps.push_back(p); ns.push_back(q); cs.push_back(got);
+        total += got;
     }
     if (rc == SC_OK && total > 0) {
         double *P = static_cast<double *>(malloc((size_t)total * 24)), *N = static_cast<double *>(malloc((size_t)total * 24));
@@ -884,12 +869,22 @@ static int vol2pcd_driver(const void *volume, int on_device, int dtype, int64_t 
     return rc;
 }
 
-int sc_vol2pcd(const void *volume, int on_device, int dtype, int64_t nx, int64_t ny, int64_t nz,
-               const double origin[3], double voxel_size, double level_set_value,
-               const double gauss_w[5], int device, double **points_out, double **normals_out,
-               int64_t *count) {
-    return vol2pcd_driver(volume, on_device, dtype, nx, ny, nz, origin, voxel_size, level_set_value, gauss_w, device,
-                          points_out, normals_out, count, nullptr);
+}  // namespace
+
+extern "C" {
+
+const char *sc_vol2pcd_last_error(void) { return g_err.msg; }
+
+void sc_free_host(void *p) { free(p); }
+
+void sc_vol2pcd_set_scratch_limit(int64_t bytes) { g_scratch_limit = bytes < 0 ? 0 : bytes; }
+
+int sc_vol2pcd(const void *volume, int on_device, int dtype, int64_t nx, int64_t ny, int64_t nz, const double origin[3],
+               double voxel_size, double level_set_value, const double gauss_w[5], int device, double **points_out,
+               double **normals_out, int64_t *count) {
+    const Input in{Input::kDense, static_cast<const char *>(volume), on_device != 0, dtype};
+    const Call c{origin, voxel_size, level_set_value, gauss_w, device};
+    return vol2pcd_driver(in, nx, ny, nz, c, points_out, normals_out, count);
 }
 
 int sc_vol2pcd_packed(const void *recv_dev, int64_t rank_bytes, int world, int partition, int bits, int64_t nx,
@@ -902,29 +897,27 @@ int sc_vol2pcd_packed(const void *recv_dev, int64_t rank_bytes, int world, int p
     const uint64_t pmax = (uint64_t)(nx + world - 1) / world;
     if ((uint64_t)rank_bytes * 8 < pmax * (uint64_t)ny * (uint64_t)nz * (uint64_t)bits)
         return g_err.fail(SC_ERR_INVALID, "rank stride too small for its planes");
-    const PackedIn pk{static_cast<const uint32_t *>(recv_dev), (uint64_t)rank_bytes / 4, (uint32_t)world, (uint32_t)nx,
-                      partition == 0 ? 1 : 0, bits};
-    return vol2pcd_driver(nullptr, 1, 3, nx, ny, nz, origin, voxel_size, level_set_value, gauss_w, device, points_out,
-                          normals_out, count, &pk);
+    Input in{Input::kPacked};
+    in.pk = PackedIn{static_cast<const uint32_t *>(recv_dev), (uint64_t)rank_bytes / 4, (uint32_t)world, (uint32_t)nx,
+                     partition == 0 ? 1 : 0, bits};
+    const Call c{origin, voxel_size, level_set_value, gauss_w, device};
+    return vol2pcd_driver(in, nx, ny, nz, c, points_out, normals_out, count);
 }
 
 int sc_vol2pcd_class(const uint8_t *winner, int on_device, int cls, int64_t nx, int64_t ny, int64_t nz, const double origin[3],
                      double voxel_size, double level_set_value, const double gauss_w[5], int device, double **points_out,
                      double **normals_out, int64_t *count) {
     if (cls < 0 || cls > 255) return g_err.fail(SC_ERR_INVALID, "cls must be 0..255 (a byte of the winner volume)");
-    return vol2pcd_driver(winner, on_device, 3, nx, ny, nz, origin, voxel_size, level_set_value, gauss_w, device, points_out,
-                          normals_out, count, nullptr, cls);
+    const Input in{Input::kWinner, reinterpret_cast<const char *>(winner), on_device != 0, 3, (uint32_t)cls};
+    const Call c{origin, voxel_size, level_set_value, gauss_w, device};
+    return vol2pcd_driver(in, nx, ny, nz, c, points_out, normals_out, count);
 }
 
 void sc_vol2pcd_release(void) {
     std::lock_guard<std::mutex> lock(g_scratch_mu);
     on_each_device([](int d) {
         ScratchSlot &sl = g_scratch[d];
-        if (sl.base && !sl.busy && hipSetDevice(d) == hipSuccess) {
-            (void)hipFree(sl.base);
-            sl.base = nullptr;
-            sl.cap = 0;
-        }
+        if (sl.base && !sl.busy && hipSetDevice(d) == hipSuccess) sl.drop();
     });
 }
 

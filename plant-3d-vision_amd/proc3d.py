@@ -122,49 +122,52 @@ def vol2pcd(volume, origin, voxel_size, level_set_value=0, device=0, as_open3d=T
     """
     from . import _native as nat
 
-    b = nat.backend()
+    nat.backend()
     codes = {np.dtype(np.int32): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2, np.dtype(np.uint8): 3}
-    keep = None
-    origin64 = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
+    origin64 = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))  # judged before the volume
+    tail = (origin64, voxel_size, level_set_value, as_open3d)
+    if hasattr(volume, "occupancy_device"):  # a sharded run's SparseGrid: its occupancy (label == 1) on the device
+        sg = volume
+        ptr, keep = sg.occupancy_device()
+        return _vol2pcd_call("sc_vol2pcd", (ptr, 1, codes[np.dtype(np.uint8)]), sg.shape, sg.device, *tail)
+    if hasattr(volume, "recv") and hasattr(volume, "rank_bytes"):  # a sharded run's PackedGrid: read as it is
+        import torch
+        pg = volume
+        torch.cuda.synchronize(pg.recv.device)  # the collective that filled it
+        head = (int(pg.recv.data_ptr()), int(pg.rank_bytes), int(pg.world), 0 if pg.partition == "cyclic" else 1, int(pg.bits))
+        return _vol2pcd_call("sc_vol2pcd_packed", head, pg.shape, pg.device, *tail, what="sc_vol2pcd")
+    if hasattr(volume, "_engine") and hasattr(volume, "shape"):  # a Backprojection: use its state in place
+        bp = volume
+        ptr = bp._engine.values_device_ptr()
+        bp._engine.synchronize()
+        shape = [int(s) for s in bp.shape]
+        code, on_device, device = codes[np.dtype(bp.dtype)], 1, bp.device
+    else:
+        vol = np.asarray(volume)
+        if vol.ndim != 3:
+            raise ValueError("volume must be 3-D")
+        if vol.dtype == np.bool_:
+            vol = vol.view(np.uint8)
+        if vol.dtype not in codes:
+            vol = vol.astype(np.float64)
+        keep = np.ascontiguousarray(vol)
+        ptr, shape, code, on_device = nat.addr(keep), list(keep.shape), codes[keep.dtype], 0
+    return _vol2pcd_call("sc_vol2pcd", (ptr, on_device, code), shape, device, *tail)
+
+
+def _vol2pcd_call(entry, head, shape, device, origin64, voxel_size, level_set_value, as_open3d, what=None):
+    """What the ``sc_vol2pcd*`` calls of ``vol2pcd`` and ``vol2pcd_class`` share: the arguments that follow an entry's own
+    (``head``: its input), the call, its check (reported as ``what``, the entry unless given) and the cloud."""
+    from . import _native as nat
+
+    b = nat.backend()
     gw = gaussian_weights(1.0)
     assert gw.size == 5
     out = np.zeros(2, dtype=np.uintp)
     cnt = np.zeros(1, dtype=np.int64)
-    if hasattr(volume, "occupancy_device"):  # a sharded run's SparseGrid: its occupancy (label == 1) on the device
-        sg = volume
-        ptr, keep = sg.occupancy_device()
-        rc = b.call("sc_vol2pcd", ptr, 1, codes[np.dtype(np.uint8)], sg.shape[0], sg.shape[1], sg.shape[2], nat.addr(origin64),
-                    float(voxel_size), float(level_set_value), nat.addr(gw), int(sg.device), nat.addr(out),
-                    nat.addr(out) + 8, nat.addr(cnt))
-    elif hasattr(volume, "recv") and hasattr(volume, "rank_bytes"):  # a sharded run's PackedGrid: read as it is
-        import torch
-        pg = volume
-        torch.cuda.synchronize(pg.recv.device)  # the collective that filled it
-        rc = b.call("sc_vol2pcd_packed", int(pg.recv.data_ptr()), int(pg.rank_bytes), int(pg.world),
-                    0 if pg.partition == "cyclic" else 1, int(pg.bits), pg.shape[0], pg.shape[1], pg.shape[2],
-                    nat.addr(origin64), float(voxel_size), float(level_set_value), nat.addr(gw), int(pg.device),
-                    nat.addr(out), nat.addr(out) + 8, nat.addr(cnt))
-    else:
-        if hasattr(volume, "_engine") and hasattr(volume, "shape"):  # a Backprojection: use its state in place
-            bp = volume
-            ptr = bp._engine.values_device_ptr()
-            bp._engine.synchronize()
-            shape = [int(s) for s in bp.shape]
-            code, on_device, device = codes[np.dtype(bp.dtype)], 1, bp.device
-        else:
-            vol = np.asarray(volume)
-            if vol.ndim != 3:
-                raise ValueError("volume must be 3-D")
-            if vol.dtype == np.bool_:
-                vol = vol.view(np.uint8)
-            if vol.dtype not in codes:
-                vol = vol.astype(np.float64)
-            keep = np.ascontiguousarray(vol)
-            ptr, shape, code, on_device = nat.addr(keep), list(keep.shape), codes[keep.dtype], 0
-        rc = b.call("sc_vol2pcd", ptr, on_device, code, shape[0], shape[1], shape[2], nat.addr(origin64),
-                    float(voxel_size), float(level_set_value), nat.addr(gw), int(device), nat.addr(out),
-                    nat.addr(out) + 8, nat.addr(cnt))
-    nat.check(rc, "sc_vol2pcd", "sc_vol2pcd_last_error")
+    rc = b.call(entry, *head, shape[0], shape[1], shape[2], nat.addr(origin64), float(voxel_size), float(level_set_value),
+                nat.addr(gw), int(device), nat.addr(out), nat.addr(out) + 8, nat.addr(cnt))
+    nat.check(rc, what or entry, "sc_vol2pcd_last_error")
     return _adopt_cloud(b, out, cnt, as_open3d)
 
 
@@ -264,12 +267,8 @@ def vol2pcd_class(winner, index, origin, voxel_size, level_set_value=0, device=0
     index : the class, 0..255 (255: the voxels of no class)."""
     from . import _native as nat
 
-    b = nat.backend()
-    origin64 = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))
-    gw = gaussian_weights(1.0)
-    assert gw.size == 5
-    out = np.zeros(2, dtype=np.uintp)
-    cnt = np.zeros(1, dtype=np.int64)
+    nat.backend()
+    origin64 = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))  # judged before the volume
     if _is_tensor(winner):
         import torch
         if winner.dtype != torch.uint8 or winner.dim() != 3 or not winner.is_contiguous() or not winner.is_cuda:
@@ -283,11 +282,7 @@ def vol2pcd_class(winner, index, origin, voxel_size, level_set_value=0, device=0
             raise ValueError("the winner volume must be uint8 [nx, ny, nz]")
         keep = np.ascontiguousarray(keep)
         ptr, shape, on_device = nat.addr(keep), list(keep.shape), 0
-    rc = b.call("sc_vol2pcd_class", ptr, on_device, int(index), shape[0], shape[1], shape[2], nat.addr(origin64),
-                float(voxel_size), float(level_set_value), nat.addr(gw), int(device), nat.addr(out), nat.addr(out) + 8,
-                nat.addr(cnt))
-    nat.check(rc, "sc_vol2pcd_class", "sc_vol2pcd_last_error")
-    return _adopt_cloud(b, out, cnt, as_open3d)
+    return _vol2pcd_call("sc_vol2pcd_class", (ptr, on_device, int(index)), shape, device, origin64, voxel_size, level_set_value, as_open3d)
 
 
 def backproject_points(points, K, rot, tvec):

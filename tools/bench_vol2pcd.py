@@ -10,12 +10,17 @@ def main():
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--cpu-n", type=int, default=192)
     ap.add_argument("--views", type=int, default=72)
+    ap.add_argument("--no-cpu", action="store_true", help="skip the SciPy leg (device-side A/B of two builds)")
+    ap.add_argument("--scratch-limit", type=int, default=None, help="proc3d.set_scratch_limit(bytes): slabs above it")
     a = ap.parse_args()
     from plant3dvision_amd import proc3d, scenes
     from plant3dvision_amd.cl import Backprojection
-    from oracle import vol2pcd_oracle
+    if not a.no_cpu:
+        from oracle import vol2pcd_oracle
+    if a.scratch_limit is not None:
+        proc3d.set_scratch_limit(a.scratch_limit)
     out = {}
-    for n, do_cpu in ((a.cpu_n, True), (a.n, False)):
+    for n, do_cpu in ((a.cpu_n, not a.no_cpu), (a.n, False)):
         shape, origin, vs, views = scenes.make_scene(n, a.views, "plant")
         bp = Backprojection(shape, origin, vs)
         for K, R, t, m in views:
