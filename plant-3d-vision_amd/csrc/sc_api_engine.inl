@@ -118,54 +118,14 @@ void sc_destroy(sc_engine *e) {
         return;
     }
     (void)hipSetDevice(e->device);
-    if (e->stream) (void)schost::wait_stream(e->stream);
-    for (int k = 0; k < kNumKernels; ++k)
-        for (auto &tl : e->timed[k]) {
-            (void)hipEventDestroy(tl.start);
-            (void)hipEventDestroy(tl.stop);
-        }
-    if (e->step_open) (void)hipEventDestroy(e->step_start);
-    if (e->span_open) (void)hipEventDestroy(e->span_start);
-    for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
-    for (auto &c : e->chunks) (void)hipFree(c.base);
-    for (int s = 0; s < kSlots; ++s) {
-        if (e->pin[s]) (void)hipHostFree(e->pin[s]);
-        if (e->raw[s]) (void)hipFree(e->raw[s]);
-        if (e->slot_ev[s]) (void)hipEventDestroy(e->slot_ev[s]);
+    if (e->stream) (void)schost::wait_stream(e->stream);  // (before anything is freed)
+    const int device = e->device;
+    const hipStream_t own = e->own_stream;
+    delete e;  // every buffer and event goes with its owner
+    if (own) {
+        (void)schost::wait_stream(own);  // (the engine may have worked on a caller's stream: its own is idle now)
+        give_stream_back(device, own);
     }
-    for (auto &a : e->hb) {
-        if (a.pin) (void)hipHostFree(a.pin);
-        if (a.dev) (void)hipFree(a.dev);
-        if (a.ev) (void)hipEventDestroy(a.ev);
-    }
-    if (e->views_dev) (void)hipFree(e->views_dev);
-    if (e->views_pin) (void)hipHostFree(e->views_pin);
-    if (e->narrow) (void)hipFree(e->narrow);
-    if (e->packed_labels) (void)hipFree(e->packed_labels);
-    for (int q = 0; q < 2; ++q)
-        if (e->sparse_buf[q]) (void)hipFree(e->sparse_buf[q]);
-    for (int q = 0; q < 2; ++q)
-        if (e->sparse_busy[q]) (void)hipEventDestroy(e->sparse_busy[q]);
-    if (e->packed_busy) (void)hipEventDestroy(e->packed_busy);
-    for (int q = 0; q < 2; ++q)
-        if (e->sparse_hdr_pin[q]) (void)hipHostFree(e->sparse_hdr_pin[q]);
-    if (e->sparse_cnt) (void)hipFree(e->sparse_cnt);
-    if (e->sparse_work) (void)hipFree(e->sparse_work);
-    if (e->wire_stage) (void)hipHostFree(e->wire_stage);
-    if (e->dense) (void)hipFree(e->dense);
-    if (e->verd) (void)hipFree(e->verd);
-    if (e->verdf) (void)hipFree(e->verdf);
-    if (e->dead) (void)hipFree(e->dead);
-    if (e->lut_dev) (void)hipFree(e->lut_dev);
-    if (e->lists) (void)hipFree(e->lists);
-    if (e->ctl2[0]) (void)hipFree(e->ctl2[0]);
-    if (e->items) (void)hipFree(e->items);
-    if (e->state) (void)hipFree(e->state);
-    if (e->own_stream) {
-        (void)schost::wait_stream(e->own_stream);  // (the engine may have worked on a caller's stream: its own is idle now)
-        give_stream_back(e->device, e->own_stream);
-    }
-    delete e;
 }
 
 int sc_clear(sc_engine *e) {
@@ -179,10 +139,8 @@ int sc_clear(sc_engine *e) {
     e->dead_clean = false;  // the labels go back to default_value: no brick is known to be all -1
     e->sparse_exact = false;
     arena_reset(e);
-    if (e->step_open) {  // the views of an open SC_KERNEL_STEP window are gone: no sample for them
-        e->event_pool.push_back(e->step_start);
-        e->step_open = false;
-    }
+    // the views of an open SC_KERNEL_STEP window are gone: no sample for them
+    if (e->step_start) e->event_pool.push_back(std::move(e->step_start));
     e->fresh = true;  // materialised lazily: a fused launch never needs to read it
     return SC_OK;
 }
@@ -241,9 +199,9 @@ int sc_set_option(sc_engine *e, int key, int64_t value) {
             int rc = use_device(e);
             if (rc) return rc;
             while ((int64_t)e->event_pool.size() < value) {
-                hipEvent_t ev;
-                HIP_TRY(hipEventCreate(&ev));
-                e->event_pool.push_back(ev);
+                Event ev;
+                HIP_TRY(hipEventCreate(ev.out()));
+                e->event_pool.push_back(std::move(ev));
             }
             return SC_OK;
         }
@@ -330,7 +288,7 @@ int sc_set_lut(sc_engine *e, const float *lut256) {
     rc = flush(e);  // views already enqueued keep the old table
     if (rc) return rc;
     HIP_TRY(schost::wait_stream(e->stream));
-    if (!e->lut_dev) HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->lut_dev), 256 * sizeof(float)));
+    if (!e->lut_dev) HIP_TRY(sc_dev_malloc(e->lut_dev.out(), 256 * sizeof(float)));
     HIP_TRY(hipMemcpy(e->lut_dev, lut256, 256 * sizeof(float), hipMemcpyHostToDevice));
     return SC_OK;
 }
@@ -356,13 +314,7 @@ int sc_order_after(sc_engine *e, void *producer_stream) {
     // torch's bundled one crashed on it)
     hipStream_t prod = static_cast<hipStream_t>(producer_stream);
     if (prod != nullptr && prod == e->stream) return SC_OK;  // same stream: already in order
-    hipEvent_t ev;
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    hipError_t he = hipEventRecord(ev, prod);
-    if (he == hipSuccess) he = hipStreamWaitEvent(e->stream, ev, 0);
-    (void)hipEventDestroy(ev);  // released once the wait has been satisfied
-    if (he != hipSuccess) return fail(SC_ERR_DEVICE, "ordering after the producer stream failed: %s", hipGetErrorString(he));
-    return SC_OK;
+    return order_streams(prod, e->stream, "ordering after the producer stream failed");
 }
 
 int sc_order_before(sc_engine *e, void *consumer_stream) {
@@ -371,13 +323,7 @@ int sc_order_before(sc_engine *e, void *consumer_stream) {
     if (rc) return rc;
     hipStream_t cons = static_cast<hipStream_t>(consumer_stream);
     if (cons != nullptr && cons == e->stream) return SC_OK;  // same stream: already in order
-    hipEvent_t ev;
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    hipError_t he = hipEventRecord(ev, e->stream);
-    if (he == hipSuccess) he = hipStreamWaitEvent(cons, ev, 0);
-    (void)hipEventDestroy(ev);  // released once the wait has been satisfied
-    if (he != hipSuccess) return fail(SC_ERR_DEVICE, "ordering the consumer stream behind the engine failed: %s", hipGetErrorString(he));
-    return SC_OK;
+    return order_streams(e->stream, cons, "ordering the consumer stream behind the engine failed");
 }
 
 int sc_process_view(sc_engine *e, const float K[4], const float R[9], const float t[3],
@@ -409,44 +355,35 @@ int sc_process_view(sc_engine *e, const float K[4], const float R[9], const floa
         HIP_TRY(schost::wait_event(e->slot_ev[s]));
         e->slot_armed[s] = false;
     }
+    void *pin = e->slot[s].pin, *raw = e->slot[s].raw;
     // consume the caller's buffer now (tight rows in the pinned slot)
     if (row_stride_bytes == (int64_t)row) {
-        memcpy(e->pin[s], mask, bytes);
+        memcpy(pin, mask, bytes);
     } else {
         for (int r = 0; r < H; ++r)
-            memcpy(static_cast<char *>(e->pin[s]) + (size_t)r * row,
-                   static_cast<const char *>(mask) + (size_t)r * row_stride_bytes, row);
+            memcpy(static_cast<char *>(pin) + (size_t)r * row, static_cast<const char *>(mask) + (size_t)r * row_stride_bytes, row);
     }
-    if (e->mode == SC_MODE_CARVE) {
-        HIP_TRY(hipMemcpyAsync(e->raw[s], e->pin[s], bytes, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipEventRecord(e->slot_ev[s], e->stream));
-        e->slot_armed[s] = true;
-        rc = enqueue_pack(e, 1, K, R, t, e->raw[s], H, W, mask_dtype, (int64_t)row, (int64_t)bytes);
+    // float32 masks read row-major are not re-laid: the slot's pixels go straight to the arena, where the view reads them
+    const bool plain = e->mode != SC_MODE_CARVE && mask_dtype != SC_MASK_U8_LUT && !e->avg_tile_f32;
+    if (plain) {
+        rc = arena_alloc(e, bytes, &raw);
         if (rc) return rc;
-    } else if (mask_dtype == SC_MASK_U8_LUT) {
-        HIP_TRY(hipMemcpyAsync(e->raw[s], e->pin[s], bytes, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipEventRecord(e->slot_ev[s], e->stream));
-        e->slot_armed[s] = true;
-        rc = enqueue_tile8(e, 1, K, R, t, e->raw[s], H, W, (int64_t)row, (int64_t)bytes);
-        if (rc) return rc;
-    } else if (e->avg_tile_f32) {
-        HIP_TRY(hipMemcpyAsync(e->raw[s], e->pin[s], bytes, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipEventRecord(e->slot_ev[s], e->stream));
-        e->slot_armed[s] = true;
-        rc = enqueue_tilef32(e, 1, K, R, t, e->raw[s], H, W, (int64_t)row, (int64_t)bytes);
-        if (rc) return rc;
-    } else {
-        void *dst = nullptr;
-        rc = arena_alloc(e, bytes, &dst);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(dst, e->pin[s], bytes, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipEventRecord(e->slot_ev[s], e->stream));
-        e->slot_armed[s] = true;
+    }
+    HIP_TRY(hipMemcpyAsync(raw, pin, bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->slot_ev[s], e->stream));
+    e->slot_armed[s] = true;
+    if (plain) {
         ViewDesc d;
-        fill_desc(e, d, K, R, t, dst, H, W);
+        fill_desc(e, d, K, R, t, raw, H, W);
         e->pending.push_back(d);
+    } else if (e->mode == SC_MODE_CARVE) {
+        rc = enqueue_pack(e, 1, K, R, t, raw, H, W, mask_dtype, (int64_t)row, (int64_t)bytes);
+    } else if (mask_dtype == SC_MASK_U8_LUT) {
+        rc = enqueue_tile8(e, 1, K, R, t, raw, H, W, (int64_t)row, (int64_t)bytes);
+    } else {
+        rc = enqueue_tilef32(e, 1, K, R, t, raw, H, W, (int64_t)row, (int64_t)bytes);
     }
-    return after_enqueue(e);
+    return rc ? rc : after_enqueue(e);
 }
 
 int sc_process_views(sc_engine *e, int V, const float *K, const float *R, const float *t,
@@ -604,28 +541,21 @@ int sc_process_views_device(sc_engine *e, int V, const float *K, const float *R,
         }
         // one pack launch for the whole batch, then carve launches per views_per_launch
         rc = enqueue_pack(e, V, K, R, t, masks_dev, H, W, mask_dtype, row, view);
-        if (rc) return rc;
-        return after_enqueue(e);
-    }
-    if (mask_dtype == SC_MASK_U8_LUT) {
+    } else if (mask_dtype == SC_MASK_U8_LUT) {
         rc = enqueue_tile8(e, V, K, R, t, masks_dev, H, W, row, view);
-        if (rc) return rc;
-        return after_enqueue(e);
-    }
-    if (e->avg_tile_f32) {
+    } else if (e->avg_tile_f32) {
         rc = enqueue_tilef32(e, V, K, R, t, masks_dev, H, W, row, view);
-        if (rc) return rc;
-        return after_enqueue(e);
+    } else {
+        for (int q = 0; q < V; ++q) {
+            ViewDesc d;
+            fill_desc(e, d, K + 4 * q, R + 9 * q, t + 3 * q, static_cast<const char *>(masks_dev) + (int64_t)q * view, H, W);
+            e->pending.push_back(d);
+            rc = after_enqueue(e);
+            if (rc) return rc;
+        }
+        return SC_OK;
     }
-    for (int q = 0; q < V; ++q) {
-        ViewDesc d;
-        fill_desc(e, d, K + 4 * q, R + 9 * q, t + 3 * q,
-                  static_cast<const char *>(masks_dev) + (int64_t)q * view, H, W);
-        e->pending.push_back(d);
-        rc = after_enqueue(e);
-        if (rc) return rc;
-    }
-    return SC_OK;
+    return rc ? rc : after_enqueue(e);
 }
 
 int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, const float *R, const float *t,
@@ -679,12 +609,8 @@ int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, c
     // whatever way this function is left they go back to the engines' own (an engine must never keep another's)
     for (int l = 1; l < L; ++l) {
         if (own[(size_t)l] == main) continue;
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t he = hipEventRecord(ev, own[(size_t)l]);
-        if (he == hipSuccess) he = hipStreamWaitEvent(main, ev, 0);
-        (void)hipEventDestroy(ev);
-        if (he != hipSuccess) return fail(SC_ERR_DEVICE, "stream ordering failed: %s", hipGetErrorString(he));
+        rc = order_streams(own[(size_t)l], main, "stream ordering failed");
+        if (rc) return rc;
     }
     struct StreamGuard {
         sc_engine *const *eng;
@@ -708,7 +634,7 @@ int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, c
         if (rc) break;
         if (hipMemcpyAsync(const_cast<ViewDesc *>(vd[l < 64 ? l : 0]), pin, (size_t)V * sizeof(ViewDesc), hipMemcpyHostToDevice, main) !=
             hipSuccess) { rc = fail(SC_ERR_DEVICE, "descriptor copy failed"); break; }
-        rc = grow_buffer(e, reinterpret_cast<void **>(&e->verd), &e->verd_cap, need, 1);
+        rc = grow_verdicts(e, need, false);
         if (rc) break;
     }
     if (rc == SC_OK && L > 64) rc = fail(SC_ERR_INVALID, "more than 64 labels");
@@ -722,7 +648,7 @@ int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, c
         memset(&a, 0, sizeof a);
         for (int q = 0; q < n; ++q) {
             sc_engine *e = engines[l0 + q];
-            a.values[q] = static_cast<float *>(e->state);
+            a.values[q] = static_cast<float *>(e->state.get());
             a.views[q] = vd[l0 + q];
             a.verd[q] = e->verd;
             a.lut[q] = e->lut_dev;
@@ -747,12 +673,11 @@ int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, c
     if (rc == SC_OK && hipGetLastError() != hipSuccess) rc = fail(SC_ERR_DEVICE, "multi-label launch failed");
     // the other engines' own streams wait for the first one's
     if (rc == SC_OK) {
-        hipEvent_t ev;
-        hipError_t he = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        Event ev;  // (released once the waits have been satisfied)
+        hipError_t he = hipEventCreateWithFlags(ev.out(), hipEventDisableTiming);
         if (he == hipSuccess) he = hipEventRecord(ev, main);
         for (int l = 1; l < L && he == hipSuccess; ++l)
             if (own[(size_t)l] != main) he = hipStreamWaitEvent(own[(size_t)l], ev, 0);
-        if (he == hipSuccess) (void)hipEventDestroy(ev);
         if (he != hipSuccess) rc = fail(SC_ERR_DEVICE, "stream ordering failed: %s", hipGetErrorString(he));
     }
     for (int l = 0; l < L; ++l) {

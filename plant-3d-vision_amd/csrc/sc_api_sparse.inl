@@ -75,22 +75,20 @@ int values_sparse(sc_engine *e, int64_t cap, int64_t min_bytes, void **ptr, int6
     const SparseLayout lay = sparse_layout(nbricks, capb);
     const int q = e->sparse_idx;
     const size_t need = std::max<size_t>(lay.total, (size_t)std::max<int64_t>(min_bytes, 0));
-    if (e->sparse_bytes[q] < need) {
-        // (the other buffer may still be read by a collective; this one was last read two calls ago, and the caller has
-        // ordered that collective before this call: sc_all_gather_sparse, sc_order_after)
-        HIP_TRY(schost::wait_stream(e->stream));
-        if (e->sparse_buf[q]) (void)hipFree(e->sparse_buf[q]);
-        e->sparse_buf[q] = nullptr;
-        e->sparse_bytes[q] = 0;
-        HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->sparse_buf[q]), need));
-        e->sparse_bytes[q] = need;
-        // what the pack kernel does not write (the padding of the codes, slots nobody took) travels too: zeroes the first
-        // time (later: whatever an earlier call with another capacity left there; a reader goes by the header)
-        HIP_TRY(hipMemsetAsync(e->sparse_buf[q], 0, need, e->stream));
-    }
+    // (the other buffer may still be read by a collective; this one was last read two calls ago, and the caller has
+    // ordered that collective before this call: sc_all_gather_sparse, sc_order_after)
+    // what the pack kernel does not write (the padding of the codes, slots nobody took) travels too: zeroes the first
+    // time (later: whatever an earlier call with another capacity left there; a reader goes by the header)
+    auto zeroed = [&] {
+        const hipError_t he = sc_dev_malloc(e->sparse_buf[q].out(), need);
+        return he != hipSuccess ? he : hipMemsetAsync(e->sparse_buf[q], 0, need, e->stream);
+    };
+    HIP_TRY(scown::grow(e->sparse_bytes[q], need, stream_idle(e), zeroed, e->sparse_buf[q]));
     if (!e->sparse_cnt) {
-        HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->sparse_cnt), 2 * sizeof(SparseCounters)));
-        HIP_TRY(hipMemsetAsync(e->sparse_cnt, 0, 2 * sizeof(SparseCounters), e->stream));
+        DevPtr<SparseCounters> cnt;
+        HIP_TRY(sc_dev_malloc(cnt.out(), 2 * sizeof(SparseCounters)));
+        HIP_TRY(hipMemsetAsync(cnt, 0, 2 * sizeof(SparseCounters), e->stream));
+        e->sparse_cnt = std::move(cnt);
     }
     char *wire = e->sparse_buf[q];
     SparseCounters *cnt = e->sparse_cnt + (e->sparse_calls & 1u), *cnt_next = e->sparse_cnt + ((e->sparse_calls + 1) & 1u);
@@ -111,7 +109,7 @@ int values_sparse(sc_engine *e, int64_t cap, int64_t min_bytes, void **ptr, int6
     const GridDesc g = grid_desc(e);
     const uint32_t nscan = (nbricks + kBlock - 1) / kBlock;
     const uint32_t code_full = (uint32_t)(init == 0 ? 1 : init) & 3u, code_untouched = (uint32_t)init & 3u;
-    const int32_t *st = static_cast<const int32_t *>(e->state);
+    const int32_t *st = static_cast<const int32_t *>(e->state.get());
     const bool exact = e->sparse_exact && e->flags != nullptr && e->ctl != nullptr && e->live != nullptr;
     if (exact) {
         // ONE launch: the verdict bytes of the batch that made these labels settle most bricks, its live list (and the
@@ -136,9 +134,9 @@ int values_sparse(sc_engine *e, int64_t cap, int64_t min_bytes, void **ptr, int6
     } else {
         // the labels' history is not one fused batch: bricks an earlier launch found empty are all -1 until the next
         // clear (the dead bytes), every other brick is read
-        if (!e->sparse_work) HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->sparse_work), (size_t)nbricks * 4));
+        if (!e->sparse_work) HIP_TRY(sc_dev_malloc(e->sparse_work.out(), (size_t)nbricks * 4));
         const bool dead = e->dead != nullptr && e->dead_clean;
-        SparseScan sc{dead ? e->dead : nullptr, nbricks, dead ? 1 : 0, code_full, code_untouched, e->sparse_work};
+        SparseScan sc{dead ? e->dead.get() : nullptr, nbricks, dead ? 1 : 0, code_full, code_untouched, e->sparse_work};
         SparseLists none{};
         hipLaunchKernelGGL(sparse_pack_kernel, dim3(nscan), dim3(kBlock), 0, e->stream, st, g, bys, bzs, sc, nscan, none,
                            wire, hdr, cnt, static_cast<SparseCounters *>(nullptr));

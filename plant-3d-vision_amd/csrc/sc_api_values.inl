@@ -40,16 +40,16 @@ int sc_get_values_i8(sc_engine *e, int8_t *out) {
     if (rc) return rc;
     rc = materialize(e);
     if (rc) return rc;
-    if (!e->narrow) HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->narrow), (size_t)e->n));
+    if (!e->narrow) HIP_TRY(sc_dev_malloc(e->narrow.out(), (size_t)e->n));
     const uint64_t n = (uint64_t)e->n;
     const uint64_t blocks = (n + (uint64_t)kBlock * 16 - 1) / ((uint64_t)kBlock * 16);
     if (e->nzp == e->nz) {
         hipLaunchKernelGGL(narrow_i8_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, e->stream,
-                           static_cast<const int32_t *>(e->state), e->narrow, n);
+                           static_cast<const int32_t *>(e->state.get()), e->narrow, n);
     } else {  // rows without their padding, narrowed on the way
         const uint64_t rows = (uint64_t)e->planes * (uint64_t)e->ny;
         hipLaunchKernelGGL(depitch_kernel<int8_t>, dim3((uint32_t)std::min<uint64_t>((rows + 3) / 4, 65536)), dim3(kBlock), 0,
-                           e->stream, static_cast<const uint32_t *>(e->state), e->narrow, rows, (uint32_t)e->nz,
+                           e->stream, static_cast<const uint32_t *>(e->state.get()), e->narrow, rows, (uint32_t)e->nz,
                            (uint32_t)e->nzp);
     }
     HIP_TRY(hipGetLastError());
@@ -89,23 +89,25 @@ int sc_values_packed(sc_engine *e, int bits, void **ptr, int64_t *bytes) {
         // room for one more plane than the engine owns: in an all-gather every rank sends the stride of the rank with
         // the most planes (sc_all_gather_packed)
         const size_t cap = (size_t)sc_packed_bytes(e->n + e->ny * e->nz, 2), own = (size_t)sc_packed_bytes(e->n, 2);
-        HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->packed_labels), cap));
+        DevPtr<uint32_t> labels;
+        HIP_TRY(sc_dev_malloc(labels.out(), cap));
         // the tail of the last 16-byte group lies behind the last word the pack kernel writes and travels with the
         // buffer (all-gather, read-back), and so does the slack: zero once, never garbage
-        HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(e->packed_labels) + (own - 16), 0, cap - (own - 16), e->stream));
+        HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(labels.get()) + (own - 16), 0, cap - (own - 16), e->stream));
+        e->packed_labels = std::move(labels);
         e->packed_cap = cap;
     }
     const uint64_t words = ((uint64_t)e->n + (32 / bits) - 1) / (32 / bits);
     // bricks an earlier launch found empty are all -1 until the next clear: not read (see the kernel)
     const uint32_t bys = (uint32_t)((e->ny + kBrickY - 1) / kBrickY), bzs = (uint32_t)((e->nz + kBrickZ - 1) / kBrickZ);
-    const uint8_t *dead = (e->dead && e->dead_clean) ? e->dead : nullptr;
+    const uint8_t *dead = (e->dead && e->dead_clean) ? e->dead.get() : nullptr;
     const dim3 grid((uint32_t)((words + kBlock - 1) / kBlock));
     if ((uint64_t)grid.x * kBlock < words) return fail(SC_ERR_INVALID, "grid too large for one launch");
     if (bits == 2)
-        hipLaunchKernelGGL(pack_labels_kernel<2>, grid, dim3(kBlock), 0, e->stream, static_cast<const int32_t *>(e->state),
+        hipLaunchKernelGGL(pack_labels_kernel<2>, grid, dim3(kBlock), 0, e->stream, static_cast<const int32_t *>(e->state.get()),
                            e->packed_labels, (uint64_t)e->n, (uint32_t)e->nz, (uint32_t)e->nzp, (uint32_t)e->ny, dead, bys, bzs);
     else
-        hipLaunchKernelGGL(pack_labels_kernel<1>, grid, dim3(kBlock), 0, e->stream, static_cast<const int32_t *>(e->state),
+        hipLaunchKernelGGL(pack_labels_kernel<1>, grid, dim3(kBlock), 0, e->stream, static_cast<const int32_t *>(e->state.get()),
                            e->packed_labels, (uint64_t)e->n, (uint32_t)e->nz, (uint32_t)e->nzp, (uint32_t)e->ny, dead, bys, bzs);
     HIP_TRY(hipGetLastError());
     // (the tail of the last 16-byte group is never read by a consumer that knows the voxel count)
@@ -186,25 +188,21 @@ int sc_get_values_wire2(sc_engine *e, int32_t *out, void *staging, int64_t stagi
     int rc = sc_values_packed(e, 2, &ptr, &bytes);
     if (rc) return rc;
     const int64_t n = e->n, words = (n + 15) / 16;
-    if (e->wire_stage_words < (size_t)words) {
-        if (e->wire_stage) (void)hipHostFree(e->wire_stage);
-        e->wire_stage = nullptr;
-        e->wire_stage_words = 0;
-        HIP_TRY(sc_pin_malloc(reinterpret_cast<void **>(&e->wire_stage), (size_t)words * 4, hipHostMallocDefault));
-        e->wire_stage_words = (size_t)words;
-    }
+    // (nothing to wait for: every call waits for its copies out of the staging buffer before it returns)
+    HIP_TRY(scown::grow(e->wire_stage_words, (size_t)words, [] { return hipSuccess; },
+                        [&] { return sc_pin_malloc(e->wire_stage.out(), (size_t)words * 4, hipHostMallocDefault); }, e->wire_stage));
     // Pieces of 1 MiB of packed labels (16 MiB of int32): every copy is put on the stream at once, an event behind
     // each; this thread waits for the events in turn and hands each landed piece to the host pool, whose workers
     // widen it while the next ones are on their way.  Nobody spins.
     const int64_t piece = (int64_t)1 << 18;  // words
     const int64_t npieces = (words + piece - 1) / piece;
     uint32_t *stg = e->wire_stage;
-    std::vector<hipEvent_t> evs((size_t)npieces, nullptr);
+    std::vector<Event> evs((size_t)npieces);
     hipError_t err = hipSuccess;
     int64_t queued = 0;
     for (int64_t k = 0; k < npieces && err == hipSuccess; ++k) {
         const int64_t w0 = k * piece, w1 = std::min(words, (k + 1) * piece);
-        if (get_event(e, &evs[(size_t)k]) != SC_OK) { err = hipErrorOutOfMemory; break; }
+        if (get_event(e, evs[(size_t)k]) != SC_OK) { err = hipErrorOutOfMemory; break; }
         ++queued;
         err = hipMemcpyAsync(stg + w0, static_cast<const uint32_t *>(ptr) + w0, (size_t)(w1 - w0) * 4, hipMemcpyDeviceToHost, e->stream);
         if (err == hipSuccess) err = hipEventRecord(evs[(size_t)k], e->stream);
@@ -223,7 +221,7 @@ int sc_get_values_wire2(sc_engine *e, int32_t *out, void *staging, int64_t stagi
         tg.wait();
     }
     (void)schost::wait_stream(e->stream);  // (every copy has landed or failed before the events go back)
-    for (int64_t k = 0; k < queued; ++k) e->event_pool.push_back(evs[(size_t)k]);
+    for (int64_t k = 0; k < queued; ++k) e->event_pool.push_back(std::move(evs[(size_t)k]));
     if (err != hipSuccess) return fail(SC_ERR_DEVICE, "label read-back failed: %s", hipGetErrorString(err));
     return SC_OK;
 }
@@ -295,8 +293,8 @@ int sc_reset_kernel_stats(sc_engine *e) {
     HIP_TRY(schost::wait_stream(e->stream));
     for (int k = 0; k < kNumKernels; ++k) {
         for (auto &tl : e->timed[k]) {
-            e->event_pool.push_back(tl.start);
-            e->event_pool.push_back(tl.stop);
+            e->event_pool.push_back(std::move(tl.start));
+            e->event_pool.push_back(std::move(tl.stop));
         }
         e->timed[k].clear();
     }
@@ -307,15 +305,15 @@ int sc_span_begin(sc_engine *e) {
     if (!e) return fail(SC_ERR_INVALID, "null engine");
     int rc = use_device(e);
     if (rc) return rc;
-    if (e->span_open) return fail(SC_ERR_STATE, "a span is open already");
-    rc = get_event(e, &e->span_start);
+    if (e->span_start) return fail(SC_ERR_STATE, "a span is open already");
+    Event start, stop;
+    rc = get_event(e, start);
     if (rc) return rc;
-    hipEvent_t stop;
-    rc = get_event(e, &stop);  // the second event exists before the span starts
+    rc = get_event(e, stop);  // the second event exists before the span starts
     if (rc) return rc;
-    e->event_pool.push_back(stop);
-    HIP_TRY(hipEventRecord(e->span_start, e->stream));
-    e->span_open = true;
+    e->event_pool.push_back(std::move(stop));
+    HIP_TRY(hipEventRecord(start, e->stream));
+    e->span_start = std::move(start);
     return SC_OK;
 }
 
@@ -323,18 +321,17 @@ int sc_span_end(sc_engine *e, double *ms) {
     if (!e || !ms) return fail(SC_ERR_INVALID, "null argument");
     int rc = use_device(e);
     if (rc) return rc;
-    if (!e->span_open) return fail(SC_ERR_STATE, "no span is open");
-    hipEvent_t stop;
-    rc = get_event(e, &stop);
+    if (!e->span_start) return fail(SC_ERR_STATE, "no span is open");
+    Event stop;
+    rc = get_event(e, stop);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(stop, e->stream));
     HIP_TRY(schost::wait_event(stop));
     float f = 0.0f;
     HIP_TRY(hipEventElapsedTime(&f, e->span_start, stop));
     *ms = (double)f;
-    e->event_pool.push_back(e->span_start);
-    e->event_pool.push_back(stop);
-    e->span_open = false;
+    e->event_pool.push_back(std::move(e->span_start));
+    e->event_pool.push_back(std::move(stop));
     return SC_OK;
 }
 
@@ -402,15 +399,15 @@ int sc_selftest_division(sc_engine *e, int64_t count, uint32_t seed, int mode,
     if (!e || !mismatches || !fast_pairs || count < 0) return fail(SC_ERR_INVALID, "bad argument");
     int rc = use_device(e);
     if (rc) return rc;
-    unsigned long long *out = nullptr, host[2] = {0, 0};
-    HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&out), sizeof host));
+    unsigned long long host[2] = {0, 0};
+    DevPtr<unsigned long long> out;
+    HIP_TRY(sc_dev_malloc(out.out(), sizeof host));
     HIP_TRY(hipMemsetAsync(out, 0, sizeof host, e->stream));
     hipLaunchKernelGGL(div_selftest_kernel, dim3(4096), dim3(kBlock), 0, e->stream, (uint64_t)count,
-                       seed, mode, out);
+                       seed, mode, out.get());
     hipError_t he = hipGetLastError();
     if (he == hipSuccess) he = hipMemcpyAsync(host, out, sizeof host, hipMemcpyDeviceToHost, e->stream);
     if (he == hipSuccess) he = schost::wait_stream(e->stream);
-    (void)hipFree(out);
     if (he != hipSuccess) return fail(SC_ERR_DEVICE, "division self-test failed: %s", hipGetErrorString(he));
     *mismatches = host[0];
     *fast_pairs = host[1];
@@ -457,38 +454,37 @@ int sc_selftest_project(sc_engine *e, int64_t count, uint32_t seed, int nposes, 
     }
     poses = reinterpret_cast<const float *>(cert.data());
     const size_t ndig = (size_t)((count + 65535) >> 16);
-    PoseRec *dp = nullptr;
-    int32_t *dijk = nullptr, *didx = nullptr;
-    uint32_t *dw = nullptr;
-    unsigned long long *dd = nullptr;
-    hipError_t he = sc_dev_malloc(reinterpret_cast<void **>(&dp), (size_t)nposes * sizeof(PoseRec));
+    DevPtr<unsigned long long> dd;  // (freed at the return, last one first)
+    DevPtr<uint32_t> dw;
+    DevPtr<int32_t> didx, dijk;
+    DevPtr<PoseRec> dp;
+    hipError_t he = sc_dev_malloc(dp.out(), (size_t)nposes * sizeof(PoseRec));
     if (he == hipSuccess) he = hipMemcpy(dp, poses, (size_t)nposes * sizeof(PoseRec), hipMemcpyHostToDevice);
     if (he == hipSuccess && ijk) {
-        he = sc_dev_malloc(reinterpret_cast<void **>(&dijk), (size_t)count * 12);
+        he = sc_dev_malloc(dijk.out(), (size_t)count * 12);
         if (he == hipSuccess) he = hipMemcpy(dijk, ijk, (size_t)count * 12, hipMemcpyHostToDevice);
     }
     if (he == hipSuccess && pose_idx) {
-        he = sc_dev_malloc(reinterpret_cast<void **>(&didx), (size_t)count * 4);
+        he = sc_dev_malloc(didx.out(), (size_t)count * 4);
         if (he == hipSuccess) he = hipMemcpy(didx, pose_idx, (size_t)count * 4, hipMemcpyHostToDevice);
     }
-    if (he == hipSuccess && words_out) he = sc_dev_malloc(reinterpret_cast<void **>(&dw), (size_t)count * 4);
+    if (he == hipSuccess && words_out) he = sc_dev_malloc(dw.out(), (size_t)count * 4);
     if (he == hipSuccess && digests_out) {
-        he = sc_dev_malloc(reinterpret_cast<void **>(&dd), ndig * 8);
+        he = sc_dev_malloc(dd.out(), ndig * 8);
         if (he == hipSuccess) he = hipMemsetAsync(dd, 0, ndig * 8, e->stream);
     }
     if (he == hipSuccess) {
         const uint64_t nwaves = ((uint64_t)count + 63) >> 6;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((nwaves + 3) / 4, 16384);
         hipLaunchKernelGGL(project_selftest_kernel, dim3(blocks), dim3(kBlock), 0, e->stream, (uint64_t)count,
-                           seed, (uint32_t)nposes, dp, dijk, didx, dw, dd);
+                           seed, (uint32_t)nposes, dp.get(), dijk.get(), didx.get(), dw.get(), dd.get());
         he = hipGetLastError();
     }
     if (he == hipSuccess) he = schost::wait_stream(e->stream);
     if (he == hipSuccess && words_out) he = hipMemcpy(words_out, dw, (size_t)count * 4, hipMemcpyDeviceToHost);
     if (he == hipSuccess && digests_out) he = hipMemcpy(digests_out, dd, ndig * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(dp); (void)hipFree(dijk); (void)hipFree(didx); (void)hipFree(dw); (void)hipFree(dd);
     if (he != hipSuccess) return fail(SC_ERR_DEVICE, "projection self-test failed: %s", hipGetErrorString(he));
-    return SC_OK;
+    return SC_OK;  // (the five buffers go with their owners)
 }
 
 int sc_host_alloc(int device, int64_t bytes, void **ptr) {

@@ -70,8 +70,8 @@ struct sc_comm {
     void *comm = nullptr;
     int nranks = 0, rank = 0, device = 0;
     hipStream_t stream = nullptr;  // collectives that run beside the engine's stream
-    hipEvent_t ev_ready = nullptr; // the engine's pack has been enqueued: the collective waits for it
-    char *scratch = nullptr;       // (nranks + 1) x 16 bytes: sc_comm_barrier's all-gather
+    DevPtr<char> scratch;          // (nranks + 1) x 16 bytes: sc_comm_barrier's all-gather
+    Event ev_ready;                // the engine's pack has been enqueued: the collective waits for it
 };
 
 extern "C" {
@@ -107,15 +107,13 @@ int sc_comm_create(sc_comm **out, const void *id, int nranks, int rank, int devi
         return fail(SC_ERR_DEVICE, "ncclCommInitRank failed: %s", rccl().get_error_string(r));
     }
     hipError_t he = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming);
-    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void **>(&c->scratch), (size_t)(nranks + 1) * 16);
+    if (he == hipSuccess) he = hipEventCreateWithFlags(c->ev_ready.out(), hipEventDisableTiming);
+    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void **>(c->scratch.out()), (size_t)(nranks + 1) * 16);
     if (he == hipSuccess) he = hipMemset(c->scratch, 0, (size_t)(nranks + 1) * 16);
     if (he != hipSuccess) {
-        if (c->scratch) (void)hipFree(c->scratch);
-        if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
         if (c->stream) (void)hipStreamDestroy(c->stream);
         (void)rccl().comm_destroy(c->comm);
-        delete c;
+        delete c;  // (with the event and the scratch buffer, if they exist)
         return fail(SC_ERR_DEVICE, "communicator stream: %s", hipGetErrorString(he));
     }
     *out = c;
@@ -127,10 +125,9 @@ void sc_comm_destroy(sc_comm *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)schost::wait_stream(c->stream);
     if (c->comm) (void)rccl().comm_destroy(c->comm);
-    if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    const hipStream_t stream = c->stream;
+    delete c;  // the event, then the scratch buffer (members go last one first)
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 int sc_comm_size(const sc_comm *c) { return c ? c->nranks : 0; }
@@ -180,7 +177,7 @@ int sc_engine_stream(sc_engine *e, void **hip_stream) {
 constexpr int kMaxHeaderRanks = 256;
 
 static int gather_behind_pack(sc_engine *e, sc_comm *c, const void *send, void *recv_dev, int64_t bytes, int overlap,
-                              hipEvent_t *busy, SparseHeader *hdr_pin = nullptr) {
+                              Event &busy, SparseHeader *hdr_pin = nullptr) {
     if (overlap) {
         HIP_TRY(hipEventRecord(c->ev_ready, e->stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_ready, 0));
@@ -194,8 +191,8 @@ static int gather_behind_pack(sc_engine *e, sc_comm *c, const void *send, void *
     // an event behind the collective (and that copy), whichever stream it is on: what a reader of the receive buffer
     // waits for without queueing behind the NEXT batch's collective, and -- overlap -- what the engine's next pack into
     // this send buffer waits for
-    if (!*busy) HIP_TRY(hipEventCreateWithFlags(busy, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(*busy, st));
+    if (!busy) HIP_TRY(hipEventCreateWithFlags(busy.out(), hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(busy, st));
     return SC_OK;
 }
 
@@ -221,12 +218,12 @@ int sc_all_gather_sparse(sc_engine *e, sc_comm *c, int64_t cap, void *recv_dev, 
     if (rank_stride < bytes)
         return fail(SC_ERR_INVALID, "rank stride of %lld bytes for a buffer of %lld", (long long)rank_stride, (long long)bytes);
     if (!e->sparse_hdr_pin[q])
-        HIP_TRY(sc_pin_malloc(reinterpret_cast<void **>(&e->sparse_hdr_pin[q]), kMaxHeaderRanks * sizeof(SparseHeader), hipHostMallocDefault));
-    rc = gather_behind_pack(e, c, ptr, recv_dev, rank_stride, overlap, &e->sparse_busy[q], e->sparse_hdr_pin[q]);
+        HIP_TRY(sc_pin_malloc(e->sparse_hdr_pin[q].out(), kMaxHeaderRanks * sizeof(SparseHeader), hipHostMallocDefault));
+    rc = gather_behind_pack(e, c, ptr, recv_dev, rank_stride, overlap, e->sparse_busy[q], e->sparse_hdr_pin[q]);
     if (rc) return rc;
     e->sparse_busy_armed[q] = overlap != 0;
-    if (done_event) *done_event = e->sparse_busy[q];
-    if (headers_host) *headers_host = c->nranks <= kMaxHeaderRanks ? e->sparse_hdr_pin[q] : nullptr;
+    if (done_event) *done_event = e->sparse_busy[q].get();
+    if (headers_host) *headers_host = c->nranks <= kMaxHeaderRanks ? e->sparse_hdr_pin[q].get() : nullptr;
     return SC_OK;
 }
 
@@ -262,7 +259,7 @@ int sc_all_gather_packed(sc_engine *e, sc_comm *c, int bits, void *recv_dev, int
     if (rc) return rc;
     if (rank_stride < bytes || (size_t)rank_stride > e->packed_cap)
         return fail(SC_ERR_INVALID, "rank stride of %lld bytes for a buffer of %lld (at most one plane more)", (long long)rank_stride, (long long)bytes);
-    rc = gather_behind_pack(e, c, ptr, recv_dev, rank_stride, overlap, &e->packed_busy);
+    rc = gather_behind_pack(e, c, ptr, recv_dev, rank_stride, overlap, e->packed_busy);
     if (rc) return rc;
     e->packed_busy_armed = overlap != 0;
     return SC_OK;

@@ -2,18 +2,21 @@
 // every entry point shares (events and timers, the grid descriptor, staging slots and arenas, mask packing jobs, survivor
 // lists and control blocks, host-packed bits).  The launches are in sc_flush.inl, the C ABI in sc_api_*.inl.
 
+// Ownership: every allocation and every event of the engine is held by an owner (sc_own.h), so `delete e` gives back
+// all of it and a new buffer is one declaration.  Pointers INTO another allocation (the views into the control block)
+// and the streams stay raw.  A resource appears in the engine only when every step that prepares it has succeeded.
 struct sc_engine {
     int device = 0;
     int mode = SC_MODE_CARVE;
     int64_t nx = 0, ny = 0, nz = 0, i0 = 0, istride = 1, planes = 0, n = 0;
     int64_t nzp = 0;     // row pitch of the state in voxels (nz rounded up to a multiple of 64)
     int64_t npitch = 0;  // planes * ny * nzp: elements of the state as it lies in memory
-    void *dense = nullptr;  // planes * ny * nz elements: the state without the row padding, made on demand
+    DevPtr<void> dense;     // planes * ny * nz elements: the state without the row padding, made on demand
                             // for read-backs and device consumers when nzp != nz
     float origin[3] = {0, 0, 0};
     float vs = 1.0f;
     float default_value = 0.0f;
-    void *state = nullptr;
+    DevPtr<void> state;
     bool fresh = true;
 
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -29,8 +32,8 @@ struct sc_engine {
 
     // deferred views
     std::vector<ViewDesc> pending;
-    ViewDesc *views_dev = nullptr;  // ring of descriptors, consumed in stream order
-    ViewDesc *views_pin = nullptr;
+    DevPtr<ViewDesc> views_dev;  // ring of descriptors, consumed in stream order
+    PinPtr<ViewDesc> views_pin;
     size_t views_cap = 0, views_head = 0;
 
     // mask storage for pending views
@@ -38,35 +41,36 @@ struct sc_engine {
 
     uint8_t *flags = nullptr;  // fused carve, brick form: one emptiness verdict per brick (inside ctl's allocation)
     uint32_t *live = nullptr;  // ... and the bricks no view found empty (count in ctl->nlive)
+    DevPtr<char> ctl_base;                  // the control block: the counter blocks, then what flags .. bulk point at
     ListCtl *ctl2[2] = {nullptr, nullptr};  // counter blocks of alternate batches (ctl points at the current one)
     bool ctl_clean[2] = {false, false};     // known to be all zero
     int ctl_idx = 0;
     int64_t full_bricks = 1;      // bricks every view sees whole over foreground get their label without projections
     int64_t avg_brick = 1;        // averaging: brick form with uniform-footprint verdicts
     int64_t avg_tile_f32 = 1;     // averaging: float32 masks are re-laid in 8x4-pixel tiles (0: read row-major)
-    uint8_t *verd = nullptr;      // ... its [bricks][views] verdicts
+    DevPtr<uint8_t> verd;         // ... its [bricks][views] verdicts
     size_t verd_cap = 0;
-    uint32_t *verdf = nullptr;    // ... and, for tiled float32 masks, the value a flat footprint adds
+    DevPtr<uint32_t> verdf;       // ... and, for tiled float32 masks, the value a flat footprint adds
     size_t verdf_cap = 0;
     int64_t pack_rows = 0;     // 0: the band form of the 16-byte pack kernel; 1, 2, 4, 8: the panel form, tile rows per block
     int64_t view_brick = 1;    // a single-view carve launch goes through the brick kernels too (0: streaming kernel)
     int64_t pack_reach = 1;    // a batch packed at its flush packs only the tiles its voxels can reach (0: whole pictures)
     int64_t pack_cnt[4] = {0, 0, 0, 0};  // sc_pack_counts of the last flushed batch ([2] on the device when riders packed)
     bool pack_cnt_riders = false;
-    uint8_t *dead = nullptr;   // per brick: an earlier launch found it empty, every voxel is -1 (until the next clear)
+    DevPtr<uint8_t> dead;      // per brick: an earlier launch found it empty, every voxel is -1 (until the next clear)
     bool dead_clean = false;   // `dead` describes the labels (false after a clear: the next flags kernel rewrites it)
     int64_t pack_ride = 1;     // a device batch is packed at flush, in view order: the first views ahead of
                                // the flags kernel, the others beside the dense stage (0: all ahead)
-    int8_t *narrow = nullptr;  // scratch of sc_get_values_i8
-    uint32_t *packed_labels = nullptr;  // sc_values_packed: the labels at 2 or 1 bits each
-    uint32_t *wire_stage = nullptr;     // sc_get_values_wire2: page-locked landing place of the packed labels
+    DevPtr<int8_t> narrow;     // scratch of sc_get_values_i8
+    DevPtr<uint32_t> packed_labels;     // sc_values_packed: the labels at 2 or 1 bits each
+    PinPtr<uint32_t> wire_stage;        // sc_get_values_wire2: page-locked landing place of the packed labels
     // sc_values_sparse (sc_sparse.h): two send buffers alternate, so that a collective may still read one while the next
     // batch's labels are packed into the other
-    char *sparse_buf[2] = {nullptr, nullptr};
+    DevPtr<char> sparse_buf[2];
     size_t sparse_bytes[2] = {0, 0};
     int sparse_idx = 0;
-    SparseCounters *sparse_cnt = nullptr;  // two, alternating (the pack kernel of a call zeroes the other call's)
-    uint32_t *sparse_work = nullptr;       // bricks whose labels have to be read when no list of them exists
+    DevPtr<SparseCounters> sparse_cnt;     // two, alternating (the pack kernel of a call zeroes the other call's)
+    DevPtr<uint32_t> sparse_work;          // bricks whose labels have to be read when no list of them exists
     uint64_t sparse_calls = 0;
     int64_t sparse_cap = 0;                // payload capacity (bricks) of the next call that does not name one
     bool sparse_exact = false;             // the verdict bytes and the live / late lists describe the labels exactly: the
@@ -74,12 +78,12 @@ struct sc_engine {
     bool sparse_late = false;              // ... and its late lists hold its failed candidates (verdict byte 5)
     // a collective enqueued beside the engine's stream (sc_all_gather_*, overlap) still reads a send buffer: the next
     // pack into that buffer waits for the event recorded behind the collective
-    hipEvent_t sparse_busy[2] = {nullptr, nullptr}, packed_busy = nullptr;
+    Event sparse_busy[2], packed_busy;
     bool sparse_busy_armed[2] = {false, false}, packed_busy_armed = false;
     size_t packed_cap = 0;                 // bytes of packed_labels
     // sc_all_gather_sparse: the ranks' headers of a gather land here (page-locked), copied behind the collective on its
     // stream: a reader waits for the gather's event and reads host memory (sc_sparse_wait_headers)
-    SparseHeader *sparse_hdr_pin[2] = {nullptr, nullptr};
+    PinPtr<SparseHeader> sparse_hdr_pin[2];
     size_t wire_stage_words = 0;
     int64_t unit_cull = 1;     // the dense stage asks the views packed ahead about every live brick's units (0: not;
                                // 2: even when the tiles settled less than half of the bricks)
@@ -88,7 +92,7 @@ struct sc_engine {
     uint32_t bulkcap = 0;      // ... per sub-list
     int64_t bulk_min = 128;    // voxels of a unit (of 256) alive after the dense views for it to go there (0: never)
     bool last_bulk = false;    // the last fused launch had a bulk list
-    uint4 *items = nullptr;    // the bulk units' work items (counts in ctl->count[4])
+    DevPtr<uint4> items;       // the bulk units' work items (counts in ctl->count[4])
     uint32_t itemcap = 0;      // ... per sub-list
     // Whether the bulk units' verdicts pay is decided on the device, inside the batch, from the number of units its
     // own dense stage left (carve_special_kernel): fewer than this and their voxels take the ordinary lists
@@ -105,10 +109,10 @@ struct sc_engine {
         int64_t row_stride = 0, view_stride = 0;
     } deferred;
     int64_t flag_views = 8;    // views that may veto a brick (0 = all of the batch)
-    float *lut_dev = nullptr;  // averaging: 256-entry byte -> float32 table (SC_MASK_U8_LUT)
+    DevPtr<float> lut_dev;     // averaging: 256-entry byte -> float32 table (SC_MASK_U8_LUT)
 
     // survivor lists of the fused carve
-    uint32_t *lists = nullptr;  // 2 x (kSub * subcap) entries
+    DevPtr<uint32_t> lists;     // 2 x (kSub * subcap) entries
     ListCtl *ctl = nullptr;
     uint32_t subcap = 0;
 
@@ -118,18 +122,22 @@ struct sc_engine {
     int64_t safe_kernels = 1;  // batches whose views are all certified take the list kernels compiled without the general path
     int64_t host_pack = 1;
     struct HostBits {
-        char *pin = nullptr, *dev = nullptr;
+        PinPtr<char> pin;
+        DevPtr<char> dev;
         size_t cap = 0, used = 0;
-        hipEvent_t ev = nullptr;  // the last copy out of `pin` has completed
+        Event ev;  // the last copy out of `pin` has completed
         bool armed = false;
     } hb[2];
     int hb_cur = 0;
     std::vector<BitsRec> hp_pending;  // host-packed views not uploaded yet (all of them are among `pending`)
 
     // host-mask staging ring
-    void *pin[kSlots] = {nullptr, nullptr, nullptr, nullptr};
-    void *raw[kSlots] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t slot_ev[kSlots] = {nullptr, nullptr, nullptr, nullptr};
+    struct Slot {
+        PinPtr<void> pin;
+        DevPtr<void> raw;
+        void reset() { pin.reset(), raw.reset(); }
+    } slot[kSlots];
+    Event slot_ev[kSlots];
     bool slot_armed[kSlots] = {false, false, false, false};
     size_t slot_bytes = 0;
     int next_slot = 0;
@@ -145,11 +153,9 @@ struct sc_engine {
     int64_t stage1_views = 6;    // views applied to the first survivor list (8 until round 5)
 
     std::vector<TimedLaunch> timed[kNumKernels];
-    hipEvent_t step_start = nullptr;
-    bool step_open = false;
-    hipEvent_t span_start = nullptr;  // sc_span_begin .. sc_span_end
-    bool span_open = false;
-    std::vector<hipEvent_t> event_pool;
+    Event step_start;  // held while a SC_KERNEL_STEP window is open (step_begin .. step_end)
+    Event span_start;  // held while a span is open (sc_span_begin .. sc_span_end)
+    std::vector<Event> event_pool;
 };
 
 namespace {
@@ -166,6 +172,11 @@ int wait_setup(sc_engine *e) {
     return SC_OK;
 }
 
+// what scown::grow waits for before an engine's buffer goes: everything on its stream
+auto stream_idle(sc_engine *e) {
+    return [e] { return schost::wait_stream(e->stream); };
+}
+
 int use_device(sc_engine *e) {
     int rc = wait_setup(e);
     if (rc) return rc;
@@ -173,55 +184,65 @@ int use_device(sc_engine *e) {
     return SC_OK;
 }
 
-int get_event(sc_engine *e, hipEvent_t *ev) {
+// `second` takes up behind what `first` holds now (a one-shot event, released once the wait has been enqueued)
+int order_streams(hipStream_t first, hipStream_t second, const char *what) {
+    Event ev;
+    HIP_TRY(hipEventCreateWithFlags(ev.out(), hipEventDisableTiming));
+    hipError_t he = hipEventRecord(ev, first);
+    if (he == hipSuccess) he = hipStreamWaitEvent(second, ev, 0);
+    if (he != hipSuccess) return fail(SC_ERR_DEVICE, "%s: %s", what, hipGetErrorString(he));
+    return SC_OK;
+}
+
+int get_event(sc_engine *e, Event &ev) {
     if (!e->event_pool.empty()) {
-        *ev = e->event_pool.back();
+        ev = std::move(e->event_pool.back());
         e->event_pool.pop_back();
         return SC_OK;
     }
-    HIP_TRY(hipEventCreate(ev));
+    HIP_TRY(hipEventCreate(ev.out()));
     return SC_OK;
 }
 
 // SC_KERNEL_STEP: one event pair around everything a fused batch puts on the stream, from the
-// packing of its masks to its last kernel.
+// packing of its masks to its last kernel.  The window is open while the engine holds its first event.
 int step_begin(sc_engine *e) {
-    if (!e->time_kernels || e->step_open || e->views_per_launch == 1) return SC_OK;
-    int rc = get_event(e, &e->step_start);
+    if (!e->time_kernels || e->step_start || e->views_per_launch == 1) return SC_OK;
+    Event start;
+    int rc = get_event(e, start);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(e->step_start, e->stream));
-    e->step_open = true;
+    HIP_TRY(hipEventRecord(start, e->stream));
+    e->step_start = std::move(start);
     return SC_OK;
 }
 
 int step_end(sc_engine *e, bool fused) {
-    if (!e->step_open) return SC_OK;
-    e->step_open = false;
+    if (!e->step_start) return SC_OK;
     if (!fused) {
-        e->event_pool.push_back(e->step_start);
+        e->event_pool.push_back(std::move(e->step_start));
         return SC_OK;
     }
-    TimedLaunch tl{};
-    tl.start = e->step_start;
-    int rc = get_event(e, &tl.stop);
+    TimedLaunch tl;
+    tl.start = std::move(e->step_start);
+    int rc = get_event(e, tl.stop);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(tl.stop, e->stream));
-    e->timed[SC_KERNEL_STEP].push_back(tl);
+    e->timed[SC_KERNEL_STEP].push_back(std::move(tl));
     return SC_OK;
 }
 
 struct LaunchTimer {
     sc_engine *e;
     int kid;
-    TimedLaunch tl{};
+    TimedLaunch tl{};  // (a begin() or end() that fails gives its events back with the timer)
     bool on = false;
     int begin() {
         if (!e->time_kernels) return SC_OK;
         if (e->time_kernels == 2 && kid != SC_KERNEL_CARVE && kid != SC_KERNEL_AVERAGE) return SC_OK;
-        if (e->time_kernels == 2 && kid == SC_KERNEL_CARVE && e->step_open) return SC_OK;  // SC_KERNEL_STEP covers it
-        int rc = get_event(e, &tl.start);
+        if (e->time_kernels == 2 && kid == SC_KERNEL_CARVE && e->step_start) return SC_OK;  // SC_KERNEL_STEP covers it
+        int rc = get_event(e, tl.start);
         if (rc) return rc;
-        rc = get_event(e, &tl.stop);
+        rc = get_event(e, tl.stop);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(tl.start, e->stream));
         on = true;
@@ -230,7 +251,7 @@ struct LaunchTimer {
     int end() {
         if (!on) return SC_OK;
         HIP_TRY(hipEventRecord(tl.stop, e->stream));
-        e->timed[kid].push_back(tl);
+        e->timed[kid].push_back(std::move(tl));
         return SC_OK;
     }
 };
@@ -268,10 +289,10 @@ int dense_state(sc_engine *e, void **ptr) {
         *ptr = e->state;
         return SC_OK;
     }
-    if (!e->dense) HIP_TRY(sc_dev_malloc(&e->dense, (size_t)e->n * 4));
+    if (!e->dense) HIP_TRY(sc_dev_malloc(e->dense.out(), (size_t)e->n * 4));
     const uint64_t rows = (uint64_t)e->planes * (uint64_t)e->ny;
     hipLaunchKernelGGL(depitch_kernel<uint32_t>, dim3((uint32_t)std::min<uint64_t>((rows + 3) / 4, 65536)), dim3(kBlock), 0,
-                       e->stream, static_cast<const uint32_t *>(e->state), static_cast<uint32_t *>(e->dense), rows,
+                       e->stream, static_cast<const uint32_t *>(e->state.get()), static_cast<uint32_t *>(e->dense.get()), rows,
                        (uint32_t)e->nz, (uint32_t)e->nzp);
     HIP_TRY(hipGetLastError());
     *ptr = e->dense;
@@ -293,7 +314,7 @@ int materialize(sc_engine *e) {
     int rc = lt.begin();
     if (rc) return rc;
     hipLaunchKernelGGL(fill_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, e->stream,
-                       static_cast<uint32_t *>(e->state), n, bits);
+                       static_cast<uint32_t *>(e->state.get()), n, bits);
     HIP_TRY(hipGetLastError());
     rc = lt.end();
     if (rc) return rc;
@@ -314,10 +335,10 @@ int arena_alloc(sc_engine *e, size_t bytes, void **out) {
     Chunk c;
     size_t last = e->chunks.empty() ? 0 : e->chunks.back().cap;
     c.cap = std::max(bytes, std::max<size_t>(last * 2, (size_t)16 << 20));
-    HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&c.base), c.cap));
+    HIP_TRY(sc_dev_malloc(c.base.out(), c.cap));
     c.used = bytes;
-    e->chunks.push_back(c);
     *out = c.base;
+    e->chunks.push_back(std::move(c));
     return SC_OK;
 }
 
@@ -328,21 +349,17 @@ void arena_reset(sc_engine *e) {
 }
 
 int ensure_slots(sc_engine *e, size_t bytes) {
-    if (bytes <= e->slot_bytes) return SC_OK;
-    HIP_TRY(schost::wait_stream(e->stream));
-    for (int s = 0; s < kSlots; ++s) {
-        if (e->pin[s]) (void)hipHostFree(e->pin[s]);
-        if (e->raw[s]) (void)hipFree(e->raw[s]);
-        e->pin[s] = e->raw[s] = nullptr;
-        e->slot_armed[s] = false;
-    }
-    e->slot_bytes = 0;
-    for (int s = 0; s < kSlots; ++s) {
-        HIP_TRY(sc_pin_malloc(&e->pin[s], bytes, hipHostMallocDefault));
-        HIP_TRY(sc_dev_malloc(&e->raw[s], bytes));
-        if (!e->slot_ev[s]) HIP_TRY(hipEventCreateWithFlags(&e->slot_ev[s], hipEventDisableTiming));
-    }
-    e->slot_bytes = bytes;
+    auto fill = [&]() -> hipError_t {
+        hipError_t he = hipSuccess;
+        for (int s = 0; s < kSlots && he == hipSuccess; ++s) {
+            e->slot_armed[s] = false;
+            he = sc_pin_malloc(e->slot[s].pin.out(), bytes, hipHostMallocDefault);
+            if (he == hipSuccess) he = sc_dev_malloc(e->slot[s].raw.out(), bytes);
+            if (he == hipSuccess && !e->slot_ev[s]) he = hipEventCreateWithFlags(e->slot_ev[s].out(), hipEventDisableTiming);
+        }
+        return he;
+    };
+    HIP_TRY(scown::grow(e->slot_bytes, bytes, stream_idle(e), fill, e->slot[0], e->slot[1], e->slot[2], e->slot[3]));
     return SC_OK;
 }
 
@@ -687,18 +704,17 @@ constexpr int kMinFusedViews = 6;  // below this a fused launch stays dense
 
 int ensure_lists(sc_engine *e) {
     if (e->lists && e->list_cap_built == e->list_cap) return SC_OK;
-    if (e->lists) {  // the capacity knob moved (tests of the overflow paths): rebuilt behind the stream
-        HIP_TRY(schost::wait_stream(e->stream));
-        (void)hipFree(e->lists);
-        e->lists = nullptr;
-    }
     // room for 5/16 of the voxels: two views of coin-flip masks leave a quarter alive, which the hashed
     // sub-lists must hold with a margin for their unevenness (an overflow sends the batch down the dense
     // special kernel's dense pass, 10 x slower)
     uint64_t total = std::max<uint64_t>((uint64_t)e->n / 4 + (uint64_t)e->n / 16, (uint64_t)kSub * 1024);
-    e->subcap = (uint32_t)((total + kSub - 1) / kSub);
-    if (e->list_cap > 0) e->subcap = (uint32_t)e->list_cap;
-    HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->lists), (size_t)2 * kSub * e->subcap * sizeof(uint32_t)));
+    const uint32_t subcap = e->list_cap > 0 ? (uint32_t)e->list_cap : (uint32_t)((total + kSub - 1) / kSub);
+    // built once, or again because the capacity knob moved (tests of the overflow paths): whatever the old size, and
+    // behind the stream when there are old lists
+    size_t built = 0;
+    HIP_TRY(scown::grow(built, 1, [&] { return e->lists ? schost::wait_stream(e->stream) : hipSuccess; },
+                        [&] { return sc_dev_malloc(e->lists.out(), (size_t)2 * kSub * subcap * sizeof(uint32_t)); }, e->lists));
+    e->subcap = subcap;
     e->list_cap_built = e->list_cap;
     return SC_OK;
 }
@@ -710,7 +726,6 @@ int ensure_ctl(sc_engine *e) {
     size_t nbricks = 0;
     if ((e->nz + kBrickZ - 1) / kBrickZ <= 64)
         nbricks = (size_t)e->planes * (size_t)((e->ny + kBrickY - 1) / kBrickY) * (size_t)((e->nz + kBrickZ - 1) / kBrickZ);
-    char *base = nullptr;
     size_t flag_bytes = (nbricks + 15) & ~(size_t)15;
     // bulk units: four per brick, hashed over the sub-lists; twice the even share each (a full one sends its
     // units' voxels down the ordinary lists)
@@ -719,19 +734,18 @@ int ensure_ctl(sc_engine *e) {
     // up to 2 halves x 2 words x 4 pieces per unit; room for a third of that on average (a full sub-list
     // sends the unit's voxels down the ordinary lists)
     const uint32_t itemcap = bulkcap * 5u;
-    uint4 *items = nullptr;
-    if (bulk_words) HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&items), (size_t)kSub * itemcap * sizeof(uint4)));
-    hipError_t he = sc_dev_malloc(reinterpret_cast<void **>(&base),
-                              2 * sizeof(ListCtl) + flag_bytes + (3 * nbricks + bulk_words) * sizeof(uint32_t) + 16);
-    if (he == hipSuccess) he = hipMemsetAsync(base, 0, 2 * sizeof(ListCtl), e->stream);
-    if (he != hipSuccess) {  // nothing of this is published before all of it exists
-        if (items) (void)hipFree(items);
-        if (base) (void)hipFree(base);
+    DevPtr<uint4> items;
+    DevPtr<char> block;
+    if (bulk_words) HIP_TRY(sc_dev_malloc(items.out(), (size_t)kSub * itemcap * sizeof(uint4)));
+    hipError_t he = sc_dev_malloc(block.out(), 2 * sizeof(ListCtl) + flag_bytes + (3 * nbricks + bulk_words) * sizeof(uint32_t) + 16);
+    if (he == hipSuccess) he = hipMemsetAsync(block, 0, 2 * sizeof(ListCtl), e->stream);
+    if (he != hipSuccess)  // nothing of this is published before all of it exists
         return fail(he == hipErrorOutOfMemory ? SC_ERR_NOMEM : SC_ERR_DEVICE, "control block allocation failed: %s", hipGetErrorString(he));
-    }
+    char *base = block;
     e->bulkcap = bulkcap;
     e->itemcap = itemcap;
-    e->items = items;
+    e->items = std::move(items);
+    e->ctl_base = std::move(block);
     e->ctl2[0] = reinterpret_cast<ListCtl *>(base);
     e->ctl2[1] = e->ctl2[0] + 1;
     e->ctl_clean[0] = e->ctl_clean[1] = true;
@@ -803,27 +817,22 @@ int hostbits_reserve(sc_engine *e, size_t bytes, char **out) {
     }
     if (a.used + bytes > a.cap) {
         const size_t cap = std::max<size_t>({a.used + bytes, a.cap * 2, (size_t)16 << 20});
-        char *pin = nullptr, *dev = nullptr;
-        HIP_TRY(sc_pin_malloc(reinterpret_cast<void **>(&pin), cap, hipHostMallocDefault));
-        hipError_t he = sc_dev_malloc(reinterpret_cast<void **>(&dev), cap);
-        if (he != hipSuccess) {
-            (void)hipHostFree(pin);
+        PinPtr<char> pin;
+        DevPtr<char> dev;
+        HIP_TRY(sc_pin_malloc(pin.out(), cap, hipHostMallocDefault));
+        const hipError_t he = sc_dev_malloc(dev.out(), cap);
+        if (he != hipSuccess)
             return fail(he == hipErrorOutOfMemory ? SC_ERR_NOMEM : SC_ERR_DEVICE, "host-mask arena: %s", hipGetErrorString(he));
-        }
         if (a.used) memcpy(pin, a.pin, a.used);
-        if (a.pin) {
-            // the old blocks may be the source / target of a copy still on the stream (a.used > 0 means: not of this
-            // batch's, but an earlier flush's): wait before they go
-            HIP_TRY(schost::wait_stream(e->stream));
-            (void)hipHostFree(a.pin);
-            (void)hipFree(a.dev);
-        }
-        a.pin = pin;
-        a.dev = dev;
+        // the old blocks may be the source / target of a copy still on the stream (a.used > 0 means: not of this
+        // batch's, but an earlier flush's): wait before they go
+        if (a.pin) HIP_TRY(schost::wait_stream(e->stream));
+        a.pin = std::move(pin);
+        a.dev = std::move(dev);
         a.cap = cap;
         a.armed = false;
     }
-    if (!a.ev) HIP_TRY(hipEventCreateWithFlags(&a.ev, hipEventDisableTiming));
+    if (!a.ev) HIP_TRY(hipEventCreateWithFlags(a.ev.out(), hipEventDisableTiming));
     *out = a.pin + a.used;
     a.used += bytes;
     return SC_OK;

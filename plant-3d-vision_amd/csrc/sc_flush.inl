@@ -172,14 +172,12 @@ int stage_descriptors(sc_engine *e, size_t nv, const ViewDesc **dev, const ViewD
         e->views_head = 0;
     }
     if (nv > e->views_cap) {
-        if (e->views_dev) (void)hipFree(e->views_dev);
-        if (e->views_pin) (void)hipHostFree(e->views_pin);
-        e->views_dev = e->views_pin = nullptr;
-        e->views_cap = 0;
-        size_t cap = std::max<size_t>(nv * 8, 4096);  // (a wrap every 56 batches of 72 views; 1024 until round 4)
-        HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->views_dev), cap * sizeof(ViewDesc)));
-        HIP_TRY(sc_pin_malloc(reinterpret_cast<void **>(&e->views_pin), cap * sizeof(ViewDesc), hipHostMallocDefault));
-        e->views_cap = cap;
+        const size_t cap = std::max<size_t>(nv * 8, 4096);  // (a wrap every 56 batches of 72 views; 1024 until round 4)
+        auto ring = [&] {
+            const hipError_t he = sc_dev_malloc(e->views_dev.out(), cap * sizeof(ViewDesc));
+            return he != hipSuccess ? he : sc_pin_malloc(e->views_pin.out(), cap * sizeof(ViewDesc), hipHostMallocDefault);
+        };
+        HIP_TRY(scown::grow(e->views_cap, cap, [] { return hipSuccess; }, ring, e->views_dev, e->views_pin));  // (waited above)
     }
     memcpy(e->views_pin + e->views_head, e->pending.data(), nv * sizeof(ViewDesc));
     *pin = e->views_pin + e->views_head;
@@ -211,7 +209,7 @@ int launch_dense_bricks(sc_engine *e, const GridDesc &g, const CarveBatch &b, co
     // for them
     const uint32_t nwalkers = ride.blocks ? kBrickWalkers : kListBlocks;
     if (!e->dead) {
-        HIP_TRY(sc_dev_malloc(reinterpret_cast<void **>(&e->dead), (size_t)nbricks));
+        HIP_TRY(sc_dev_malloc(e->dead.out(), (size_t)nbricks));
         e->dead_clean = false;
     }
     const int dead_stale = e->dead_clean ? 0 : 1;  // the flags kernel rewrites them all
@@ -369,7 +367,7 @@ int launch_list_stages(sc_engine *e, const GridDesc &g, const CarveBatch &b, con
 // The fused carve of a batch, or of one view in brick form: dense for the first `ndense` views (brick form: behind the
 // flags kernel's verdicts), then -- survivor compaction -- the list stages.
 int carve_batch(sc_engine *e, size_t nv, const GridDesc &g, const ViewDesc *vd, const ViewDesc *vpin, const Ride &ride) {
-    CarveBatch b{nv, fused_plan(e, nv, e->pending[0].occ != nullptr), vd, vpin, static_cast<int32_t *>(e->state), init_bits_i32(e)};
+    CarveBatch b{nv, fused_plan(e, nv, e->pending[0].occ != nullptr), vd, vpin, static_cast<int32_t *>(e->state.get()), init_bits_i32(e)};
     const FusedPlan &fp = b.fp;
     const bool compact = fp.compact, brick = fp.brick;
     // what sc_values_sparse may take from this launch's verdict bytes and lists (sc_sparse.h)
@@ -451,24 +449,19 @@ int carve_stream(sc_engine *e, const GridDesc &g) {
     const uint32_t per_block = !e->fresh ? kBlock * kStreamGroups : kBlock;
     const dim3 grid1((uint32_t)((g.ngroups + per_block - 1) / per_block));
     hipLaunchKernelGGL((e->fresh ? carve_kernel_1<true, true> : carve_kernel_1<false, true>), grid1, dim3(kBlock), 0, e->stream,
-                       static_cast<int32_t *>(e->state), g, e->pending[0], init_bits_i32(e));
+                       static_cast<int32_t *>(e->state.get()), g, e->pending[0], init_bits_i32(e));
     HIP_TRY(hipGetLastError());
     return lt.end();
 }
 
-// A device buffer of `need` elements of `size` bytes, grown behind the stream (the brick averaging form's verdicts).
-int grow_buffer(sc_engine *e, void **buf, size_t *cap, size_t need, size_t size) {
-    if (need <= *cap) return SC_OK;
-    HIP_TRY(schost::wait_stream(e->stream));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(sc_dev_malloc(buf, need * size));
-    *cap = need;
+// The brick averaging form's verdict buffers, `need` elements each, grown behind the stream.
+int grow_verdicts(sc_engine *e, size_t need, bool f32) {
+    HIP_TRY(scown::grow(e->verd_cap, need, stream_idle(e), [&] { return sc_dev_malloc(e->verd.out(), need); }, e->verd));
+    if (f32) HIP_TRY(scown::grow(e->verdf_cap, need, stream_idle(e), [&] { return sc_dev_malloc(e->verdf.out(), need * 4); }, e->verdf));
     return SC_OK;
 }
 
-// The brick averaging form of `nv` views (descriptors at vd, verdict buffers grown: grow_buffer): the uniformity verdicts of every
+// The brick averaging form of `nv` views (descriptors at vd, verdict buffers grown: grow_verdicts): the uniformity verdicts of every
 // (brick, view), then the bricks.  `timed`: each launch under its kernel timer.
 int launch_average_bricks(sc_engine *e, const GridDesc &g, const ViewDesc *vd, int nv, uint32_t *verdf, bool timed) {
     const uint32_t abys = (uint32_t)((e->ny + kBrickY - 1) / kBrickY), abzs = (uint32_t)((e->nz + kBrickZ - 1) / kBrickZ);
@@ -483,7 +476,7 @@ int launch_average_bricks(sc_engine *e, const GridDesc &g, const ViewDesc *vd, i
     rc = timed ? lta.begin() : SC_OK;
     if (rc) return rc;
     hipLaunchKernelGGL(e->fresh ? average_brick_kernel<true> : average_brick_kernel<false>, dim3(anb), dim3(kBlock), 0, e->stream,
-                       static_cast<float *>(e->state), g, vd, nv, e->default_value, e->lut_dev, abys, abzs, e->verd, verdf);
+                       static_cast<float *>(e->state.get()), g, vd, nv, e->default_value, e->lut_dev, abys, abzs, e->verd, verdf);
     HIP_TRY(hipGetLastError());
     return lta.end();
 }
@@ -505,15 +498,14 @@ int average_batch(sc_engine *e, size_t nv, const GridDesc &g, const ViewDesc *vd
     }
     if (abrick) {
         const size_t need = (size_t)e->planes * abys * abzs * nv;  // (the flat values of float32 views as well)
-        rc = grow_buffer(e, reinterpret_cast<void **>(&e->verd), &e->verd_cap, need, 1);
-        if (!rc && any_f32) rc = grow_buffer(e, reinterpret_cast<void **>(&e->verdf), &e->verdf_cap, need, 4);
+        rc = grow_verdicts(e, need, any_f32);
         if (rc) return rc;
-        return launch_average_bricks(e, g, vd, (int)nv, any_f32 ? e->verdf : nullptr, true);
+        return launch_average_bricks(e, g, vd, (int)nv, any_f32 ? e->verdf.get() : nullptr, true);
     }
     LaunchTimer lt{e, SC_KERNEL_AVERAGE};
     rc = lt.begin();
     if (rc) return rc;
-    float *st = static_cast<float *>(e->state);
+    float *st = static_cast<float *>(e->state.get());
     const dim3 grid((uint32_t)((g.ngroups + kBlock - 1) / kBlock)), block(kBlock);
     if (nv == 1)
         hipLaunchKernelGGL((e->fresh ? average_kernel_1<true, true> : average_kernel_1<false, true>), grid, block, 0, e->stream, st, g,
@@ -650,7 +642,7 @@ int device_setup_body(sc_engine *e) {
     }
     hipError_t he = sctrace::timed("hipSetDevice", __LINE__, 0, [&] { return hipSetDevice(device); });
     if (he == hipSuccess) he = take_stream(device, &e->own_stream);
-    if (he == hipSuccess) he = sc_dev_malloc(&e->state, (size_t)e->npitch * 4);
+    if (he == hipSuccess) he = sc_dev_malloc(e->state.out(), (size_t)e->npitch * 4);
     if (he != hipSuccess)
         return fail(he == hipErrorOutOfMemory ? SC_ERR_NOMEM : SC_ERR_DEVICE, "engine setup failed: %s", hipGetErrorString(he));
     e->stream = e->own_stream;

@@ -86,6 +86,8 @@ inline hipError_t host(T **p, size_t bytes, unsigned flags, int line) {
 #define sc_dev_malloc(p, n) sctrace::dev((p), (n), __LINE__)
 #define sc_pin_malloc(p, n, f) sctrace::host((p), (n), (f), __LINE__)
 
+#include "sc_own.h"
+
 namespace {
 
 // ------------------------------------------------------------------------------------------
@@ -130,12 +132,12 @@ int fail(int code, const char *fmt, ...) {
     } while (0)
 
 struct Chunk {
-    char *base = nullptr;
+    DevPtr<char> base;
     size_t cap = 0, used = 0;
 };
 
 struct TimedLaunch {
-    hipEvent_t start, stop;
+    Event start, stop;
 };
 
 constexpr int kSlots = 4;
