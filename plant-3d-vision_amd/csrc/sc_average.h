@@ -237,11 +237,9 @@ __global__ __launch_bounds__(kBlock) void avg_flags_kernel(GridDesc g, const Vie
     const uint32_t lb = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t vi = blockIdx.y;  // block-uniform view: scalar descriptor
     if (lb >= nbricks) return;
-    const uint32_t per_plane = bricks_y * bricks_z;
-    const uint32_t il = lb / per_plane;
-    const uint32_t rem = lb - il * per_plane;
-    const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
-    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;
+    const BrickAt at = brick_at(lb, bricks_y, bricks_z);
+    const uint32_t by = at.by, bz = at.bz;
+    const float x = plane_x(g, at.il);
     const ViewDesc d = views[vi];
     // Verdict 5 (round 5): the footprint is MIXED -- the voxels have to be projected -- but lies wholly inside the picture
     // (rect_box: every voxel of the brick in front of the camera, its pixel inside the picture, rounding included):
@@ -283,13 +281,11 @@ __global__ __launch_bounds__(kBlock) void average_brick_kernel(float *__restrict
     lut_s[threadIdx.x] = lut != nullptr ? lut[threadIdx.x] : 0.0f;  // kBlock == 256
     __syncthreads();
     const uint32_t lb = spread_block(blockIdx.x, gridDim.x);
-    const uint32_t per_plane = bricks_y * bricks_z;
-    const uint32_t il = lb / per_plane;
-    const uint32_t rem = lb - il * per_plane;
-    const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
+    const BrickAt at = brick_at(lb, bricks_y, bricks_z);
+    const uint32_t il = at.il;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const uint32_t j = by * kBrickY + wave * 4 + (lane >> 4);
-    const uint32_t k0 = bz * kBrickZ + (lane & 15) * 4;
+    const uint32_t j = at.by * kBrickY + wave * 4 + (lane >> 4);
+    const uint32_t k0 = at.bz * kBrickZ + (lane & 15) * 4;
     const bool inside = j < g.ny && k0 < g.nz;
     const int nvalid = inside ? (int)min(4u, g.nz - k0) : 0;
     const bool vec = (g.nzp & 3u) == 0;
@@ -307,8 +303,8 @@ __global__ __launch_bounds__(kBlock) void average_brick_kernel(float *__restrict
                 if (e < nvalid) val[e] = p[e];
         }
     }
-    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;  // backprojection.c:71-73
-    const float y = g.oy + (float)(int)j * g.vs;
+    const float x = plane_x(g, il);
+    const float y = g.oy + (float)(int)j * g.vs;  // backprojection.c:72-73
     float z[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) z[e] = g.oz + (float)(int)(k0 + e) * g.vs;
@@ -410,13 +406,10 @@ __global__ __launch_bounds__(kBlock) void avg_flags_multi_kernel(MultiArgs a, Gr
     const uint32_t lb = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t vi = blockIdx.y;  // block-uniform view: scalar descriptor
     if (lb >= nbricks) return;
-    const uint32_t per_plane = bricks_y * bricks_z;
-    const uint32_t il = lb / per_plane;
-    const uint32_t rem = lb - il * per_plane;
-    const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
-    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;
+    const BrickAt at = brick_at(lb, bricks_y, bricks_z);
+    const float x = plane_x(g, at.il);
     const ViewDesc d = a.views[0][vi];
-    const Footprint fpr = brick_footprint(d, g, x, (int)(by * kBrickY), (int)(bz * kBrickZ));
+    const Footprint fpr = brick_footprint(d, g, x, (int)(at.by * kBrickY), (int)(at.bz * kBrickZ));
     const int occ_tx = (d.W + 31) >> 5;
     uint32_t v[L];
 #pragma unroll
@@ -451,13 +444,11 @@ __global__ __launch_bounds__(kBlock) void average_multi_kernel(MultiArgs a, Grid
     for (int l = 0; l < L; ++l) lut_s[l][threadIdx.x] = a.lut[l][threadIdx.x];  // kBlock == 256
     __syncthreads();
     const uint32_t lb = spread_block(blockIdx.x, gridDim.x);
-    const uint32_t per_plane = bricks_y * bricks_z;
-    const uint32_t il = lb / per_plane;
-    const uint32_t rem = lb - il * per_plane;
-    const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
+    const BrickAt at = brick_at(lb, bricks_y, bricks_z);
+    const uint32_t il = at.il;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const uint32_t j = by * kBrickY + wave * 4 + (lane >> 4);
-    const uint32_t k0 = bz * kBrickZ + (lane & 15) * 4;
+    const uint32_t j = at.by * kBrickY + wave * 4 + (lane >> 4);
+    const uint32_t k0 = at.bz * kBrickZ + (lane & 15) * 4;
     const bool inside = j < g.ny && k0 < g.nz;
     const uint64_t elem = ((uint64_t)il * g.ny + j) * g.nzp + k0;  // the pitch is a multiple of 64: 16-byte groups
     float val[L][4];
@@ -470,8 +461,8 @@ __global__ __launch_bounds__(kBlock) void average_multi_kernel(MultiArgs a, Grid
             val[l][0] = q.x; val[l][1] = q.y; val[l][2] = q.z; val[l][3] = q.w;
         }
     }
-    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;  // backprojection.c:71-73
-    const float y = g.oy + (float)(int)j * g.vs;
+    const float x = plane_x(g, il);
+    const float y = g.oy + (float)(int)j * g.vs;  // backprojection.c:72-73
     float z[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) z[e] = g.oz + (float)(int)(k0 + e) * g.vs;

@@ -86,7 +86,7 @@ __device__ __forceinline__ void brick_voxels(int32_t *__restrict__ labels, const
         alive[e] = __ballot(lab[e] != -1);  // :67
         kept[e] = 0;
     }
-    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;  // :71, global plane index
+    const float x = plane_x(g, il);
     const float y = g.oy + (float)(int)j * g.vs;
     float z[4];
 #pragma unroll
@@ -285,7 +285,6 @@ __global__ __launch_bounds__(64 * kConfirmWaves) void brick_confirm_kernel(
     __shared__ unsigned long long s_full[kConfirmWaves], s_seen[kConfirmWaves];
     __shared__ unsigned long long s_road, s_rseen;  // the group's failed candidates that take the units' road, and who saw them
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    const uint32_t per_plane = bricks_y * bricks_z;
     // a persistent grid over the groups of 64 candidates
     for (uint32_t grp = blockIdx.x; grp < gfirst[kCandSub]; grp += gridDim.x) {
         uint32_t sub = 0, first = 0, n = ncand[0];
@@ -298,16 +297,14 @@ __global__ __launch_bounds__(64 * kConfirmWaves) void brick_confirm_kernel(
         const uint32_t fl = isc ? flags[lb] : 0u;
         unsigned long long any_seen = __ballot(fl == 3u);  // some view so far saw the brick whole (7: none sees it)
         unsigned long long cand = __ballot(isc);
-        const uint32_t il = lb / per_plane;
-        const uint32_t rem = lb - il * per_plane;
-        const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
-        const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;
+        const BrickAt cb = brick_at(lb, bricks_y, bricks_z);
+        const float x = plane_x(g, cb.il);
         for (int base = v0; base < v1 && cand != 0; base += kConfirmWaves) {  // block-uniform
             const int vi = base + (int)wave;
             bool keeps = true, sees = false;
             if (vi < v1 && ((cand >> lane) & 1ull)) {
                 const ViewDesc d = views[vi];
-                const uint32_t v = brick_verdict(d, g, x, (int)(by * kBrickY), (int)(bz * kBrickZ), d.tiles_x);
+                const uint32_t v = brick_verdict(d, g, x, (int)(cb.by * kBrickY), (int)(cb.bz * kBrickZ), d.tiles_x);
                 keeps = v == 2u || v == 4u;
                 sees = v == 2u;
             }
@@ -327,8 +324,7 @@ __global__ __launch_bounds__(64 * kConfirmWaves) void brick_confirm_kernel(
                 uint32_t pos = 0;
                 if (lane == 0) pos = atomicAdd(road ? &ctl->nlate_units : &ctl->nlate, (uint32_t)__popcll(m));
                 pos = __shfl(pos, 0);
-                const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-                const uint32_t at = pos + (uint32_t)__popcll(m & below);
+                const uint32_t at = pos + lanes_below(m);
                 if (failed) late[road ? ur.nbricks - 1u - at : at] = lb;  // (failed candidates are bricks: both ends fit)
             }
             if (lane == 0) { s_road = road ? m : 0ull; s_rseen = any_seen; }  // (words of their own: a wavefront may still be reading the last round's)
@@ -344,14 +340,13 @@ __global__ __launch_bounds__(64 * kConfirmWaves) void brick_confirm_kernel(
                 const uint32_t src = (uint32_t)__builtin_ctzll(mm);
                 const uint32_t b = __builtin_amdgcn_readlane(lb, src);
                 const bool seen = (ms >> src) & 1ull;
-                const uint32_t bil = b / per_plane, brem = b - bil * per_plane;
-                const uint32_t bby = brem / bricks_z, bbz = brem - bby * bricks_z;
-                const uint32_t k0 = bbz * kBrickZ + (lane & 15u) * 4u;
+                const BrickAt rb = brick_at(b, bricks_y, bricks_z);
+                const uint32_t k0 = rb.bz * kBrickZ + (lane & 15u) * 4u;
 #pragma unroll
                 for (uint32_t i = 0; i < 4u; ++i) {
-                    const uint32_t j = bby * kBrickY + i * 4u + (lane >> 4);
+                    const uint32_t j = rb.by * kBrickY + i * 4u + (lane >> 4);
                     if (j >= g.ny || k0 >= g.nz) continue;
-                    int32_t *p = ur.labels + ((uint64_t)bil * g.ny + j) * g.nzp + k0;  // the pitch is a multiple of 64: 16-byte groups
+                    int32_t *p = ur.labels + ((uint64_t)rb.il * g.ny + j) * g.nzp + k0;  // the pitch is a multiple of 64: 16-byte groups
                     if (ur.fresh) {
                         const int32_t val = (seen && ur.init == 0) ? 1 : ur.init;  // backprojection.c:81 by a view that keeps the brick whole
                         *reinterpret_cast<int4 *>(p) = make_int4(val, val, val, val);
@@ -417,7 +412,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
     // device, from this batch's own live count)
     if (nlive < bulk_min_live) ap.bulk = nullptr;
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t per_plane = bricks_y * bricks_z;
     const uint32_t xcd = blockIdx.x & 7u;
     // (the first ticket of a wavefront is its own number among the XCD's: a thousand atomics on one address at the
     // kernel's start would take longer than the first bricks)
@@ -453,9 +447,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
         if ((t / kXcdRun) * 8u * kXcdRun >= nlive) break;  // past the last run for every XCD
         if (entry >= nlive) continue;
         const uint32_t lb = __builtin_amdgcn_readfirstlane(live[entry]);
-        const uint32_t il = lb / per_plane;
-        const uint32_t rem = lb - il * per_plane;
-        const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
+        const BrickAt at = brick_at(lb, bricks_y, bricks_z);
+        const uint32_t il = at.il, by = at.by, bz = at.bz;
         uint32_t culled = 0;
 #ifdef SC_TRACE_DENSE
         const uint64_t trb = wall_clock64();
@@ -471,7 +464,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
             uint32_t v = 0u;
             if ((int)vq < nverd) {
                 const ViewDesc d = views[vq];  // one descriptor per lane
-                const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;
+                const float x = plane_x(g, il);
                 v = rect_verdict_cells(d, g, x, (int)(by * kBrickY), (int)(by * kBrickY) + kBrickY - 1,
                                        (int)(bz * kBrickZ + u * 16u), (int)(bz * kBrickZ + u * 16u) + 15);
             }
@@ -538,13 +531,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
                 const uint32_t ent = __builtin_amdgcn_readlane(mine, q);
                 const bool isfull = (ent >> 31) != 0, isunt = ((ent >> 30) & 1u) != 0;
                 if (isunt && !FRESH) continue;  // kept and unseen: the labels stay
-                const uint32_t lb = ent & 0x3fffffffu;
-                const uint32_t il = lb / per_plane;
-                const uint32_t rem = lb - il * per_plane;
-                const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
-                const uint32_t j = by * kBrickY + wave * 4 + (lane >> 4), k0 = bz * kBrickZ + (lane & 15) * 4;
+                const BrickAt at = brick_in_plane(ent & 0x3fffffffu, per_plane, bricks_z);
+                const uint32_t j = at.by * kBrickY + wave * 4 + (lane >> 4), k0 = at.bz * kBrickZ + (lane & 15) * 4;
                 if (j >= g.ny || k0 >= g.nz) continue;
-                int32_t *p = labels + ((uint64_t)il * g.ny + j) * g.nzp + k0;
+                int32_t *p = labels + ((uint64_t)at.il * g.ny + j) * g.nzp + k0;
                 const uint32_t nv4 = min(4u, g.nz - k0);
                 if (!isfull || FRESH) {
                     const int32_t val = isunt ? init : (isfull ? kept : -1);
@@ -564,18 +554,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(102))) void 
         return;
     }
     const uint32_t nlive = ctl->nlive[parity];
-    const Append none{nullptr, nullptr, 0u, 0u, nullptr, 0u, 0u};
     const uint32_t xcd = blockIdx.x & 7u, seq = blockIdx.x >> 3, per_xcd = nwalkers >> 3;
     for (uint32_t t = seq; ; t += per_xcd) {
         const uint32_t entry = ((t / kXcdRun) * 8u + xcd) * kXcdRun + (t % kXcdRun);
         if ((t / kXcdRun) * 8u * kXcdRun >= nlive) break;  // past the last run for every XCD
         if (entry >= nlive) continue;
         const uint32_t lb = live[entry];
-        const uint32_t il = lb / per_plane;
-        const uint32_t rem = lb - il * per_plane;
-        const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
-        const uint32_t j = by * kBrickY + wave * 4 + (lane >> 4);
-        brick_voxels<FRESH>(labels, g, views, nviews, init, none, il, j, bz * kBrickZ + (lane & 15) * 4, lb, lane);
+        const BrickAt at = brick_in_plane(lb, per_plane, bricks_z);
+        const uint32_t j = at.by * kBrickY + wave * 4 + (lane >> 4);
+        brick_voxels<FRESH>(labels, g, views, nviews, init, Append{}, at.il, j, at.bz * kBrickZ + (lane & 15) * 4, lb, lane);
     }
 }
 
@@ -590,7 +577,6 @@ __global__ __launch_bounds__(kBlock) void carve_kernel_1(int32_t *__restrict__ l
     constexpr int G = !FRESH ? kStreamGroups : 1;
     uint32_t lb = spread_block(blockIdx.x, gridDim.x);
     uint64_t grp = (uint64_t)lb * (kBlock * G) + threadIdx.x;
-    Append none{nullptr, nullptr, 0u, 0u, nullptr, 0u, 0u};
     int4 cur = make_int4(-1, -1, -1, -1);
     // streaming loads: the state (512 MiB) is far bigger than the Infinity Cache, every view
     // reads all of it once
@@ -605,7 +591,7 @@ __global__ __launch_bounds__(kBlock) void carve_kernel_1(int32_t *__restrict__ l
         int4 nxt = make_int4(-1, -1, -1, -1);
         if (G > 1 && s + 1 < G && grp + kBlock < g.ngroups)
             nxt = stream_load(grp + kBlock);
-        if (grp < g.ngroups) carve_group<FRESH>(labels, g, &view, 1, init, grp, cur, none);
+        if (grp < g.ngroups) carve_group<FRESH>(labels, g, &view, 1, init, grp, cur, Append{});
         cur = nxt;
     }
 }

@@ -1,5 +1,5 @@
 // Part of spacecarve.hip (included there, inside its anonymous namespace, in this order: sc_types, sc_project,
-// sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- the survivor stages (carve_list_kernel), the bulk units' verdicts and the special kernel (bulk units, late bricks, the dense fallback).
+// sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- the sub-lists' scan and search (scan_sublists, sublist_of), the survivor stages (carve_list_kernel), the bulk units' verdicts and the special kernel (bulk units, late bricks, the dense fallback).
 
 // Work items of the bulk units (see unit_verdicts): (half a unit = 8 columns x 16 voxels, up to 16 of the
 // views that have to project its voxels, as a mask over 64 consecutive views).  The final list stage's
@@ -36,6 +36,36 @@ struct UnitSpill {
     uint32_t cap, floor;
     uint32_t bricks_y, bricks_z;
 };
+
+// The work of the kSub sub-lists as ONE run of items: thread tid brings sub-list tid's count c, and the block leaves
+// with pf[0] = 0, pf[s + 1] = the items of sub-lists 0 .. s (an inclusive scan in LDS, two barriers a step).
+// GUARDED: a block of more than kSub threads (the special kernel's 512) -- the others only keep the barriers.
+template <bool GUARDED = false>
+__device__ __forceinline__ void scan_sublists(uint32_t *pf, uint32_t c, uint32_t tid) {
+    const bool mine = !GUARDED || tid < kSub;
+    if (tid == 0) pf[0] = 0;
+    if (mine) pf[tid + 1] = c;
+    __syncthreads();
+    for (uint32_t off = 1; off < kSub; off <<= 1) {
+        uint32_t val = 0, add = 0;
+        if (mine) {
+            val = pf[tid + 1];
+            add = (tid >= off) ? pf[tid + 1 - off] : 0u;
+        }
+        __syncthreads();
+        if (mine) pf[tid + 1] = val + add;
+        __syncthreads();
+    }
+}
+// ... and the sub-list item `key` of that run belongs to: the largest s with pf[s] <= key (it is item key - pf[s] there)
+__device__ __forceinline__ uint32_t sublist_of(const uint32_t *pf, uint32_t key) {
+    uint32_t lo = 0, hi = kSub;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pf[mid] <= key) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // Fused carve, sparse phase: one lane per SURVIVOR.  Reads the survivor sub-lists a previous
 // stage appended and applies views with every lane busy, two views per iteration (two
@@ -99,19 +129,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
     if (ctl->overflow) return;  // the special kernel's dense pass has applied the remaining views instead
     const uint32_t bid = bx;
     constexpr uint32_t CH = 64u * P;
-    {
-        uint32_t c = (list_count(ctl->count[sin][tid], subcap) + CH - 1u) / CH;  // kSub == kBlock
-        if (tid == 0) pref[0] = 0;
-        pref[tid + 1] = c;
-        __syncthreads();
-        for (uint32_t off = 1; off < kSub; off <<= 1) {
-            uint32_t val = pref[tid + 1];
-            uint32_t add = (tid >= off) ? pref[tid + 1 - off] : 0u;
-            __syncthreads();
-            pref[tid + 1] = val + add;
-            __syncthreads();
-        }
-    }
+    scan_sublists(pref, (list_count(ctl->count[sin][tid], subcap) + CH - 1u) / CH, tid);  // kSub == kBlock
     const uint32_t chunks = pref[kSub];
     const uint32_t lane = tid & 63u;
     __shared__ uint32_t ipref[kSub + 1];  // FINAL: the work items' prefix; else: the spilled bulk units'
@@ -119,32 +137,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
     uint32_t uchunks = 0;  // chunks made of spilled bulk units, behind the list's own
     constexpr uint32_t kUnitParts = 256u / (64u * P);  // chunks per unit
     if (!FINAL && us.units != nullptr) {  // grid-uniform
-        const uint32_t c = min(ctl->count[3][tid].n, us.cap);
-        if (tid == 0) ipref[0] = 0;
-        ipref[tid + 1] = c;
-        __syncthreads();
-        for (uint32_t off = 1; off < kSub; off <<= 1) {
-            const uint32_t val = ipref[tid + 1];
-            const uint32_t add = (tid >= off) ? ipref[tid + 1 - off] : 0u;
-            __syncthreads();
-            ipref[tid + 1] = val + add;
-            __syncthreads();
-        }
+        scan_sublists(ipref, min(ctl->count[3][tid].n, us.cap), tid);
         if (ipref[kSub] < us.floor) uchunks = ipref[kSub] * kUnitParts;  // (else the special kernel has dealt with them)
     }
-    if (with_items) {
-        const uint32_t c = list_count(ctl->count[4][tid], ui.cap);
-        if (tid == 0) ipref[0] = 0;
-        ipref[tid + 1] = c;
-        __syncthreads();
-        for (uint32_t off = 1; off < kSub; off <<= 1) {
-            const uint32_t val = ipref[tid + 1];
-            const uint32_t add = (tid >= off) ? ipref[tid + 1 - off] : 0u;
-            __syncthreads();
-            ipref[tid + 1] = val + add;
-            __syncthreads();
-        }
-    }
+    if (with_items) scan_sublists(ipref, list_count(ctl->count[4][tid], ui.cap), tid);
     const uint64_t nworkers = (uint64_t)nbid * (kBlock / 64);
     // the wavefront index must be a scalar for the compiler, or everything derived from the
     // item (view range, descriptors) is treated as divergent and fetched with vector loads
@@ -182,12 +178,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
         const bool from_unit = !FINAL && c >= chunks;  // wave-uniform: a chunk of a spilled bulk unit
         const uint32_t *pf = from_unit ? ipref : pref;
         const uint32_t key = from_unit ? (c - chunks) / kUnitParts : c;
-        uint32_t lo = 0, hi = kSub;  // largest s with pf[s] <= key (wave-uniform)
-        while (hi - lo > 1) {
-            uint32_t mid = (lo + hi) >> 1;
-            if (pf[mid] <= key) lo = mid; else hi = mid;
-        }
-        const uint32_t s = lo;
+        const uint32_t s = sublist_of(pf, key);  // wave-uniform
         const uint32_t cnt = list_count(ctl->count[sin][s], subcap);
         // P voxels per lane: the descriptor traffic and the scalar bookkeeping of a view are shared,
         // and a lane has P * U independent projection chains and gathers in flight.
@@ -207,14 +198,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             if (from_unit) {
-                // voxel v of the unit (16 columns x 16 voxels of brick unit >> 2, its z quarter unit & 3): column v >> 4
+                // voxel v of the unit (16 columns x 16 voxels, unit_at): column v >> 4
                 const uint32_t v = upart * CH + (uint32_t)p * 64u + lane;
-                const uint32_t lb = unit >> 2, per_plane = us.bricks_y * us.bricks_z;
-                const uint32_t il = lb / per_plane, rem = lb - il * per_plane;
-                const uint32_t by = rem / us.bricks_z, bz = rem - by * us.bricks_z;
-                const uint32_t j = by * kBrickY + (v >> 4), k = bz * kBrickZ + (unit & 3u) * 16u + (v & 15u);
+                const UnitAt at = unit_at(unit, us.bricks_y, us.bricks_z);
+                const uint32_t j = at.j0 + (v >> 4), k = at.kb + (v & 15u);
                 const bool inside = j < g.ny && k < g.nz;
-                idx[p] = inside ? (il * g.ny + j) * g.nzp + k : 0u;
+                idx[p] = inside ? (at.il * g.ny + j) * g.nzp + k : 0u;
                 int32_t lab = -1;
                 if (inside) lab = labels[idx[p]];
                 alive_m[p] = __ballot(lab != -1);   // backprojection.c:67
@@ -233,8 +222,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
             const uint32_t k = idx[p] - col * g.nzp;
             const uint32_t il = fdiv(col, g.by_ny);
             const uint32_t j = col - il * g.ny;
-            x[p] = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;  // backprojection.c:71-73
-            y[p] = g.oy + (float)(int)j * g.vs;
+            x[p] = plane_x(g, il);
+            y[p] = g.oy + (float)(int)j * g.vs;  // backprojection.c:72-73
             z[p] = g.oz + (float)(int)k * g.vs;
         }
         // U views per iteration: four (8 projection chains and 8 gathers in flight per lane).  The final stage ran
@@ -336,26 +325,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
         // the bulk units' work items, dealt round-robin: two voxels per lane, the views the item names, two
         // per turn as above
         const uint32_t itotal = ipref[kSub];
-        const uint32_t per_plane = ui.bricks_y * ui.bricks_z;
         for (uint32_t i = (uint32_t)wid; i < itotal; i += (uint32_t)nworkers) {
-            uint32_t lo = 0, hi = kSub;  // largest s with ipref[s] <= i (wave-uniform)
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (ipref[mid] <= i) lo = mid; else hi = mid;
-            }
+            const uint32_t lo = sublist_of(ipref, i);  // wave-uniform
             uint4 it = ui.items[(size_t)lo * ui.cap + (i - ipref[lo])];
             it.x = __builtin_amdgcn_readfirstlane(it.x);
             it.y = __builtin_amdgcn_readfirstlane(it.y);
             it.z = __builtin_amdgcn_readfirstlane(it.z);
             it.w = __builtin_amdgcn_readfirstlane(it.w);
-            const uint32_t unit = it.x >> 1, lb = unit >> 2;
-            const uint32_t il = lb / per_plane, rem = lb - il * per_plane;
-            const uint32_t by = rem / ui.bricks_z, bz = rem - by * ui.bricks_z;
+            const UnitAt at = unit_at(it.x >> 1, ui.bricks_y, ui.bricks_z);
+            const uint32_t il = at.il;
             // half h of a unit: its columns 8 h .. 8 h + 7; lane = column * 8 + (voxel & 7), p = voxel >> 3: a lane's two
             // voxels share their column, so the x and y terms of a view's three sums are computed once for both
-            const uint32_t j = by * kBrickY + (it.x & 1u) * 8u + (lane >> 3), k0 = bz * kBrickZ + (unit & 3u) * 16u + (lane & 7u);
-            const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;  // backprojection.c:71-73
-            const float y = g.oy + (float)(int)j * g.vs;
+            const uint32_t j = at.j0 + (it.x & 1u) * 8u + (lane >> 3), k0 = at.kb + (lane & 7u);
+            const float x = plane_x(g, il);
+            const float y = g.oy + (float)(int)j * g.vs;  // backprojection.c:72-73
             uint32_t idx[2];
             unsigned long long alive_m[2], zero_m[2];
             float z[2];
@@ -401,6 +384,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(96))) void c
                         if (ok) w[q][p] = load_mask_at(d.mask, mask_byte_offset(sh[q][p], vv, tile_row));
                     }
                 }
+                // (the same application as the chunk loop's, U = 2 and always final.  As ONE function of U, P and FINAL
+                // for both, the final stage's instances grew by 58 to 108 instructions and took wavefront masks through
+                // vector registers: the two copies stay)
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     unsigned long long carve = 0, keep = 0;
@@ -446,13 +432,10 @@ template <bool FRESH>
 __device__ __forceinline__ void late_unit(int32_t *__restrict__ labels, const GridDesc &g,
                                           const ViewDesc *__restrict__ views, int nall, int32_t init, uint32_t unit,
                                           uint32_t bricks_y, uint32_t bricks_z, uint32_t lane) {
-    const uint32_t lb = unit >> 2, w = unit & 3u;
-    const uint32_t per_plane = bricks_y * bricks_z;
-    const uint32_t il = lb / per_plane;
-    const uint32_t rem = lb - il * per_plane;
-    const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
-    const int j0 = (int)(by * kBrickY), kb = (int)(bz * kBrickZ + w * 16u);  // 16 columns x 16 voxels
-    const uint32_t j = (uint32_t)j0 + (lane >> 2), k0 = (uint32_t)kb + (lane & 3u) * 4u;
+    const UnitAt at = unit_at(unit, bricks_y, bricks_z);  // 16 columns x 16 voxels
+    const uint32_t il = at.il;
+    const int j0 = (int)at.j0, kb = (int)at.kb;
+    const uint32_t j = at.j0 + (lane >> 2), k0 = at.kb + (lane & 3u) * 4u;
     const bool inside = j < g.ny && k0 < g.nz;
     const int nvalid = inside ? (int)min(4u, g.nz - k0) : 0;
     int32_t *p = labels + ((uint64_t)il * g.ny + j) * g.nzp + k0;  // the pitch is a multiple of 64: 16-byte groups
@@ -475,7 +458,7 @@ __device__ __forceinline__ void late_unit(int32_t *__restrict__ labels, const Gr
         alive[e] = __ballot(lab[e] != -1);  // :67
         kept[e] = 0;
     }
-    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;  // :71, global plane index
+    const float x = plane_x(g, il);
     const float y = g.oy + (float)(int)j * g.vs;
     float z[4];
 #pragma unroll
@@ -556,13 +539,10 @@ struct SecondWord {
 // so the caller loads it once; the special kernel has the registers: 94 of the 128 that four wavefronts per SIMD allow)
 __device__ __forceinline__ void unit_verdicts(const UnitJob &uj, const GridDesc &g, ListCtl *ctl, uint32_t unit,
                                               uint32_t sub, uint32_t lane, const SecondWord &second, const ViewDesc &first) {
-    const uint32_t lb = unit >> 2, w = unit & 3u;
-    const uint32_t per_plane = uj.bricks_y * uj.bricks_z;
-    const uint32_t il = lb / per_plane;
-    const uint32_t rem = lb - il * per_plane;
-    const uint32_t by = rem / uj.bricks_z, bz = rem - by * uj.bricks_z;
-    const int j0 = (int)(by * kBrickY), kb = (int)(bz * kBrickZ + w * 16u);  // 16 columns x 16 voxels
-    const uint32_t j = (uint32_t)j0 + (lane >> 2), k0 = (uint32_t)kb + (lane & 3u) * 4u;
+    const UnitAt at = unit_at(unit, uj.bricks_y, uj.bricks_z);  // 16 columns x 16 voxels
+    const uint32_t il = at.il;
+    const int j0 = (int)at.j0, kb = (int)at.kb;
+    const uint32_t j = at.j0 + (lane >> 2), k0 = at.kb + (lane & 3u) * 4u;
     const bool inside = j < g.ny && k0 < g.nz;
     const int nvalid = inside ? (int)min(4u, g.nz - k0) : 0;
     const uint32_t elem = (il * g.ny + j) * g.nzp + k0;
@@ -570,7 +550,7 @@ __device__ __forceinline__ void unit_verdicts(const UnitJob &uj, const GridDesc 
     // (the labels are asked for here and looked at behind the verdict round: one memory round trip, not two in a row)
     int4 q = make_int4(-1, -1, -1, -1);  // what a lane does not own counts as carved
     if (inside) q = *reinterpret_cast<const int4 *>(p);
-    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;  // :71, global plane index
+    const float x = plane_x(g, il);
     unsigned long long need[2] = {0ull, second.need};
     bool seen = second.full != 0, empty = second.empty != 0;
     {
@@ -720,19 +700,7 @@ __global__ __launch_bounds__(64 * kFlagWaves) void carve_special_kernel(int32_t 
         const uint32_t nl = sj.lb.late != nullptr ? 4u * ctl->nlate_units : 0u;
         const uint32_t total = nb + nl;
         if (total != 0u) {
-            if (tid < kSub) upref[tid + 1] = mine;
-            if (tid == 0) upref[0] = 0;
-            __syncthreads();
-            for (uint32_t off = 1; off < kSub; off <<= 1) {
-                uint32_t val = 0, add = 0;
-                if (tid < kSub) {
-                    val = upref[tid + 1];
-                    add = (tid >= off) ? upref[tid + 1 - off] : 0u;
-                }
-                __syncthreads();
-                if (tid < kSub) upref[tid + 1] = val + add;
-                __syncthreads();
-            }
+            scan_sublists<true>(upref, mine, tid);
             // A wavefront asks the first 64 views about a unit in one round, a view per lane; the views behind them -- 8 of
             // a batch of 72 -- would fill an eighth of a second round, so that round is asked for G = 64 / (nall - 64)
             // units at once (lane = unit slot * (nall - 64) + view - 64), ahead of the units' own rounds: 1 1/8 verdict
@@ -756,11 +724,7 @@ __global__ __launch_bounds__(64 * kFlagWaves) void carve_special_kernel(int32_t 
                 // unit i: one of the bulk list's (the first nb), or unit (i - nb) & 3 of a failed candidate
                 uint32_t my_unit = 0u, lo = 0u;
                 if (has && i < nb) {
-                    uint32_t hi = kSub;  // largest s with upref[s] <= i (per lane: the lanes of a slot agree)
-                    while (hi - lo > 1) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (upref[mid] <= i) lo = mid; else hi = mid;
-                    }
+                    lo = sublist_of(upref, i);  // (per lane: the lanes of a slot agree)
                     my_unit = sj.uj.units[(size_t)lo * sj.uj.cap + (i - upref[lo])];
                 } else if (has) {
                     const uint32_t lbq = sj.lb.late[nbricks_all - 1u - ((i - nb) >> 2)];
@@ -771,12 +735,9 @@ __global__ __launch_bounds__(64 * kFlagWaves) void carve_special_kernel(int32_t 
                 if (has && per1) {
                     const int vi = 64 + (int)(lane - slot * per1);
                     const ViewDesc d = sj.uj.views[vi];  // one descriptor per lane
-                    const uint32_t lb = my_unit >> 2, w = my_unit & 3u;
-                    const uint32_t per_plane = sj.uj.bricks_y * sj.uj.bricks_z;
-                    const uint32_t il = lb / per_plane, rem = lb - il * per_plane;
-                    const uint32_t by = rem / sj.uj.bricks_z, bz = rem - by * sj.uj.bricks_z;
-                    const int j0 = (int)(by * kBrickY), kb = (int)(bz * kBrickZ + w * 16u);
-                    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;
+                    const UnitAt at = unit_at(my_unit, sj.uj.bricks_y, sj.uj.bricks_z);
+                    const int j0 = (int)at.j0, kb = (int)at.kb;
+                    const float x = plane_x(g, at.il);
                     v1 = d.cmask != nullptr ? rect_verdict_cells(d, g, x, j0, j0 + kBrickY - 1, kb, kb + 15) : 0u;
                 }
                 const unsigned long long e1 = __ballot(v1 == 1u), f1 = __ballot(v1 == 2u), n1 = __ballot(v1 == 0u);
@@ -806,7 +767,6 @@ __global__ __launch_bounds__(64 * kFlagWaves) void carve_special_kernel(int32_t 
     // bricks whatever their state; settled bricks (their fill comes with the list kernels' store blocks, which run
     // whatever the flag says) and late bricks (above, over ALL views, perhaps by a block that has not written
     // them yet) are not this pass's voxels.
-    const Append none{nullptr, nullptr, 0u, 0u, nullptr, 0u, 0u};
     const uint64_t nblk = (g.ngroups + kThreads - 1) / kThreads;
     for (uint64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const uint64_t grp = blk * kThreads + tid;
@@ -821,7 +781,7 @@ __global__ __launch_bounds__(64 * kFlagWaves) void carve_special_kernel(int32_t 
         // (a wavefront's lanes leave carve_group's view loop together: skipped lanes still vote)
         if (!skip) {
             const int4 pre = *reinterpret_cast<const int4 *>(labels + grp * 4);
-            carve_group<false>(labels, g, sj.rest, sj.nrest, 0, grp, pre, none);
+            carve_group<false>(labels, g, sj.rest, sj.nrest, 0, grp, pre, Append{});
         }
     }
 }

@@ -1,5 +1,5 @@
 // Part of spacecarve.hip (included there, inside its anonymous namespace, in this order: sc_types, sc_project,
-// sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- block placement, the exact shared-reciprocal division, project() (backprojection.c:3-34), mask words, unravel_index (common.h:1-12).
+// sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- block placement, the exact shared-reciprocal division, project() (backprojection.c:3-34), mask words, a plane's x (plane_x), unravel_index (common.h:1-12).
 
 // XCD-aware block remap.  Blocks b and b+8 share an XCD (round-robin dispatch); runs of
 // kXcdRun consecutive logical blocks (neighbouring columns, which project onto the same mask
@@ -167,6 +167,10 @@ struct Vox4 {
     float x, y;
 };
 
+// x of the voxel centres of the engine's plane il: backprojection.c:71 -- origin + (float)index * voxel_size, with the
+// GLOBAL x index of the plane.  The casts in this order, unsigned -> int -> float, are part of the parity contract.
+__device__ __forceinline__ float plane_x(const GridDesc &g, uint32_t il) { return g.ox + (float)(int)(il * g.istride + g.i0) * g.vs; }
+
 // group index -> column and z run (common.h:6-8: z fastest), voxel centre x, y
 __device__ __forceinline__ void decode_group(const GridDesc &g, uint64_t grp, Vox4 &vx) {
     uint32_t col, kq;
@@ -183,7 +187,6 @@ __device__ __forceinline__ void decode_group(const GridDesc &g, uint64_t grp, Vo
     vx.k0 = kq * 4u;
     vx.nvalid = vx.k0 < g.nz ? min(4u, g.nz - vx.k0) : 0u;
     vx.elem = (uint64_t)col * g.nzp + vx.k0;  // == grp * 4: rows are whole groups
-    // backprojection.c:71-72 -- origin + (float)index * voxel_size, GLOBAL x index of the plane
-    vx.x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;
-    vx.y = g.oy + (float)(int)j * g.vs;
+    vx.x = plane_x(g, il);
+    vx.y = g.oy + (float)(int)j * g.vs;  // :72
 }

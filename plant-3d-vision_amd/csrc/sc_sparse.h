@@ -151,11 +151,10 @@ __global__ __launch_bounds__(kBlock) void sparse_pack_kernel(const int32_t *__re
                 if (mine >= hdr.nbricks) mine = 0xffffffffu;
             }
             if (mine != 0xffffffffu) {
-                const uint32_t il = mine / per_plane, rem = mine - il * per_plane;
-                const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
-                j0 = by * kBrickY;
-                kb = bz * kBrickZ;
-                const uint64_t off = ((uint64_t)il * g.ny + j0) * g.nzp + kb;
+                const BrickAt at = brick_in_plane(mine, per_plane, bricks_z);
+                j0 = at.by * kBrickY;
+                kb = at.bz * kBrickZ;
+                const uint64_t off = ((uint64_t)at.il * g.ny + j0) * g.nzp + kb;
                 off_lo = (uint32_t)off;
                 off_hi = (uint32_t)(off >> 32);
             }
@@ -269,11 +268,9 @@ struct SparseIn {
 template <typename OUT, bool OCC>
 __device__ __forceinline__ void sparse_put_brick(const SparseIn &in, OUT *__restrict__ out, uint32_t r, uint32_t first,
                                                  uint32_t stride, uint32_t b, uint32_t word, uint32_t lane) {
-    const uint32_t per_plane = in.bricks_y * in.bricks_z;
-    const uint32_t il = b / per_plane, rem = b - il * per_plane;
-    const uint32_t by = rem / in.bricks_z, bz = rem - by * in.bricks_z;
-    const uint32_t i = first + il * stride;
-    const uint32_t j = by * kBrickY + (lane >> 2), k0 = bz * kBrickZ + (lane & 3u) * 16u;
+    const BrickAt at = brick_at(b, in.bricks_y, in.bricks_z);
+    const uint32_t i = first + at.il * stride;
+    const uint32_t j = at.by * kBrickY + (lane >> 2), k0 = at.bz * kBrickZ + (lane & 3u) * 16u;
     if (i >= in.nx || j >= in.ny || k0 >= in.nz) return;
     auto decode = [](uint32_t lab) -> uint32_t {  // the output element as its bit pattern
         return OCC ? (lab == 1u ? 1u : 0u) : (lab == 3u ? (sizeof(OUT) == 1 ? 0xffu : 0xffffffffu) : lab);

@@ -2,17 +2,17 @@
 // sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- where survivors go (Append), carve_group and the dense kernel without bricks (backprojection.c:57-84).
 
 // Where a fused launch appends the voxels that are still alive after its dense views.
-struct Append {
-    uint32_t *list;   // nullptr: no append
-    ListCtl *ctl;
-    uint32_t subcap;  // entries per sub-list
-    uint32_t sub;     // sub-list of this block
+struct Append {       // (Append{}: no append)
+    uint32_t *list = nullptr;   // nullptr: no append
+    ListCtl *ctl = nullptr;
+    uint32_t subcap = 0;  // entries per sub-list
+    uint32_t sub = 0;     // sub-list of this block
     // brick form: a wavefront's share of a brick (16 columns x 16 voxels, a UNIT) with at least `bulk_min`
     // voxels alive after the dense views goes on the bulk list as a whole instead of voxel by voxel
     // (unit_verdicts: the views are asked about the unit, one view per lane, before any projects its voxels)
-    uint32_t *bulk;   // nullptr: no such list
-    uint32_t bulkcap; // units per sub-list
-    uint32_t bulk_min;
+    uint32_t *bulk = nullptr;   // nullptr: no such list
+    uint32_t bulkcap = 0; // units per sub-list
+    uint32_t bulk_min = 0;
 };
 
 // carve (backprojection.c:57-84) of one 4-voxel group over views[0..nviews), state in

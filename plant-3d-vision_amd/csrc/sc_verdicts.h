@@ -1,5 +1,5 @@
 // Part of spacecarve.hip (included there, inside its anonymous namespace, in this order: sc_types, sc_project,
-// sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- bricks, the footprint bound of DESIGN.md 4b, tile- and cell-level verdicts, brick_flags_kernel.
+// sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- bricks and units and their numbering (brick_at, unit_at), the footprint bound of DESIGN.md 4b, tile- and cell-level verdicts, brick_flags_kernel.
 
 // ---- brick form of the dense stage -------------------------------------------------------
 // A block takes a BRICK of 16 columns (along y) x 64 voxels (along z) instead of 1024 consecutive
@@ -14,6 +14,30 @@
 // Any doubt -> no culling.  Measured on the 512^3 plant scene: 72 % of the bricks are culled
 // in the first view.
 constexpr int kBrickY = 16, kBrickZ = 64;
+// The number of a brick says where it lies: plane-major, then the brick row (along y), then the brick column (along
+// z).  Its first column is by * kBrickY, its first voxel bz * kBrickZ.
+struct BrickAt {
+    uint32_t il, by, bz;  // plane of the engine, brick row, brick column
+};
+// (per_plane = bricks_y * bricks_z, from a kernel that takes the product once, ahead of its loop or of a branch with a
+// decode on either side, where the compiler does not: sparse_pack_kernel, carve_brick_light_kernel)
+__device__ __forceinline__ BrickAt brick_in_plane(uint32_t lb, uint32_t per_plane, uint32_t bricks_z) {
+    const uint32_t il = lb / per_plane, rem = lb - il * per_plane;
+    const uint32_t by = rem / bricks_z;
+    return {il, by, rem - by * bricks_z};
+}
+__device__ __forceinline__ BrickAt brick_at(uint32_t lb, uint32_t bricks_y, uint32_t bricks_z) {
+    return brick_in_plane(lb, bricks_y * bricks_z, bricks_z);
+}
+// The number of a UNIT (a wavefront's share of a brick: its 16 columns, 16 voxels of each -- see Append) is
+// brick * 4 + quarter: first column j0, first voxel kb = the brick's + 16 * quarter.
+struct UnitAt {
+    uint32_t il, j0, kb;
+};
+__device__ __forceinline__ UnitAt unit_at(uint32_t unit, uint32_t bricks_y, uint32_t bricks_z) {
+    const BrickAt b = brick_at(unit >> 2, bricks_y, bricks_z);
+    return {b.il, b.by * kBrickY, b.bz * kBrickZ + (unit & 3u) * 16u};
+}
 
 // One lane per (view, brick).  A brick lies in one x-plane, so it is a planar rectangle: with
 // every corner in front of the camera its image is the convex hull of the images of its four
@@ -302,12 +326,9 @@ __global__ __launch_bounds__(64 * kFlagWaves) void brick_flags_kernel(
     // and this launch rewrites every flag instead of a memset on the stream)
     const bool isdead = inb && dead != nullptr && !dead_stale && dead[lb] != 0;
     const bool valid = inb && !isdead;
-    const uint32_t per_plane = bricks_y * bricks_z;
-    const uint32_t il = lb / per_plane;
-    const uint32_t rem = lb - il * per_plane;
-    const uint32_t by = rem / bricks_z, bz = rem - by * bricks_z;
-    const float x = g.ox + (float)(int)(il * g.istride + g.i0) * g.vs;
-    const int j0 = (int)(by * kBrickY), k0 = (int)(bz * kBrickZ);
+    const BrickAt at = brick_at(lb, bricks_y, bricks_z);
+    const float x = plane_x(g, at.il);
+    const int j0 = (int)(at.by * kBrickY), k0 = (int)(at.bz * kBrickZ);
     // round 0: the first `nviews` views, one per wavefront (more: strided)
     // `full`: every view so far keeps the brick as it is -- sees all of it over foreground (verdict 2) or
     // does not see it at all (4, OUTSIDE); `seen`: at least one of them was a 2, so a label 0 becomes 1
@@ -371,12 +392,11 @@ __global__ __launch_bounds__(64 * kFlagWaves) void brick_flags_kernel(
     // the bricks left go on the live list, one atomic per block
     const bool alive = valid && !gone && !kept;
     const unsigned long long m = __ballot(alive);
-    const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     if (m != 0) {
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(&ctl->nlive[parity], (uint32_t)__popcll(m));
         base = __shfl(base, 0);
-        if (alive) live[base + (uint32_t)__popcll(m & below)] = lb;
+        if (alive) live[base + lanes_below(m)] = lb;
     }
     // ... and, while later views are not packed yet (grid-uniform), the kept ones on the candidate list, whose 64-entry
     // groups the confirm kernel asks those views about with every lane at work (asked where they lie, a block of 64
@@ -388,7 +408,7 @@ __global__ __launch_bounds__(64 * kFlagWaves) void brick_flags_kernel(
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(&ctl->ncand[parity][sub].n, (uint32_t)__popcll(mc));
         base = __shfl(base, 0);
-        if (open) cands[(size_t)sub * cand_per * 64u + base + (uint32_t)__popcll(mc & below)] = lb;
+        if (open) cands[(size_t)sub * cand_per * 64u + base + lanes_below(mc)] = lb;
     }
     if (fill_list != nullptr) {  // launches whose dense kernel fills from a list (see carve_brick_light_kernel)
         const bool fillme = valid && (gone || kept);
@@ -397,9 +417,8 @@ __global__ __launch_bounds__(64 * kFlagWaves) void brick_flags_kernel(
             uint32_t base = 0;
             if (lane == 0) base = atomicAdd(&ctl->nfill[parity], (uint32_t)__popcll(mf));
             base = __shfl(base, 0);
-            const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
             // bit 31: kept whole (0 -> 1); bit 30: kept and unseen (nothing changes)
-            if (fillme) fill_list[base + (uint32_t)__popcll(mf & below)] = lb | (gone ? 0u : (saw ? 0x80000000u : 0x40000000u));
+            if (fillme) fill_list[base + lanes_below(mf)] = lb | (gone ? 0u : (saw ? 0x80000000u : 0x40000000u));
         }
     }
 }

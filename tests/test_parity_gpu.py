@@ -164,11 +164,12 @@ def test_failed_reservations_leave_no_holes_in_the_lists(gpu_device, device_mask
         e.close()
 
 
-@pytest.mark.parametrize("nviews", [6, 7, 10, 11, 13])
+@pytest.mark.parametrize("nviews", [6, 7, 10, 11, 13, 66, 72])
 @pytest.mark.parametrize("kind,shape", [("dense", (9, 32, 192)), ("plant", (12, 48, 128))])
 def test_bulk_units_whatever_the_number_of_list_stages(gpu_device, nviews, kind, shape):
     """Bulk units below the floor are taken by the FIRST survivor stage as they are; a batch short enough to have
-    only the final stage (<= 10 views) has no such stage and must have its units asked instead."""
+    only the final stage (<= 10 views) has no such stage and must have its units asked instead.  66 and 72 views:
+    the special kernel asks views 64 and up about several units in one round (2 views a unit: up to 32 units, 8: 8)."""
     sh, origin, vs, views = scene(shape, nviews, kind)
     want = oracle_c.carve(sh, origin, vs, views, nthreads=4)
     for floor in (None, 0):
