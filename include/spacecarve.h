@@ -532,6 +532,37 @@ const char *sc_masks_last_error(void);
 void sc_masks_release(void);
 
 /*
+ * The lens correction in front of the mask producer: plant3dvision/tasks/proc2d.py::Undistorted.f (:120-143) over
+ * plant3dvision/proc2d.py::undistort (:25-66) = cv2.undistort(img, A, dist, None) on the GPU, for V pictures of ONE
+ * camera.  rgb, rgb_out: uint8 [V][H][W][3]; K = fx, fy, cx, cy and dist = k1, k2, p1, p2, k3 as binary64 (a caller that
+ * follows the reference rounds them through float32 first: plant3dvision/camera.py:104-128 makes float32 arrays).
+ * Per output pixel (row i, column j), every operation IEEE binary64 in the order written, no contraction:
+ *   x = (j - cx) / fx, y = (i - cy) / fy, x2 = x x, y2 = y y, r2 = x2 + y2, _2xy = (2 x) y,
+ *   kr = 1 + ((k3 r2 + k2) r2 + k1) r2, xd = (x kr + p1 _2xy) + p2 (r2 + 2 x2), yd = (y kr + p1 (r2 + 2 y2)) + p2 _2xy,
+ *   u = fx xd + cx, v = fy yd + cy, iu = rint(32 u), iv = rint(32 v) (half to even).
+ * A pixel with u or v not finite or |iu|, |iv| >= 2^30 is unmapped: output (0, 0, 0), map entry (INT32_MIN, INT32_MIN).
+ * Otherwise sx = iu >> 5, sy = iv >> 5, a = iu & 31, b = iv & 31 and per channel, a tap outside the picture counting 0
+ * (and never read),  out = ((32-a)(32-b) p(sy,sx) + a(32-b) p(sy,sx+1) + (32-a)b p(sy+1,sx) + ab p(sy+1,sx+1) + 512) >> 10.
+ * Restates OpenCV's initUndistortRectifyMap (CV_16SC2, INTER_BITS 5) + remap(INTER_LINEAR, BORDER_CONSTANT 0) from its
+ * published algorithm: parity unpinned, with two deviations (the ray is evaluated directly per pixel, not by running
+ * sums along a row; sx, sy beyond +-32768 lie outside, no (short) wrap) -- DESIGN.md 17.
+ *
+ * Device pointers on both sides: the work is enqueued on hip_stream (NULL = the legacy default stream) and the call
+ * returns without waiting, so sc_masks_from_rgb on the same stream consumes rgb_out without a host wait.  A host
+ * pointer on either side is staged by the library and the call returns when rgb_out is complete.  map_out (host,
+ * [H][W][2] = iu, iv; may be NULL) is a diagnostic and makes the call wait.  The work buffer (the map, 8 bytes per
+ * pixel) is the library's, one per device, kept between calls, ordered across streams as sc_masks_from_rgb's are, given
+ * back by sc_undistort_release (the caller's current HIP device is left as it was).
+ * Judged before any device call (SC_ERR_INVALID): V, H, W >= 1, 3 H W < 2^31, non-NULL rgb / K / dist / rgb_out, all
+ * nine numbers finite, fx and fy non-zero, rgb and rgb_out must not overlap.
+ */
+int sc_undistort_rgb(const void *rgb, int rgb_on_device, int V, int H, int W, const double K[4] /* fx fy cx cy */,
+                     const double dist[5] /* k1 k2 p1 p2 k3 */, int device, void *hip_stream, void *rgb_out, int out_on_device,
+                     int32_t *map_out /* [H][W][2] iu, iv; may be NULL */);
+const char *sc_undistort_last_error(void);
+void sc_undistort_release(void);
+
+/*
  * The clustering of OrganSegmentation (plant3dvision/tasks/proc3d.py:419-521): what open3d's
  * cluster_dbscan(eps, min_points) computes for one cloud, on the GPU.  points: float64 [P][3]; labels_out: int32 [P],
  * cluster ids from 0, noise -1; nclusters_out (host, may be NULL): the number of clusters.  The rules, order-free:

@@ -132,6 +132,9 @@ _SIGNATURES = {
     "sc_masks_from_rgb": ("i", ["p", "i", "i", "i", "i", "i", "p", "d", "p", "i", "i", "p", "p", "i", "p"]),
     "sc_masks_last_error": ("s", []),
     "sc_masks_release": ("v", []),
+    "sc_undistort_rgb": ("i", ["p", "i", "i", "i", "i", "p", "p", "i", "p", "p", "i", "p"]),
+    "sc_undistort_last_error": ("s", []),
+    "sc_undistort_release": ("v", []),
     "sc_dbscan": ("i", ["p", "i", "q", "d", "q", "i", "p", "i", "p", "p"]),
     "sc_dbscan_last_error": ("s", []),
     "sc_dbscan_release": ("v", []),

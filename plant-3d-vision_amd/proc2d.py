@@ -1,4 +1,5 @@
-"""The geometric pipeline's mask producer on the device: RGB pictures -> dilated binary masks.
+"""The geometric pipeline's picture stages on the device: the lens correction (``undistort``, below the masks) and
+the mask producer, RGB pictures -> dilated binary masks.
 
 Mirror of what ``Masks.f`` does to one picture (``plant3dvision/tasks/proc2d.py:224-249`` over
 ``plant3dvision/proc2d.py:69-220``) -- float64 copy, ``rescale_intensity(out_range=(0, 1))``, the ``linear`` or
@@ -76,4 +77,70 @@ def masks_from_images(images, type="linear", parameters=(0, 1, 0), threshold=0.3
         raise ValueError("V, H and W must be at least 1")
     nat.check(b.call("sc_masks_from_rgb", nat.addr(images), 0, *args, int(device), 0, nat.addr(out), 0, 0),
               "sc_masks_from_rgb", "sc_masks_last_error")
+    return out
+
+
+def _camera_numbers(camera_mtx, distortion_vect):
+    """``(K = fx fy cx cy, dist = k1 k2 p1 p2 k3)`` as float64 arrays, widened as cv2 widens its arguments."""
+    mtx = np.asarray(camera_mtx, dtype=np.float64)
+    if mtx.shape != (3, 3):
+        raise ValueError("camera_mtx must be 3 x 3")
+    if mtx[0, 1] != 0 or mtx[1, 0] != 0 or mtx[2].tolist() != [0, 0, 1]:
+        raise ValueError("camera_mtx with a skew or a last row other than [0, 0, 1] takes the reference's CPU route")
+    d = np.asarray(distortion_vect, dtype=np.float64).reshape(-1)
+    if d.size < 4:
+        raise ValueError("distortion_vect must hold k1, k2, p1, p2 and optionally k3")
+    if np.any(d[5:] != 0):  # (a NaN there is refused as well)
+        raise ValueError("distortion models beyond k1, k2, p1, p2, k3 take the reference's CPU route")
+    dist = np.zeros(5, dtype=np.float64)
+    dist[:min(5, d.size)] = d[:5]
+    return np.array([mtx[0, 0], mtx[1, 1], mtx[0, 2], mtx[1, 2]], dtype=np.float64), dist
+
+
+def undistort(img, camera_mtx, distortion_vect, device=0):
+    """``plant3dvision.proc2d.undistort`` (:25-66), which is ``cv2.undistort(img, camera_mtx, distortion_vect, None)``,
+    for one picture or a batch of pictures of one camera, in one call of ``sc_undistort_rgb`` (``csrc/undistort.hip``).
+
+    img : NumPy ``uint8 [H, W, 3]`` or ``[V, H, W, 3]`` -> NumPy of the same shape; or a contiguous CUDA torch
+        ``uint8`` tensor of that shape -> a CUDA torch tensor on the same device, produced on torch's current stream
+        without a host wait (``masks_from_images`` takes it from there).
+    camera_mtx : 3 x 3 of any dtype, widened to float64 as cv2 does -- the reference passes float32 arrays
+        (``camera.camera_arrays_from_params``), so the values are the float32-rounded ones.  A skew or a last row other
+        than ``[0, 0, 1]`` raises ``ValueError``: the caller keeps the reference's route.
+    distortion_vect : ``k1, k2, p1, p2[, k3]``; longer vectors only if the further entries are zero.
+
+    PARITY UNPINNED: OpenCV is not available here, so the kernels restate its published algorithm
+    (``initUndistortRectifyMap``, ``CV_16SC2`` maps with 5 fraction bits, ``remap`` with ``INTER_LINEAR`` and a
+    constant 0 border) with two documented deviations: the ray of a pixel is evaluated directly, and source positions
+    beyond +-32768 lie outside.  There is no CPU path.
+    """
+    K, dist = _camera_numbers(camera_mtx, distortion_vect)
+    b = nat.backend()
+    is_tensor = not isinstance(img, np.ndarray) and hasattr(img, "data_ptr")
+    if is_tensor:
+        import torch
+        if img.dtype != torch.uint8 or not img.is_cuda or not img.is_contiguous():
+            raise ValueError("a tensor of pictures must be a contiguous CUDA uint8 tensor")
+        shape = tuple(int(s) for s in img.shape)
+    else:
+        img = np.asarray(img)
+        if img.dtype != np.uint8:
+            raise ValueError("pictures must be uint8 (float pictures take the reference's CPU route)")
+        shape = img.shape
+    if len(shape) not in (3, 4) or shape[-1] != 3:
+        raise ValueError("pictures must be [V, H, W, 3] or [H, W, 3] (RGB; RGBA and grey pictures take the reference's CPU route)")
+    if 0 in shape:
+        raise ValueError("V, H and W must be at least 1")
+    V, H, W = (1,) + tuple(shape[:2]) if len(shape) == 3 else tuple(shape[:3])
+    if is_tensor:
+        dev = img.device.index
+        out = torch.empty_like(img)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(b.call("sc_undistort_rgb", img.data_ptr(), 1, int(V), int(H), int(W), nat.addr(K), nat.addr(dist), int(dev),
+                         int(stream), out.data_ptr(), 1, 0), "sc_undistort_rgb", "sc_undistort_last_error")
+        return out
+    img = np.ascontiguousarray(img)
+    out = np.empty_like(img)
+    nat.check(b.call("sc_undistort_rgb", nat.addr(img), 0, int(V), int(H), int(W), nat.addr(K), nat.addr(dist), int(device), 0,
+                     nat.addr(out), 0, 0), "sc_undistort_rgb", "sc_undistort_last_error")
     return out

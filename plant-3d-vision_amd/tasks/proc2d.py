@@ -5,6 +5,9 @@ As with ``tasks/cl.py::voxels_run``, the task's *logic* -- read every picture, f
 output metadata -- is a plain function, ``masks_run``, without luigi / plantdb.  The reference runs ``Masks.f`` file
 by file; here pictures of equal size go to the device as one batch (every picture still has its own range).
 INTEGRATION.md has the lines a maintainer of the reference puts into ``Masks.run``.
+
+``undistorted_run`` is the same for the task in front of it, ``Undistorted`` (tasks/proc2d.py:26-143), around
+``proc2d.undistort``: pictures of one size and one camera make one batch.
 """
 import logging
 
@@ -14,6 +17,49 @@ logger = logging.getLogger(__name__)
 
 #: parameter defaults of the reference task (tasks/proc2d.py:207-211)
 MASKS_DEFAULTS = dict(type="linear", parameters=[0, 1, 0], threshold=0.3, dilation=0)
+
+
+def undistorted_run(image_files, camera_model_src="Colmap", upstream_task="ImagesFilesetExists", undistort_fn=None):
+    """The ``Undistorted.run`` / ``.f`` loop without luigi / plantdb (tasks/proc2d.py:90-143).
+
+    image_files : list of file-like objects (``.id``, ``.get_metadata``; pixels via ``cl.read_image``), uint8 RGB
+        pictures with their camera in the ``colmap_camera`` metadata (whatever ``camera_model_src`` put it there:
+        :106-113 happen before this loop).
+    undistort_fn : ``proc2d.undistort`` by default; an argument only, the CPU tests pass a function of theirs.
+
+    The reference corrects file by file; here the files of one picture shape and one camera go to the device as one
+    batch.  A file without ``colmap_camera`` is logged as an error and left out (:141-143).  Returns
+    ``[(id, picture, metadata), ...]`` in input order: ``metadata`` is the input file's with what ``f`` sets (:138)
+    over it (:116-118).
+    """
+    if undistort_fn is None:  # the product: the HIP kernels
+        from ..proc2d import undistort as undistort_fn
+    from ..camera import camera_arrays_from_params, camera_kwargs_from_images_metadata
+    from ..cl import read_image
+    logger.info(f"Processing a list of {len(image_files)} image files...")
+    groups, cameras = {}, {}  # files of one shape and one camera make one batch, in input order
+    pictures = [None] * len(image_files)
+    for q, fi in enumerate(image_files):
+        cam_kwargs = camera_kwargs_from_images_metadata(fi)
+        if cam_kwargs is None:
+            logger.error(f"Could not find a camera model in '{getattr(fi, 'filename', fi.id)}' metadata!")
+            continue
+        pictures[q] = np.asarray(read_image(fi))
+        camera_mtx, distortion_vect = camera_arrays_from_params(**cam_kwargs)
+        key = (pictures[q].shape, camera_mtx.tobytes(), distortion_vect.tobytes())
+        groups.setdefault(key, []).append(q)
+        cameras[key] = (camera_mtx, distortion_vect)
+    for key, members in groups.items():
+        out = undistort_fn(np.stack([pictures[q] for q in members]), *cameras[key])
+        for k, q in enumerate(members):
+            pictures[q] = out[k]
+    md = {"upstream_task": str(upstream_task), "Camera model source": str(camera_model_src)}
+    return [(fi.id, pictures[q], {**_file_metadata(fi), **md}) for q, fi in enumerate(image_files) if pictures[q] is not None]
+
+
+def _file_metadata(fi):
+    md = fi.get_metadata()
+    return dict(md) if md else {}
 
 
 def _plain_query(query):
