@@ -324,6 +324,28 @@ def check(rc, what, last_error="sc_last_error"):
     raise SpaceCarveError(msg)
 
 
+#: entry point of a device unit -> the error getter of that unit (each unit keeps its own last message)
+UNIT_ERRORS = {
+    "sc_vol2pcd": "sc_vol2pcd_last_error", "sc_vol2pcd_packed": "sc_vol2pcd_last_error", "sc_vol2pcd_class": "sc_vol2pcd_last_error",
+    "sc_label_points": "sc_label_points_last_error",
+    "sc_masks_from_rgb": "sc_masks_last_error",
+    "sc_undistort_rgb": "sc_undistort_last_error",
+    "sc_dbscan": "sc_dbscan_last_error",
+    "sc_eval_masks": "sc_eval_last_error", "sc_eval_voxels": "sc_eval_last_error",
+    "sc_select_classes": "sc_select_last_error",
+    "sc_nearest": "sc_nearest_last_error", "sc_nearest_confusion": "sc_nearest_last_error",
+}
+
+
+def unit_call(entry, *args, what=None):
+    """Call a device unit's ``entry`` and ``check`` its code against that unit's own error getter (reported as
+    ``what``, the entry unless given).  An entry that ``UNIT_ERRORS`` does not list is a ``KeyError``."""
+    getter = UNIT_ERRORS[entry]
+    rc = (_backend or backend()).call(entry, *args)
+    if rc != SC_OK:
+        check(rc, what or entry, getter)
+
+
 def addr(a):
     """Address of a C-contiguous ndarray's data."""
     assert a.flags["C_CONTIGUOUS"]
@@ -379,7 +401,6 @@ def host_workers(limit=8):
 
 def widen_i8(dst, src, workers=None):
     """``dst[...] = src`` (int8 -> int32, same shape) slab by slab on a few threads."""
-    import threading
     flat_d, flat_s = dst.reshape(-1), src.reshape(-1)
     n = flat_d.size
     workers = workers or host_workers()
@@ -403,7 +424,6 @@ class TouchedEmpty:
     needed."""
 
     def __init__(self, shape, dtype, threads=None):
-        import threading
         threads = threads or min(4, host_workers())  # first-touch faults do not scale past a few threads
         self._arr = np.empty(shape, dtype=dtype)
         flat = self._arr.reshape(-1)
@@ -1093,7 +1113,7 @@ class Engine:
         ``on_piece`` must release the interpreter lock for the overlap to happen (NumPy's loops do).
         ``pool``: a caller's ``ThreadPoolExecutor`` -- the pieces' futures are returned instead of waited for, so that
         the next volume's copy follows this one's at once (several labels: one PCIe link, no gap between them)."""
-        from concurrent.futures import ThreadPoolExecutor
+        from concurrent.futures import ThreadPoolExecutor, wait
         if out.dtype != self.dtype or out.size != int(np.prod(self.slab_shape)) or not out.flags["C_CONTIGUOUS"]:
             raise ValueError("output buffer has the wrong dtype/size/layout")
         flat = out.reshape(-1)
@@ -1106,8 +1126,8 @@ class Engine:
         own = pool is None
         if own:
             pool = ThreadPoolExecutor(max_workers=nw)
+        futs = []
         try:
-            futs = []
             for a in range(0, flat.size, step):
                 b = min(flat.size, a + step)
                 self.dev_download(flat[a:b], src + a * flat.itemsize)  # (blocks this thread, not the pool's)
@@ -1118,15 +1138,7 @@ class Engine:
             for f in futs:
                 f.result()
         except BaseException:
-            # nothing of this call may stay in flight into the caller's `out`, and no failed piece may stay on a slot
-            with state["lock"]:
-                for slot in state["busy"]:
-                    for f in slot:
-                        try:
-                            f.result()
-                        except BaseException:  # noqa: BLE001
-                            pass
-                    slot.clear()
+            wait(futs)  # nothing of this call may stay in flight into the caller's `out`
             raise
         finally:
             if own:

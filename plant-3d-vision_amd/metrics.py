@@ -115,10 +115,6 @@ class CompareMasks(SetMetrics):
         super(CompareMasks, self).__init__(MaskEvaluator(dilation_amount), groundtruth, prediction)
 
 
-def _is_tensor(a):
-    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
-
-
 def compare_mask_stacks(groundtruths, predictions, dilation_amount=0, device=0):
     """``MaskEvaluator.evaluate`` for ``n`` pictures in one call (``sc_eval_masks``).
 
@@ -126,14 +122,15 @@ def compare_mask_stacks(groundtruths, predictions, dilation_amount=0, device=0):
         of one device; tensors are read in place on torch's current stream.
     Returns the NumPy int64 array ``[n, 4]`` of ``tp, fn, tn, fp`` (the reference's order)."""
     from . import _native as nat
+    from ._operands import is_tensor
 
     k = int(dilation_amount)
     if k < 0:
         raise ValueError("dilation_amount must not be negative")
-    if _is_tensor(groundtruths) != _is_tensor(predictions):
+    if is_tensor(groundtruths) != is_tensor(predictions):
         raise ValueError("ground truths and predictions must both be NumPy arrays or both CUDA tensors")
-    b = nat.backend()
-    if _is_tensor(groundtruths):
+    nat.backend()
+    if is_tensor(groundtruths):
         import torch
         gt, pr = groundtruths, predictions
         for t in (gt, pr):
@@ -163,8 +160,7 @@ def compare_mask_stacks(groundtruths, predictions, dilation_amount=0, device=0):
         return counts[:0]
     if H == 0 or W == 0:
         raise ValueError("pictures must not be empty")
-    nat.check(b.call("sc_eval_masks", gptr, pptr, on_dev, n, H, W, min(k, 2 ** 31 - 1), dev, int(stream), nat.addr(counts)),
-              "sc_eval_masks", "sc_eval_last_error")
+    nat.unit_call("sc_eval_masks", gptr, pptr, on_dev, n, H, W, min(k, 2 ** 31 - 1), dev, int(stream), nat.addr(counts))
     return counts
 
 
@@ -191,7 +187,7 @@ def voxel_confusion(voxels, groundtruths, background="background", min_contrast=
     Returns ``{label: {"tp", "fp", "tn", "fn"}}`` (Python ints) for every label but the background -- the reference's
     ``histograms`` -- and with ``projections=True`` the pair ``(that, {label: uint8 [ny, nz]})``: 1 where some x of
     the column predicts the label (``prediction_c.max(0)``, :455)."""
-    from . import _native as nat
+    from . import _native as nat, _operands as ops
 
     labels = list(groundtruths.keys())
     L = len(labels)
@@ -202,61 +198,25 @@ def voxel_confusion(voxels, groundtruths, background="background", min_contrast=
     for label in labels:
         if label not in voxels:
             raise ValueError(f"label '{label}' of the ground truth is missing from the voxels")
+    refused = "device voxels must be float32 or float64, device ground truths float32, float64, uint8 or bool"
+    floats = (nat.SC_EVAL_F32, nat.SC_EVAL_F64)
     pred, gt = [voxels[label] for label in labels], [groundtruths[label] for label in labels]
-    tensors = [_is_tensor(v) for v in pred + gt]
-    if any(tensors) and not all(tensors):
+    if len({ops.is_tensor(v) for v in pred + gt}) > 1:  # (across both stacks, before either is judged)
         raise ValueError("volumes must be all NumPy arrays or all CUDA tensors")
+    p = ops.class_stack(pred, "voxels", floats, refused, device)
+    g = ops.class_stack(gt, "ground truths", floats + (nat.SC_EVAL_U8,), refused, device)
+    ops.same([p.tdevice, g.tdevice], "devices")
     bg = labels.index(background) if background in labels else -1
-    codes = {np.dtype(np.float32): nat.SC_EVAL_F32, np.dtype(np.float64): nat.SC_EVAL_F64, np.dtype(np.uint8): nat.SC_EVAL_U8}
-
-    def same(things, what):
-        if any(t != things[0] for t in things):
-            raise ValueError(f"the {what} differ: {sorted(set(str(t) for t in things))}")
-        return things[0]
-
-    if all(tensors):
-        import torch
-        tcodes = {torch.float32: nat.SC_EVAL_F32, torch.float64: nat.SC_EVAL_F64, torch.uint8: nat.SC_EVAL_U8, torch.bool: nat.SC_EVAL_U8}
-        for t in pred + gt:
-            if not t.is_cuda or not t.is_contiguous() or t.dim() != 3:
-                raise ValueError("device volumes must be contiguous 3-D CUDA tensors")
-        dev = same([t.device for t in pred + gt], "devices").index
-        pshape = same([tuple(int(s) for s in t.shape) for t in pred], "shapes of the voxels")
-        gshape = same([tuple(int(s) for s in t.shape) for t in gt], "shapes of the ground truths")
-        pdt, gdt = same([t.dtype for t in pred], "dtypes of the voxels"), same([t.dtype for t in gt], "dtypes of the ground truths")
-        if pdt not in (torch.float32, torch.float64) or gdt not in tcodes:
-            raise ValueError("device voxels must be float32 or float64, device ground truths float32, float64, uint8 or bool")
-        pcode, gcode = tcodes[pdt], tcodes[gdt]
-        pptr, gptr = [t.data_ptr() for t in pred], [t.data_ptr() for t in gt]
-        on_dev, stream = 1, torch.cuda.current_stream(dev).cuda_stream
-    else:
-        pred, gt = [np.asarray(v) for v in pred], [np.asarray(v) for v in gt]
-        pshape = same([v.shape for v in pred], "shapes of the voxels")
-        gshape = same([v.shape for v in gt], "shapes of the ground truths")
-        pdt, gdt = same([v.dtype for v in pred], "dtypes of the voxels"), same([v.dtype for v in gt], "dtypes of the ground truths")
-        if len(pshape) != 3 or len(gshape) != 3:
-            raise ValueError("volumes must be 3-D")
-        if pdt not in (np.float32, np.float64):
-            pred = [v.astype(np.float64) for v in pred]
-        if gdt == np.bool_:
-            gt = [v.view(np.uint8) for v in gt]
-        elif gdt not in codes:
-            gt = [v.astype(np.float64) for v in gt]
-        pred, gt = [np.ascontiguousarray(v) for v in pred], [np.ascontiguousarray(v) for v in gt]
-        pcode, gcode = codes[pred[0].dtype], codes[gt[0].dtype]
-        pptr, gptr = [nat.addr(v) for v in pred], [nat.addr(v) for v in gt]
-        dev, on_dev, stream = int(device), 0, 0
-    if any(g < p for g, p in zip(gshape, pshape)):
+    pshape, gshape = p.shape, g.shape
+    if any(gs < ps for gs, ps in zip(gshape, pshape)):
         raise ValueError(f"ground truth {gshape} smaller than the prediction {pshape}")
     if min(pshape) < 1:
         raise ValueError("volumes must not be empty")
-    pp, gp = np.array(pptr, dtype=np.uintp), np.array(gptr, dtype=np.uintp)
     counts = np.zeros((L, 4), dtype=np.int64)
     proj = np.zeros((L, pshape[1], pshape[2]), dtype=np.uint8) if projections else None
-    nat.check(nat.backend().call("sc_eval_voxels", nat.addr(pp), pcode, nat.addr(gp), gcode, L, pshape[0], pshape[1], pshape[2],
-                                 gshape[0], gshape[1], gshape[2], bg, float(min_contrast), on_dev, dev, int(stream),
-                                 nat.addr(counts), nat.addr(proj) if projections else 0),
-              "sc_eval_voxels", "sc_eval_last_error")
+    nat.unit_call("sc_eval_voxels", nat.addr(p.table), p.code, nat.addr(g.table), g.code, L, pshape[0], pshape[1], pshape[2],
+                  gshape[0], gshape[1], gshape[2], bg, float(min_contrast), p.on_device, p.device, p.stream,
+                  nat.addr(counts), nat.addr(proj) if projections else 0)
     out = {label: {"tp": int(counts[q, 0]), "fp": int(counts[q, 1]), "tn": int(counts[q, 2]), "fn": int(counts[q, 3])}
            for q, label in enumerate(labels) if q != bg}
     if projections:
@@ -305,10 +265,11 @@ def _device_tables(source, source_ids, target, target_ids, n_labels, device=0):
     """The product's table function: ``counts[a, b]`` = source points of label id ``a`` whose nearest target point has
     label id ``b``, by ``sc_nearest`` and ``sc_nearest_confusion``.  With CUDA tensors as points the indices stay on
     the device and the label ids are sent there."""
+    from ._operands import is_tensor
     from .proc3d import nearest_confusion, nearest_points
 
     index, _ = nearest_points(source, target, None, device=device)
-    if _is_tensor(index):
+    if is_tensor(index):
         import torch
         source_ids = torch.from_numpy(np.ascontiguousarray(source_ids, dtype=np.int32)).to(index.device)
         target_ids = torch.from_numpy(np.ascontiguousarray(target_ids, dtype=np.int32)).to(index.device)

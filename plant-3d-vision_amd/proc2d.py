@@ -14,6 +14,7 @@ There is no CPU path: pictures that are not uint8 RGB are refused and the caller
 import numpy as np
 
 from . import _native as nat
+from . import _operands as ops
 from .masks2d import disk_series
 
 #: filter names of ``Masks.type`` (tasks/proc2d.py:217-222) -> SC_FILTER_*
@@ -43,40 +44,13 @@ def masks_from_images(images, type="linear", parameters=(0, 1, 0), threshold=0.3
         raise ValueError("parameters must be the three linear coefficients")
     dilation = int(dilation)
     steps = dilation_steps(dilation) if dilation > 0 else np.zeros(0, dtype=np.uint8)
-    b = nat.backend()
-    is_tensor = not isinstance(images, np.ndarray) and hasattr(images, "data_ptr")
-    if is_tensor:
-        import torch
-        if images.dtype != torch.uint8 or not images.is_cuda or not images.is_contiguous():
-            raise ValueError("a tensor of pictures must be a contiguous CUDA uint8 tensor")
-        shape = tuple(int(s) for s in images.shape)
-    else:
-        images = np.asarray(images)
-        if images.dtype != np.uint8:
-            raise ValueError("pictures must be uint8 (float pictures take the reference's CPU route)")
-        shape = images.shape
-    single = len(shape) == 3
-    if len(shape) not in (3, 4) or shape[-1] != 3:
-        raise ValueError("pictures must be [V, H, W, 3] or [H, W, 3] (RGB; RGBA and grey pictures take the reference's CPU route)")
-    V, H, W = (1,) + tuple(shape[:2]) if single else tuple(shape[:3])
-    args = (int(V), int(H), int(W), FILTERS[type], nat.addr(coefs), float(threshold),
-            nat.addr(steps) if steps.size else 0, int(steps.size))
-    if is_tensor:
-        import torch
-        dev = images.device.index
-        out = torch.empty((H, W) if single else (V, H, W), dtype=torch.uint8, device=images.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if images.numel() == 0:
-            raise ValueError("V, H and W must be at least 1")
-        nat.check(b.call("sc_masks_from_rgb", images.data_ptr(), 1, *args, int(dev), int(stream), out.data_ptr(), 1, 0),
-                  "sc_masks_from_rgb", "sc_masks_last_error")
-        return out
-    images = np.ascontiguousarray(images)
-    out = np.empty((H, W) if single else (V, H, W), dtype=np.uint8)
-    if images.size == 0:
+    nat.backend()
+    p = ops.picture_batch(images, device)
+    out = ops.empty_uint8(p.shape[:-1], p.tdevice)
+    if 0 in p.shape:  # (an empty batch is refused once its output exists)
         raise ValueError("V, H and W must be at least 1")
-    nat.check(b.call("sc_masks_from_rgb", nat.addr(images), 0, *args, int(device), 0, nat.addr(out), 0, 0),
-              "sc_masks_from_rgb", "sc_masks_last_error")
+    nat.unit_call("sc_masks_from_rgb", p.ptr, p.on_device, *p.vhw, FILTERS[type], nat.addr(coefs), float(threshold),
+                  nat.addr(steps) if steps.size else 0, int(steps.size), p.device, p.stream, ops.ptr_of(out), p.on_device, 0)
     return out
 
 
@@ -115,32 +89,11 @@ def undistort(img, camera_mtx, distortion_vect, device=0):
     beyond +-32768 lie outside.  There is no CPU path.
     """
     K, dist = _camera_numbers(camera_mtx, distortion_vect)
-    b = nat.backend()
-    is_tensor = not isinstance(img, np.ndarray) and hasattr(img, "data_ptr")
-    if is_tensor:
-        import torch
-        if img.dtype != torch.uint8 or not img.is_cuda or not img.is_contiguous():
-            raise ValueError("a tensor of pictures must be a contiguous CUDA uint8 tensor")
-        shape = tuple(int(s) for s in img.shape)
-    else:
-        img = np.asarray(img)
-        if img.dtype != np.uint8:
-            raise ValueError("pictures must be uint8 (float pictures take the reference's CPU route)")
-        shape = img.shape
-    if len(shape) not in (3, 4) or shape[-1] != 3:
-        raise ValueError("pictures must be [V, H, W, 3] or [H, W, 3] (RGB; RGBA and grey pictures take the reference's CPU route)")
-    if 0 in shape:
+    nat.backend()
+    p = ops.picture_batch(img, device)
+    if 0 in p.shape:
         raise ValueError("V, H and W must be at least 1")
-    V, H, W = (1,) + tuple(shape[:2]) if len(shape) == 3 else tuple(shape[:3])
-    if is_tensor:
-        dev = img.device.index
-        out = torch.empty_like(img)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        nat.check(b.call("sc_undistort_rgb", img.data_ptr(), 1, int(V), int(H), int(W), nat.addr(K), nat.addr(dist), int(dev),
-                         int(stream), out.data_ptr(), 1, 0), "sc_undistort_rgb", "sc_undistort_last_error")
-        return out
-    img = np.ascontiguousarray(img)
-    out = np.empty_like(img)
-    nat.check(b.call("sc_undistort_rgb", nat.addr(img), 0, int(V), int(H), int(W), nat.addr(K), nat.addr(dist), int(device), 0,
-                     nat.addr(out), 0, 0), "sc_undistort_rgb", "sc_undistort_last_error")
+    out = ops.empty_uint8(p.shape, p.tdevice)
+    nat.unit_call("sc_undistort_rgb", p.ptr, p.on_device, *p.vhw, nat.addr(K), nat.addr(dist), p.device, p.stream,
+                  ops.ptr_of(out), p.on_device, 0)
     return out

@@ -40,17 +40,18 @@ def gaussian_weights(sigma=1.0, truncate=4.0):
     return np.ascontiguousarray(phi[radius:], dtype=np.float64)
 
 
+#: what ``release_device_buffers`` calls, in this order
+RELEASES = ("sc_vol2pcd_release", "sc_dbscan_release", "sc_eval_release", "sc_select_release", "sc_nearest_release")
+
+
 def release_device_buffers():
     """Give back the device work buffers ``vol2pcd`` keeps between calls (``sc_vol2pcd_release``; it keeps them
     only while they are at most 1 GiB), those of ``cluster_dbscan`` (``sc_dbscan_release``), those of the
     evaluation counts of ``metrics`` (``sc_eval_release``), those of ``select_classes`` (``sc_select_release``) and
     those of ``nearest_points`` and the cloud metrics (``sc_nearest_release``).  ``Backprojection.close`` calls this."""
     from . import _native as nat
-    nat.backend().call("sc_vol2pcd_release")
-    nat.backend().call("sc_dbscan_release")
-    nat.backend().call("sc_eval_release")
-    nat.backend().call("sc_select_release")
-    nat.backend().call("sc_nearest_release")
+    for entry in RELEASES:
+        nat.backend().call(entry)
 
 
 def set_scratch_limit(nbytes):
@@ -165,14 +166,9 @@ def _vol2pcd_call(entry, head, shape, device, origin64, voxel_size, level_set_va
     assert gw.size == 5
     out = np.zeros(2, dtype=np.uintp)
     cnt = np.zeros(1, dtype=np.int64)
-    rc = b.call(entry, *head, shape[0], shape[1], shape[2], nat.addr(origin64), float(voxel_size), float(level_set_value),
-                nat.addr(gw), int(device), nat.addr(out), nat.addr(out) + 8, nat.addr(cnt))
-    nat.check(rc, what or entry, "sc_vol2pcd_last_error")
+    nat.unit_call(entry, *head, shape[0], shape[1], shape[2], nat.addr(origin64), float(voxel_size), float(level_set_value),
+                  nat.addr(gw), int(device), nat.addr(out), nat.addr(out) + 8, nat.addr(cnt), what=what)
     return _adopt_cloud(b, out, cnt, as_open3d)
-
-
-def _is_tensor(a):
-    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
 
 
 def set_select_chunk_bytes(nbytes):
@@ -197,7 +193,7 @@ def select_classes(voxels, background_prior=1.0, min_contrast=10.0, min_score=0.
     the voxel belongs to, 255 for none; the reference's volume of class ``c`` is ``winner == c`` -- a NumPy array, or a
     CUDA tensor on the inputs' device; ``labels = list(voxels.keys())``; ``counts`` int64 ``[L]``, the voxels of each
     class (0 for the background)."""
-    from . import _native as nat
+    from . import _native as nat, _operands as ops
 
     labels = list(voxels.keys())
     L = len(labels)
@@ -205,56 +201,15 @@ def select_classes(voxels, background_prior=1.0, min_contrast=10.0, min_score=0.
         raise ValueError("at least two classes are needed (with one key the reference takes its single-volume branch)")
     if L > 32:
         raise ValueError("at most 32 classes")
-    vols = [voxels[label] for label in labels]
-    tensors = [_is_tensor(v) for v in vols]
-    if any(tensors) and not all(tensors):
-        raise ValueError("volumes must be all NumPy arrays or all CUDA tensors")
+    s = ops.class_stack([voxels[label] for label in labels], "voxels", (nat.SC_EVAL_F32, nat.SC_EVAL_F64, nat.SC_EVAL_U8),
+                        "device volumes must be float32, float64, uint8 or bool", device)
+    if min(s.shape) < 1:
+        raise ValueError("volumes must not be empty")
     bg = labels.index(background) if background in labels else -1
-    codes = {np.dtype(np.float32): nat.SC_EVAL_F32, np.dtype(np.float64): nat.SC_EVAL_F64, np.dtype(np.uint8): nat.SC_EVAL_U8}
-
-    def same(things, what):
-        if any(t != things[0] for t in things):
-            raise ValueError(f"the {what} differ: {sorted(set(str(t) for t in things))}")
-        return things[0]
-
-    if all(tensors):
-        import torch
-        tcodes = {torch.float32: nat.SC_EVAL_F32, torch.float64: nat.SC_EVAL_F64, torch.uint8: nat.SC_EVAL_U8, torch.bool: nat.SC_EVAL_U8}
-        for t in vols:
-            if not t.is_cuda or not t.is_contiguous() or t.dim() != 3:
-                raise ValueError("device volumes must be contiguous 3-D CUDA tensors")
-        tdev = same([t.device for t in vols], "devices")
-        shape = same([tuple(int(s) for s in t.shape) for t in vols], "shapes of the voxels")
-        dt = same([t.dtype for t in vols], "dtypes of the voxels")
-        if dt not in tcodes:
-            raise ValueError("device volumes must be float32, float64, uint8 or bool")
-        if min(shape) < 1:
-            raise ValueError("volumes must not be empty")
-        code, dev, on_dev = tcodes[dt], tdev.index, 1
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        winner = torch.empty(shape, dtype=torch.uint8, device=tdev)
-        ptrs, wptr = [t.data_ptr() for t in vols], winner.data_ptr()
-    else:
-        vols = [np.asarray(v) for v in vols]
-        shape = same([v.shape for v in vols], "shapes of the voxels")
-        dt = same([v.dtype for v in vols], "dtypes of the voxels")
-        if len(shape) != 3:
-            raise ValueError("volumes must be 3-D")
-        if min(shape) < 1:
-            raise ValueError("volumes must not be empty")
-        if dt == np.bool_:
-            vols = [v.view(np.uint8) for v in vols]
-        elif dt not in codes:
-            vols = [v.astype(np.float64) for v in vols]
-        vols = [np.ascontiguousarray(v) for v in vols]
-        code, dev, on_dev, stream = codes[vols[0].dtype], int(device), 0, 0
-        winner = np.empty(shape, dtype=np.uint8)
-        ptrs, wptr = [nat.addr(v) for v in vols], nat.addr(winner)
-    pp = np.array(ptrs, dtype=np.uintp)
+    winner = ops.empty_uint8(s.shape, s.tdevice)
     counts = np.zeros(L, dtype=np.int64)
-    nat.check(nat.backend().call("sc_select_classes", nat.addr(pp), code, L, bg, shape[0], shape[1], shape[2], float(background_prior),
-                                 float(min_contrast), float(min_score), on_dev, dev, int(stream), wptr, nat.addr(counts)),
-              "sc_select_classes", "sc_select_last_error")
+    nat.unit_call("sc_select_classes", nat.addr(s.table), s.code, L, bg, s.shape[0], s.shape[1], s.shape[2], float(background_prior),
+                  float(min_contrast), float(min_score), s.on_device, s.device, s.stream, ops.ptr_of(winner), nat.addr(counts))
     return winner, labels, counts
 
 
@@ -265,11 +220,11 @@ def vol2pcd_class(winner, index, origin, voxel_size, level_set_value=0, device=0
     winner : uint8 ``[nx, ny, nz]``, what ``select_classes`` returns: a NumPy array, or a contiguous CUDA torch tensor
         read in place (it never leaves the device; only points and normals come back).
     index : the class, 0..255 (255: the voxels of no class)."""
-    from . import _native as nat
+    from . import _native as nat, _operands as ops
 
     nat.backend()
     origin64 = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(3))  # judged before the volume
-    if _is_tensor(winner):
+    if ops.is_tensor(winner):
         import torch
         if winner.dtype != torch.uint8 or winner.dim() != 3 or not winner.is_contiguous() or not winner.is_cuda:
             raise ValueError("a device winner volume must be a contiguous uint8 CUDA tensor [nx, ny, nz]")
@@ -303,16 +258,16 @@ def label_points(points, cameras, masks, device=0):
     Returns ``(labels int32 [P], scores float64 [L, P])``; ``labels[i]`` indexes the L labels in
     the order given (the reference iterates a Python ``set``; fix the order yourself).
     """
-    from . import _native as nat
+    from . import _native as nat, _operands as ops
 
-    b = nat.backend()
+    nat.backend()
     pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
     P = pts.shape[0]
     V = len(cameras)
     K = np.ascontiguousarray(np.array([c["camera_model"]["params"][0:4] for c in cameras], dtype=np.float64).reshape(V, 4))
     R = np.ascontiguousarray(np.array([c["rotmat"] for c in cameras], dtype=np.float64).reshape(V, 9))
     t = np.ascontiguousarray(np.array([c["tvec"] for c in cameras], dtype=np.float64).reshape(V, 3))
-    if hasattr(masks, "data_ptr"):  # torch tensor on the device
+    if ops.is_tensor(masks):  # torch tensor on the device
         import torch
         if masks.dtype != torch.uint8 or masks.dim() != 4 or not masks.is_contiguous() or not masks.is_cuda:
             raise ValueError("device masks must be a contiguous uint8 CUDA tensor [L, V, H, W]")
@@ -329,9 +284,8 @@ def label_points(points, cameras, masks, device=0):
         raise ValueError("one camera per view")
     scores = np.zeros((L, P), dtype=np.float64)
     labels = np.zeros(P, dtype=np.int32)
-    rc = b.call("sc_label_points", nat.addr(pts), P, L, V, nat.addr(K), nat.addr(R), nat.addr(t), mptr, on_dev,
-                H, W, int(device), nat.addr(scores), nat.addr(labels))
-    nat.check(rc, "sc_label_points", "sc_label_points_last_error")
+    nat.unit_call("sc_label_points", nat.addr(pts), P, L, V, nat.addr(K), nat.addr(R), nat.addr(t), mptr, on_dev,
+                  H, W, int(device), nat.addr(scores), nat.addr(labels))
     return labels, scores
 
 
@@ -350,55 +304,21 @@ def cluster_dbscan(points, eps, min_points, device=0):
     clusters = connected components of the core points, a border point joins the smallest id among its core
     neighbours.  Deviation: non-finite coordinates (and ``eps`` that is not finite and positive) raise ``ValueError``.
     """
-    from . import _native as nat
+    from . import _native as nat, _operands as ops
 
-    b = nat.backend()
-
-    if not isinstance(points, np.ndarray) and hasattr(points, "points"):
-        points = points.points
-    if not isinstance(points, np.ndarray) and hasattr(points, "data_ptr"):  # torch tensor on the device
+    nat.backend()
+    p = ops.points(points, "points", "[P, 3]")
+    P = p.n
+    if p.on_device:
         import torch
-        if (points.dtype != torch.float64 or not points.is_cuda or not points.is_contiguous() or points.dim() != 2
-                or points.shape[1] != 3):
-            raise ValueError("device points must be a contiguous float64 CUDA tensor [P, 3]")
-        dev = points.device.index
-        P = int(points.shape[0])
-        out = torch.empty((P,), dtype=torch.int32, device=points.device)
+        out = torch.empty((P,), dtype=torch.int32, device=p.points.device)
         if P:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            nat.check(b.call("sc_dbscan", points.data_ptr(), 1, P, float(eps), int(min_points), int(dev), out.data_ptr(), 1, 0,
-                             int(stream)), "sc_dbscan", "sc_dbscan_last_error")
+            dev, stream = ops.tensor_place(p.points)
+            nat.unit_call("sc_dbscan", p.ptr, 1, P, float(eps), int(min_points), int(dev), out.data_ptr(), 1, 0, int(stream))
         return out
-    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
-    if pts.ndim != 2 or pts.shape[1] != 3:
-        if pts.size:
-            raise ValueError("points must be [P, 3]")
-        pts = pts.reshape(0, 3)
-    P = pts.shape[0]
     labels = np.full(max(P, 1), -1, dtype=np.int32)
-    keep = pts if P else np.zeros((1, 3))  # a valid address for an empty cloud
-    nat.check(b.call("sc_dbscan", nat.addr(keep), 0, P, float(eps), int(min_points), int(device), nat.addr(labels), 0, 0, 0),
-              "sc_dbscan", "sc_dbscan_last_error")
+    nat.unit_call("sc_dbscan", p.ptr, 0, P, float(eps), int(min_points), int(device), nat.addr(labels), 0, 0, 0)
     return labels[:P]
-
-
-def _cloud_points(cloud, what):
-    """``cloud`` as the search takes it: ``(kind, points)`` with kind ``"tensor"`` (a contiguous float64 CUDA tensor
-    ``[n, 3]``, used in place) or ``"array"`` (a C-contiguous float64 NumPy array ``[n, 3]``)."""
-    if not isinstance(cloud, np.ndarray) and hasattr(cloud, "points"):
-        cloud = cloud.points
-    if _is_tensor(cloud):
-        import torch
-        if (cloud.dtype != torch.float64 or not cloud.is_cuda or not cloud.is_contiguous() or cloud.dim() != 2
-                or cloud.shape[1] != 3):
-            raise ValueError(f"device {what} must be a contiguous float64 CUDA tensor [n, 3]")
-        return "tensor", cloud
-    pts = np.ascontiguousarray(np.asarray(cloud, dtype=np.float64))
-    if pts.ndim != 2 or pts.shape[1] != 3:
-        if pts.size:
-            raise ValueError(f"{what} must be [n, 3]")
-        pts = pts.reshape(0, 3)
-    return "array", pts
 
 
 def _max_distance_arg(max_distance):
@@ -414,37 +334,31 @@ def _max_distance_arg(max_distance):
 def _nearest_call(queries, targets, max_distance, device, want_points, want_sums):
     """One ``sc_nearest`` call: ``(index, d2, sums)``; ``index`` / ``d2`` are ``None`` without ``want_points``,
     ``sums`` (NumPy float64 ``[3]``: n, sum d2, sum sqrt d2) is ``None`` without ``want_sums``."""
-    from . import _native as nat
+    from . import _native as nat, _operands as ops
 
     md = _max_distance_arg(max_distance)
-    qkind, q = _cloud_points(queries, "queries")
-    tkind, t = _cloud_points(targets, "targets")
-    if qkind != tkind:
+    q, t = ops.points(queries, "queries"), ops.points(targets, "targets")
+    if q.on_device != t.on_device:
         raise ValueError("queries and targets must both be arrays (or clouds) or both CUDA tensors")
-    Q, P = int(q.shape[0]), int(t.shape[0])
+    Q, P = q.n, t.n
     sums = np.zeros(3, dtype=np.float64) if want_sums else None
     sptr = nat.addr(sums) if want_sums else 0
-    b = nat.backend()
-    if qkind == "tensor":
+    if q.on_device:
         import torch
-        if q.device != t.device:
+        if q.points.device != t.points.device:
             raise ValueError("queries and targets must be on one device")
-        dev = q.device.index
         index = d2 = None
         if want_points:
-            index = torch.full((Q,), -1, dtype=torch.int32, device=q.device)
-            d2 = torch.full((Q,), float("inf"), dtype=torch.float64, device=q.device)
+            index = torch.full((Q,), -1, dtype=torch.int32, device=q.points.device)
+            d2 = torch.full((Q,), float("inf"), dtype=torch.float64, device=q.points.device)
         if Q and P:  # rule N4 otherwise: the outputs are filled already
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            nat.check(b.call("sc_nearest", q.data_ptr(), 1, Q, t.data_ptr(), 1, P, md, int(dev), index.data_ptr() if want_points else 0,
-                             d2.data_ptr() if want_points else 0, 1, sptr, int(stream)), "sc_nearest", "sc_nearest_last_error")
+            dev, stream = ops.tensor_place(q.points)
+            nat.unit_call("sc_nearest", q.ptr, 1, Q, t.ptr, 1, P, md, int(dev), index.data_ptr() if want_points else 0,
+                          d2.data_ptr() if want_points else 0, 1, sptr, int(stream))
         return index, d2, sums
     index = np.full(max(Q, 1), -1, dtype=np.int32)
     d2 = np.full(max(Q, 1), np.inf, dtype=np.float64)
-    keep_q = q if Q else np.zeros((1, 3))  # valid addresses for empty clouds
-    keep_t = t if P else np.zeros((1, 3))
-    nat.check(b.call("sc_nearest", nat.addr(keep_q), 0, Q, nat.addr(keep_t), 0, P, md, int(device), nat.addr(index), nat.addr(d2), 0, sptr, 0),
-              "sc_nearest", "sc_nearest_last_error")
+    nat.unit_call("sc_nearest", q.ptr, 0, Q, t.ptr, 0, P, md, int(device), nat.addr(index), nat.addr(d2), 0, sptr, 0)
     return (index[:Q], d2[:Q], sums) if want_points else (None, None, sums)
 
 
@@ -479,28 +393,15 @@ def nearest_confusion(index, query_labels, target_labels, n_labels, device=0):
     """``counts[a, b]`` = queries of label id ``a`` whose nearest target has label id ``b`` (``sc_nearest_confusion``):
     NumPy int64 ``[L, L]``.  ``index`` / ``query_labels`` are both int32 NumPy arrays or both int32 CUDA tensors,
     ``target_labels`` either; queries with index -1 are not counted; ids outside ``0..L-1`` raise ``ValueError``."""
-    from . import _native as nat
+    from . import _native as nat, _operands as ops
 
     L = int(n_labels)
-    if _is_tensor(index) != _is_tensor(query_labels):
+    if ops.is_tensor(index) != ops.is_tensor(query_labels):
         raise ValueError("index and query_labels must both be arrays or both CUDA tensors")
-    keep, ptrs, on_dev, devs = [], [], [], []
-    for a, what in ((index, "index"), (query_labels, "query_labels"), (target_labels, "target_labels")):
-        if _is_tensor(a):
-            import torch
-            if a.dtype != torch.int32 or not a.is_cuda or not a.is_contiguous() or a.dim() != 1:
-                raise ValueError(f"device {what} must be a contiguous int32 CUDA tensor [n]")
-            keep.append(a)
-            ptrs.append(a.data_ptr() if a.numel() else 0)
-            on_dev.append(1)
-            devs.append(a.device)
-        else:
-            arr = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
-            keep.append(arr)
-            ptrs.append(nat.addr(arr) if arr.size else 0)
-            on_dev.append(0)
-    if len(keep[0]) != len(keep[1]):
+    i, q, t = ops.ids(index, "index"), ops.ids(query_labels, "query_labels"), ops.ids(target_labels, "target_labels")
+    if i.n != q.n:
         raise ValueError("one label per query")
+    devs = [a.tdevice for a in (i, q, t) if a.on_device]
     if len(set(devs)) > 1:
         raise ValueError("the device arrays must be on one device")
     stream = 0
@@ -509,6 +410,6 @@ def nearest_confusion(index, query_labels, target_labels, n_labels, device=0):
         device = devs[0].index
         stream = torch.cuda.current_stream(device).cuda_stream
     counts = np.zeros((max(L, 1), max(L, 1)), dtype=np.int64)
-    nat.check(nat.backend().call("sc_nearest_confusion", ptrs[0], ptrs[1], on_dev[0], len(keep[0]), ptrs[2], on_dev[2], len(keep[2]), L,
-                                 int(device), nat.addr(counts), int(stream)), "sc_nearest_confusion", "sc_nearest_last_error")
+    nat.unit_call("sc_nearest_confusion", i.ptr, q.ptr, i.on_device, i.n, t.ptr, t.on_device, t.n, L, int(device), nat.addr(counts),
+                  int(stream))
     return counts

@@ -99,7 +99,8 @@ def _points_of(cloud):
 
 def _subset(points, idx):
     """The rows ``idx`` of a NumPy array or of a CUDA tensor (which stays on its device)."""
-    if not isinstance(points, np.ndarray) and hasattr(points, "data_ptr"):
+    from .._operands import is_tensor
+    if is_tensor(points):
         import torch
         return points[torch.as_tensor(idx, dtype=torch.long, device=points.device)].contiguous()
     return np.asarray(points, dtype=np.float64).reshape(-1, 3)[idx]

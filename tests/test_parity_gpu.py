@@ -1624,6 +1624,36 @@ def test_read_back_in_pieces_with_a_host_function_beside_the_copies(gpu_device):
     ec.close()
 
 
+def test_pipelined_read_back_hands_on_the_exception_of_its_host_function(gpu_device):
+    """``on_piece`` raises on the third of eight pieces: the caller gets that very exception (the method owns no ring
+    to tidy), and the engine reads back as before afterwards, in one piece and in pieces."""
+    shape, origin, vs, views = scene((8, 8, 8), 4, "plant")
+    ea = nat.Engine(shape, origin, vs, nat.SC_MODE_AVERAGE)
+    for K, R, t, m in views:
+        ea.process_view(K, R, t, img_as_float32(m), nat.SC_MASK_F32)
+    before = ea.get_values().copy()
+    assert before.nbytes == 8 * 256
+
+    class Marker(Exception):
+        pass
+
+    out = np.full(shape, 7, dtype=np.float32)
+
+    def third_piece_fails(piece):  # (called once per sub-piece, a piece being split among the workers: by address)
+        if (piece.ctypes.data - out.ctypes.data) // 256 == 2:
+            raise Marker("the third piece")
+
+    with pytest.raises(Marker) as info:
+        ea.get_values_pipelined(out, third_piece_fails, piece_bytes=256)
+    assert type(info.value) is Marker and str(info.value) == "the third piece"
+    assert np.array_equal(ea.get_values(), before)
+    seen = []
+    again = np.full(shape, 7, dtype=np.float32)
+    assert ea.get_values_pipelined(again, lambda piece: seen.append(piece.size), piece_bytes=256) is again
+    assert np.array_equal(again, before) and sum(seen) == before.size
+    ea.close()
+
+
 @pytest.mark.parametrize("default_value", [0, 1, -1, 5])
 @pytest.mark.parametrize("kind", ["plant", "solid", "dense"])
 def test_bricks_no_view_sees_keep_their_labels(gpu_device, kind, default_value):
