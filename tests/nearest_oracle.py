@@ -47,6 +47,13 @@ def nearest_all_pairs(queries, targets, max_distance=None):
     return _bound(index, d[np.arange(len(q)), index], max_distance)
 
 
+def nearest_in_pieces(queries, targets, max_distance=None, piece=16384):
+    """``nearest_all_pairs`` for many queries against few targets: the same literal form, ``piece`` queries at a time."""
+    q, t = _clouds(queries, targets)
+    parts = [nearest_all_pairs(q[k:k + piece], t, max_distance) for k in range(0, len(q), piece)]
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
 def nearest(queries, targets, max_distance=None, return_ties=False):
     """The k-d tree form: N1 and N2 over EVERY candidate ``query_ball_point`` returns within the tree's own nearest
     distance times ``1 + 1e-9`` (plus the tree's own answer); the tree's arithmetic decides nothing.
@@ -170,3 +177,108 @@ def tie_clouds(seed=5):
     edges[np.arange(70), rng.integers(0, 3, size=70)] += 0.5
     on = np.concatenate([lattice[[3, 50, 100, 200]], rng.integers(0, 6, size=(46, 3)).astype(np.float64)])
     return np.ascontiguousarray(np.concatenate([centres, edges, on])), np.ascontiguousarray(targets)
+
+
+# ---- the launch geometry of csrc/nearest.hip, for the tests that go past its capped grids ---------------------------
+# Nothing below decides a result.  The caps are read out of the sources' text (a constant that is no longer there fails
+# loudly: tests/test_unit_plans_host.py), the grid is sc_nearest.h's plan restated: with them a test can say, from its
+# inputs alone, that a thread takes a second trip through its loop or that the far pass has more queries than wavefronts.
+FAR_P, FAR_Q, FAR_NEAR_EVERY = 600, 9300, 31      # a far list longer than the far pass has wavefronts; 300 near queries
+SUMS_Q, SUMS_P = 66000, 64                         # queries past the blocks of the sums launch
+LATE_P = 65836                                     # targets past the blocks of the box launch
+LATE_Q = 262144 + 300                              # device queries whose judge takes a trip more than an uncapped grid's 3
+CONFUSION_Q, CONFUSION_P = 262144 + 777, 1000      # queries past the blocks of the labels and confusion launches
+
+
+def launch_caps():
+    """The block size and the block caps of nearest.hip's launches, and of sc_points.h's judge of device points."""
+    from tests.evaluation_oracle import source_constant
+    caps = {name: source_constant("nearest.hip", name) for name in ("kB", "kPartials", "kFarBlocks", "kLdsTable")}
+    caps["kNearRings"] = source_constant("sc_nearest.h", "kNearRings")
+    caps["label_blocks"] = source_constant("nearest.hip", "the cap of sc_nearest_confusion's grids",
+                                           r"std::min<int64_t>\(\(std::max\(Q, P\) \+ kB - 1\) / kB,\s*(\d+)\)")
+    caps["finite_blocks"] = source_constant("sc_points.h", "the cap of launch_points_finite's grid",
+                                            r"std::min<int64_t>\(\(n \+ 255\) / 256,\s*(\d+)\)")
+    return caps
+
+
+def _stride(n, block, cap):
+    return min((n + block - 1) // block, cap) * block
+
+
+def box_stride(P):
+    """Targets a trip of ``nearest_box_kernel``'s loop takes; a target of index >= this is seen on a later trip."""
+    caps = launch_caps()
+    return _stride(P, caps["kB"], caps["kPartials"])
+
+
+def sums_stride(Q):
+    """The same for the queries of ``nearest_sums_kernel``."""
+    return box_stride(Q)
+
+
+def finite_stride(n):
+    """COORDINATES (of the 3 n) a trip of ``points_finite_kernel``'s loop takes for n points."""
+    return _stride(n, 256, launch_caps()["finite_blocks"])
+
+
+def labels_stride(Q, P):
+    """Elements a trip of ``nearest_labels_kernel``'s and ``nearest_confusion_kernel``'s loops takes."""
+    caps = launch_caps()
+    return _stride(max(Q, P), caps["kB"], caps["label_blocks"])
+
+
+def far_waves(Q):
+    """Wavefronts of ``nearest_far_kernel``: a far list longer than this makes them go round."""
+    caps = launch_caps()
+    return min((Q + 3) // 4, caps["kFarBlocks"]) * (caps["kB"] // 64)
+
+
+K_MAX_CELLS, K_SHRINK, K_EDGE_MIN, K_EDGE_MAX, K_PLAN_STEPS = 1 << 22, 1.0 - 2.0 ** -20, 2.0 ** -480, 2.0 ** 480, 8192
+
+
+def plan_grid(targets):
+    """``nn::plan_grid`` over the targets' bounding box: ``(lo, h, n)``."""
+    t = np.asarray(targets, dtype=np.float64).reshape(-1, 3)
+    lo, hi = t.min(axis=0), t.max(axis=0)
+    cap = float(min(max(2 * len(t), 64), K_MAX_CELLS))
+    ext = hi - lo
+    n = np.ones(3, dtype=np.int64)
+    if not np.all(np.isfinite(ext)) or not (ext > 0.0).any():
+        return lo, 1.0, n
+    k = int((ext > 0.0).sum())
+    h = math.exp((sum(math.log(e) for e in ext if e > 0.0) - math.log(cap / 2.0)) / k)
+    for _ in range(K_PLAN_STEPS):
+        if h >= K_EDGE_MIN:
+            if not h <= K_EDGE_MAX:
+                break
+            cnt = np.floor(ext / h) + 1.0
+            if cnt[0] * cnt[1] * cnt[2] <= cap:
+                return lo, h, cnt.astype(np.int64)
+        h *= 1.25
+    return lo, 1.0, n
+
+
+def cell_of(x, lo, h, n):
+    """``nn::cell_of`` for arrays ``[..., 3]``."""
+    with np.errstate(over="ignore"):
+        return np.minimum(np.maximum(np.floor((x - lo) / h), 0.0), (n - 1).astype(np.float64)).astype(np.int64)
+
+
+def ring_bound(h, r):
+    """``nn::ring_bound``."""
+    hr = h * float(r)
+    return (hr * hr) * K_SHRINK
+
+
+def certainly_far(queries, targets, d2, max_distance=None):
+    """How many queries the rings cannot settle, whatever the last bit of ``h`` is: the ring that reaches every far face
+    lies beyond ``kNearRings``, and the bound after ring ``kNearRings``, raised by 1e-9, is still below the query's true
+    ``d2`` (the checker's) and below ``md2``.  A condition on the inputs, not a tolerance on the kernel."""
+    rings = launch_caps()["kNearRings"]
+    lo, h, n = plan_grid(targets)
+    c = cell_of(np.asarray(queries, dtype=np.float64).reshape(-1, 3), lo, h, n)
+    last = np.maximum(c, n - 1 - c).max(axis=1)
+    bound = ring_bound(h, rings) * (1.0 + 1e-9)
+    md2 = np.inf if max_distance is None else np.float64(max_distance) * np.float64(max_distance)
+    return int(np.count_nonzero((last > rings) & (bound < d2) & (bound < md2)))

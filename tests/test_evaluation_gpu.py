@@ -142,6 +142,86 @@ def test_slabs_equal_one_piece_and_calls_repeat(gpu_device):
     assert metrics.voxel_confusion(v, g, background=None, device=gpu_device) == one
 
 
+# ---- several x-planes per block ---------------------------------------------------------------------------------
+# Every volume above gives a block ONE x-plane (tests/test_unit_plans_host.py): its loop over the planes of a run, the
+# short last run, the LDS counters and seen[] across planes run here.  Each case first asserts, by the plan's replica
+# and the CHECKER's account, that it is such a case.  Ground truths are one longer on every axis: their own pitches.
+def _ids(shape):
+    return "%dx%dx%d" % shape
+
+
+def _longer(shape):
+    return tuple(s + 1 for s in shape)
+
+
+def _device_route(v, g, device, want, wproj, **kw):
+    import torch
+    tv, tg = ({k: torch.from_numpy(a).cuda(device) for k, a in d.items()} for d in (v, g))
+    got, proj = metrics.voxel_confusion(tv, tg, projections=True, **kw)
+    assert got == want and all(np.array_equal(proj[k], wproj[k]) for k in wproj)
+    assert metrics.voxel_confusion(tv, tg, **kw) == want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", oracle.LONG_SHAPES, ids=_ids)
+@pytest.mark.parametrize("pred_dtype,gt_dtype", [(np.float32, np.uint8), (np.float32, np.float64), (np.float64, np.uint8),
+                                                 (np.float64, np.float64)])
+def test_long_volumes_counts_add_up_over_a_run_of_planes(gpu_device, shape, pred_dtype, gt_dtype):
+    plan = oracle.quad_plan(*shape)
+    assert plan["xc"] >= 2 and shape[0] % plan["xc"] == plan["last"] % plan["xc"]  # (the last run: short on three of the four)
+    v, g = oracle.adversarial_volumes(shape, _longer(shape), 3, seed=sum(shape), pred_dtype=pred_dtype, gt_dtype=gt_dtype)
+    got, proj = check_voxels(v, g, gpu_device, background="c1")
+    # more voxels in one counter than a plane holds, and than a block adds in one plane: the planes of a run added up
+    more = max(shape[1] * shape[2], 4 * plan["threads"])
+    assert all(h["tp"] > 0 and h["fp"] > 0 and h["tn"] > more and h["fn"] > more for h in got.values())
+    _device_route(v, g, gpu_device, got, proj, background="c1")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", oracle.LONG_SHAPES, ids=_ids)
+def test_long_volumes_projection_of_single_planes(gpu_device, shape):
+    """The adversarial pool predicts every class in every column of a long volume: its projection is all ones whatever
+    ``seen[]`` does.  Here a column predicts its class in ONE plane or in none: the first, the last or a middle plane
+    of a run, or a plane of the short last run."""
+    pred_dtype, gt_dtype = ((np.float32, np.uint8), (np.float64, np.float64))[oracle.LONG_SHAPES.index(shape) % 2]
+    v, g, at, placed = oracle.needle_volumes(shape, _longer(shape), 4, seed=5 + sum(shape), pred_dtype=pred_dtype, gt_dtype=gt_dtype)
+    print(placed)
+    assert set(placed) == set(oracle.needle_planes(shape[0], oracle.quad_plan(*shape))) and all(n > 0 for n in placed.values())
+    want, wproj = oracle.voxel_histograms(v, g, background=None, projections=True)
+    for c, k in enumerate(v):  # by the CHECKER's account: neither empty nor full, and exactly the needles
+        assert 0 < wproj[k].sum() < wproj[k].size and np.array_equal(wproj[k], (at[c] >= 0).astype(np.uint8))
+        assert want[k]["tp"] + want[k]["fp"] > 0
+    got, proj = check_voxels(v, g, gpu_device, background=None)  # the host route
+    _device_route(v, g, gpu_device, got, proj, background=None)
+    v, g = _rename(v, "c2", "background"), _rename(g, "c2", "background")
+    got, proj = check_voxels(v, g, gpu_device)
+    _device_route(v, g, gpu_device, got, proj)
+
+
+@pytest.mark.gpu
+def test_slabs_of_a_long_volume_walk_runs_of_two_planes(gpu_device):
+    shape, gshape = oracle.SLAB_SHAPE, _longer(oracle.SLAB_SHAPE)
+    nx, ny, nz = shape
+    v, g, at, placed = oracle.needle_volumes(shape, gshape, 3, seed=23, pred_dtype=np.float32, gt_dtype=np.uint8)
+    want, wproj = oracle.voxel_histograms(v, g, background=None, projections=True)
+    assert all(0 < wproj[k].sum() < wproj[k].size for k in wproj)
+    one, one_proj = metrics.voxel_confusion(v, g, background=None, projections=True, device=gpu_device)
+    assert one == want and all(np.array_equal(one_proj[k], wproj[k]) for k in wproj)
+    per_plane = 3 * ny * nz * 4 + 3 * gshape[1] * gshape[2]  # one x-plane of every volume
+    laid, pad = 1024 + 256 * ((3 * ny * nz + 255) // 256), 6 * 256  # the counters and the projection; the volumes' padding
+    limit = laid + pad + oracle.SLAB_PLANES * per_plane + per_plane // 2
+    # room for 4100 planes: slabs of 4100, 4100 and 1800 planes, in runs of 2, 2 and 1 planes per block
+    assert (limit - laid - pad) // per_plane == oracle.SLAB_PLANES == 4100
+    assert [oracle.quad_plan(p, ny, nz)["xc"] for p in (4100, 4100, 1800)] == [2, 2, 1]
+    try:
+        metrics.set_chunk_bytes(limit)
+        got, proj = metrics.voxel_confusion(v, g, background=None, projections=True, device=gpu_device)
+        assert got == one and all(np.array_equal(proj[k], one_proj[k]) for k in one_proj)
+    finally:
+        metrics.set_chunk_bytes(0)  # the default again
+    assert metrics.voxel_confusion(v, g, background=None, projections=True, device=gpu_device)[0] == one
+
+
 # ---- masks ------------------------------------------------------------------------------------------------------
 # (n, 33, 577): two tile rows (a tile has 32) and two tile columns (10 words against a tile's 8), a last word of one bit
 PICTURES = [(1, 1, 1), (3, 1, 1), (1, 37, 41), (3, 37, 41), (1, 64, 130), (3, 64, 130), (1, 33, 577), (2, 33, 577)]

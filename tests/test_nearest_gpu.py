@@ -361,3 +361,135 @@ def test_virtual_plant_cloud_against_its_mesh(gpu_device):
     assert abs(chamfer - want_chamfer) <= 2 * oracle.sums_tolerance(len(verts)) * want_chamfer
     print(f"virtual plant: {len(cloud)} points against {len(verts)} vertices: fitness {got['all']['fitness']:.6f}, "
           f"inlier_rmse {got['all']['inlier_rmse']:.6f} at max_distance 0.5, chamfer distance {chamfer:.6f}")
+
+
+# ---- 12: past the capped grids ---------------------------------------------------------------------------------------
+# Every launch of nearest.hip but the one-thread-per-point ones has a capped grid and a grid-stride loop; the clouds
+# above are all small enough for one trip.  tests/test_unit_plans_host.py pins the caps' replica and these sizes; each
+# case below first shows from its INPUTS and the checker that it goes past its cap.
+@pytest.mark.gpu
+def test_far_list_longer_than_the_far_pass_has_wavefronts(gpu_device):
+    rng = np.random.default_rng(108)
+    t = rng.uniform(0.0, 1.0, size=(oracle.FAR_P, 3))
+    extent = (t.max(axis=0) - t.min(axis=0)).max()
+    q = t.mean(axis=0) + 1e3 * extent * np.array([1.0, -0.5, 0.25]) + rng.uniform(-1.0, 1.0, size=(oracle.FAR_Q, 3))
+    near = np.arange(oracle.FAR_Q) % oracle.FAR_NEAR_EVERY == 0  # interleaved: the far list has gaps
+    q[near] = rng.uniform(0.0, 1.0, size=(int(near.sum()), 3))
+    q = np.ascontiguousarray(q)
+    assert near.sum() == 300
+    index, d2 = oracle.nearest(q, t)
+    far = oracle.certainly_far(q, t, d2)
+    print(f"certainly far {far} of {len(q)}, wavefronts {oracle.far_waves(len(q))}")
+    assert far > oracle.far_waves(len(q)) and oracle.certainly_far(q[near], t, d2[near]) == 0
+    assert d2[~near].min() > (900.0 * extent) ** 2 and d2[near].max() < 1.0
+    check(q, t, gpu_device, want=(index, d2))
+    check(q, t, gpu_device, tensors=True, want=(index, d2))
+
+
+@pytest.mark.gpu
+def test_sums_past_the_partial_blocks(gpu_device):
+    import torch
+    rng = np.random.default_rng(109)
+    q, t = rng.uniform(0.0, 4.0, size=(oracle.SUMS_Q, 3)), rng.uniform(0.0, 4.0, size=(oracle.SUMS_P, 3))
+    Q = len(q)
+    assert Q > oracle.sums_stride(Q)  # the last queries are added on a second trip
+    free = oracle.nearest_in_pieces(q, t)
+    tq_, tt_ = torch.from_numpy(q).cuda(gpu_device), torch.from_numpy(t).cuda(gpu_device)
+    for md in (None, 0.5):
+        d2 = oracle._bound(*free, md)[1]
+        n, s2, s1 = oracle.sums(d2)
+        late = int(np.isfinite(d2[oracle.sums_stride(Q):]).sum())
+        print(f"max_distance {md}: matched {n} of {Q}, {late} of them past the first trip")
+        assert late > 0 and (n == Q if md is None else 0 < n < Q)  # matched and unmatched queries both exist
+        runs = [proc3d.nearest_sums(q, t, md, device=gpu_device) for _ in range(3)] + [proc3d.nearest_sums(tq_, tt_, md)]
+        assert runs[0][0] == n and _close(runs[0][1], s2, Q) and _close(runs[0][2], s1, Q)
+        assert all(r == runs[0] for r in runs[1:])  # the same bits, from host arrays and from tensors
+        check(q, t, gpu_device, max_distance=md, tensors=True, want=oracle._bound(*free, md))
+
+
+@pytest.fixture(scope="module")
+def late_targets():
+    """65 836 targets whose box only the last 300 span: its eight corners lie among the indices >= 65 536, the others
+    well inside.  3000 queries inside and around the box, with the checker's answer."""
+    rng = np.random.default_rng(110)
+    P = oracle.LATE_P
+    first_late = oracle.box_stride(P)
+    assert 0 < first_late < P - 8
+    t = rng.uniform(1.0, 9.0, size=(P, 3))
+    corners = np.array([[x, y, z] for x in (0.0, 10.0) for y in (0.0, 10.0) for z in (0.0, 10.0)])
+    t[first_late + 3 + 37 * np.arange(8)] = corners
+    t = np.ascontiguousarray(t)
+    assert t[:first_late].min() >= 1.0 and t[:first_late].max() <= 9.0 and t.min() == 0.0 and t.max() == 10.0
+    q = _around(t, rng, n=1500)
+    assert q.shape == (3000, 3)
+    return dict(q=q, t=t, qt=oracle.nearest(q, t))
+
+
+@pytest.mark.gpu
+def test_targets_past_the_partial_blocks(gpu_device, late_targets):
+    q, t, want = late_targets["q"], late_targets["t"], late_targets["qt"]
+    first_late = oracle.box_stride(len(t))
+    assert (want[0] >= first_late).any() and (want[0] < first_late).any()  # late targets are answers too
+    check(q, t, gpu_device, want=want)
+    check(q, t, gpu_device, tensors=True, want=want)
+    bounded = oracle._bound(*want, 0.75)
+    assert (bounded[0] == -1).any() and (bounded[0] >= 0).any()
+    check(q, t, gpu_device, max_distance=0.75, want=bounded)
+    check(q, t, gpu_device, max_distance=0.75, tensors=True, want=bounded)
+
+
+@pytest.mark.gpu
+def test_refusals_on_the_device_in_a_late_trip(gpu_device, late_targets):
+    """The judges of device points are grid-stride loops under a cap: a bad value in the LAST point is found by a late
+    trip only (the box launch's second, the fourth of the judge of the queries)."""
+    import torch
+    q, t, want = late_targets["q"], late_targets["t"], late_targets["qt"]
+    tq, tt = torch.from_numpy(q).cuda(gpu_device), torch.from_numpy(t).cuda(gpu_device)
+    assert len(t) - 1 >= oracle.box_stride(len(t))
+    for bad in (float("nan"), float("inf")):
+        broken = tt.clone()
+        broken[-1, 2] = bad
+        with pytest.raises(ValueError, match="non-finite coordinate in the device targets"):
+            proc3d.nearest_points(tq, broken)
+        index, d2 = proc3d.nearest_points(tq, tt)  # the call after a refused one is a whole one
+        assert np.array_equal(index.cpu().numpy(), want[0]) and np.array_equal(d2.cpu().numpy(), want[1])
+    rng = np.random.default_rng(111)
+    lq, st = rng.uniform(0.0, 4.0, size=(oracle.LATE_Q, 3)), rng.uniform(0.0, 4.0, size=(64, 3))
+    assert (3 * len(lq) - 1) // oracle.finite_stride(len(lq)) == 3
+    lwant = oracle.nearest_in_pieces(lq, st)
+    tlq, tst = torch.from_numpy(lq).cuda(gpu_device), torch.from_numpy(st).cuda(gpu_device)
+    for bad in (float("nan"), float("-inf")):
+        broken = tlq.clone()
+        broken[-1, 2] = bad
+        with pytest.raises(ValueError, match="non-finite coordinate in the device queries"):
+            proc3d.nearest_points(broken, tst)
+        index, d2 = proc3d.nearest_points(tlq, tst)
+        assert np.array_equal(index.cpu().numpy(), lwant[0]) and np.array_equal(d2.cpu().numpy(), lwant[1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("L", [LDS_MAX_LABELS, LDS_MAX_LABELS + 1])
+def test_confusion_past_the_label_blocks(gpu_device, L):
+    import torch
+    rng = np.random.default_rng(112 + L)
+    Q, P = oracle.CONFUSION_Q, oracle.CONFUSION_P
+    first_late = oracle.labels_stride(Q, P)
+    assert 0 < first_late < Q - 5 and (L * L <= oracle.launch_caps()["kLdsTable"]) == (L == LDS_MAX_LABELS)  # the LDS table, the global one
+    index = rng.integers(0, P, size=Q).astype(np.int32)
+    index[rng.integers(0, Q - 5, size=Q // 10)] = -1  # unmatched: not counted
+    tl = rng.integers(0, L, size=P).astype(np.int32)
+    ql = np.concatenate([rng.integers(0, L - 1, size=first_late), rng.integers(0, L, size=Q - first_late)]).astype(np.int32)
+    ql[-5:], tl[index[-5:]] = L - 1, L - 1  # the last cell is used, and only by queries of a second trip
+    table, early = np.zeros((L, L), dtype=np.int64), np.zeros((L, L), dtype=np.int64)
+    ok = index >= 0
+    np.add.at(table, (ql[ok], tl[index[ok]]), 1)
+    np.add.at(early, (ql[:first_late][ok[:first_late]], tl[index[:first_late][ok[:first_late]]]), 1)
+    assert table[L - 1, L - 1] >= 5 and early[L - 1].sum() == 0 and table.sum() == ok.sum() < Q
+    assert np.array_equal(proc3d.nearest_confusion(index, ql, tl, L, device=gpu_device), table)
+    dev = [torch.from_numpy(a).cuda(gpu_device) for a in (index, ql, tl)]
+    assert np.array_equal(proc3d.nearest_confusion(*dev, L), table)
+    dev[1][Q - 1] = L  # one bad query label, where only the second trip of the judge looks
+    with pytest.raises(ValueError, match="outside"):
+        proc3d.nearest_confusion(*dev, L)
+    dev[1][Q - 1] = L - 1
+    assert np.array_equal(proc3d.nearest_confusion(*dev, L), table)  # the call after a refused one is a whole one

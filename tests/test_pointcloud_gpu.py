@@ -10,6 +10,7 @@ from plant3dvision_amd import _native as nat
 from plant3dvision_amd import proc3d
 from plant3dvision_amd.tasks import proc3d as task
 from tests import pointcloud_oracle as oracle
+from tests.evaluation_oracle import LONG_SHAPES, SLAB_PLANES, SLAB_SHAPE, quad_plan  # the run plan's replica
 
 SHAPE = (6, 5, 7)
 DEFAULT = (1.0, 10.0, 0.2)
@@ -156,6 +157,53 @@ def test_slabs_equal_one_piece_and_calls_repeat(gpu_device):
         proc3d.set_select_chunk_bytes(256 + 4 * 256 + 13 * per_plane + per_plane // 2)
         assert np.array_equal(check_select(stack, DEFAULT, gpu_device, want), one)
         proc3d.set_select_chunk_bytes(1)  # less than one plane: one plane per slab
+        assert np.array_equal(check_select(stack, DEFAULT, gpu_device, want), one)
+    finally:
+        proc3d.set_select_chunk_bytes(0)  # the default again
+    assert np.array_equal(check_select(stack, DEFAULT, gpu_device, want), one)
+
+
+# ---- several x-planes per block -----------------------------------------------------------------------------------
+# Every volume above gives a block ONE x-plane (tests/test_unit_plans_host.py pins the plan's replica and these
+# shapes): the loop over the planes of a run, its short last run and the LDS counters across planes run here.
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", LONG_SHAPES, ids=lambda s: "%dx%dx%d" % s)
+@pytest.mark.parametrize("dtype", [np.float32, np.float64, np.uint8])
+@pytest.mark.parametrize("L", [3, 4, 5])
+def test_long_volumes_counts_add_up_over_a_run_of_planes(gpu_device, shape, dtype, L):
+    """(4099, 2, 8): the launch of whole aligned quads, 252 threads of the block beyond the plane; (10000, 3, 7): row
+    tails, three planes per run; (2100, 17, 61) and (2049, 17, 64): two tiles, the second with 16 live threads."""
+    import torch
+    plan = quad_plan(*shape)
+    assert plan["xc"] >= 2 and shape[0] % plan["xc"] == plan["last"] % plan["xc"]
+    stack = oracle.adversarial_stack(shape, L, seed=300 + L + sum(shape), dtype=dtype, background_at=L // 2)
+    tens = {k: torch.from_numpy(v).cuda(gpu_device) for k, v in stack.items()}
+    assert all(t.data_ptr() % 16 == 0 for t in tens.values())
+    for params in (DEFAULT, (0.5, 1.0, 0.2)):
+        want = oracle.literal_winner(stack, *params)
+        # by the CHECKER's account: owned and unowned voxels, and more voxels in one counter than a plane holds and than
+        # a block adds in one plane -- the planes of a run added up
+        assert (want[0] != oracle.NONE).any() and (want[0] == oracle.NONE).any()
+        assert want[2].max() > max(shape[1] * shape[2], 4 * plan["threads"]) and want[2][L // 2] == 0
+        check_select(stack, params, gpu_device, want)
+        check_select(tens, params, gpu_device, want)
+
+
+@pytest.mark.gpu
+def test_slabs_of_a_long_volume_walk_runs_of_two_planes(gpu_device):
+    shape = SLAB_SHAPE
+    nx, ny, nz = shape
+    stack = oracle.adversarial_stack(shape, 3, seed=72, dtype=np.float32, background_at=1)
+    want = oracle.literal_winner(stack, *DEFAULT)
+    one = check_select(stack, DEFAULT, gpu_device, want)
+    per_plane = 3 * ny * nz * 4 + ny * nz  # one x-plane of every volume and of the winners
+    laid, pad = 256, 4 * 256  # the counters; the buffers' padding
+    limit = laid + pad + SLAB_PLANES * per_plane + per_plane // 2
+    # room for 4100 planes: slabs of 4100, 4100 and 1800 planes, in runs of 2, 2 and 1 planes per block
+    assert (limit - laid - pad) // per_plane == SLAB_PLANES == 4100
+    assert [quad_plan(p, ny, nz)["xc"] for p in (4100, 4100, 1800)] == [2, 2, 1] and quad_plan(nx, ny, nz)["xc"] == 3
+    try:
+        proc3d.set_select_chunk_bytes(limit)
         assert np.array_equal(check_select(stack, DEFAULT, gpu_device, want), one)
     finally:
         proc3d.set_select_chunk_bytes(0)  # the default again
