@@ -379,9 +379,9 @@ int sc_process_view(sc_engine *e, const float K[4], const float R[9], const floa
     } else if (e->mode == SC_MODE_CARVE) {
         rc = enqueue_pack(e, 1, K, R, t, raw, H, W, mask_dtype, (int64_t)row, (int64_t)bytes);
     } else if (mask_dtype == SC_MASK_U8_LUT) {
-        rc = enqueue_tile8(e, 1, K, R, t, raw, H, W, (int64_t)row, (int64_t)bytes);
+        rc = enqueue_tiles(e, kFormU8Strips, 1, K, R, t, raw, H, W, (int64_t)row, (int64_t)bytes);
     } else {
-        rc = enqueue_tilef32(e, 1, K, R, t, raw, H, W, (int64_t)row, (int64_t)bytes);
+        rc = enqueue_tiles(e, kFormF32Tiles, 1, K, R, t, raw, H, W, (int64_t)row, (int64_t)bytes);
     }
     return rc ? rc : after_enqueue(e);
 }
@@ -542,9 +542,9 @@ int sc_process_views_device(sc_engine *e, int V, const float *K, const float *R,
         // one pack launch for the whole batch, then carve launches per views_per_launch
         rc = enqueue_pack(e, V, K, R, t, masks_dev, H, W, mask_dtype, row, view);
     } else if (mask_dtype == SC_MASK_U8_LUT) {
-        rc = enqueue_tile8(e, V, K, R, t, masks_dev, H, W, row, view);
+        rc = enqueue_tiles(e, kFormU8Strips, V, K, R, t, masks_dev, H, W, row, view);
     } else if (e->avg_tile_f32) {
-        rc = enqueue_tilef32(e, V, K, R, t, masks_dev, H, W, row, view);
+        rc = enqueue_tiles(e, kFormF32Tiles, V, K, R, t, masks_dev, H, W, row, view);
     } else {
         for (int q = 0; q < V; ++q) {
             ViewDesc d;
@@ -577,10 +577,9 @@ int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, c
     // launches took 16.5-17.4 ms where six launches of their own take 14.3: the labels' footprints are mixed in
     // different places, so the union of the (brick, view) pairs to project is nearly their sum, and every label
     // is dragged through every pair.  3 labels: 3.6 ms against 4.5.)
-    bool fused = L >= 2 && L <= kMaxLabels && V > 1 && e0->avg_brick && (uint64_t)e0->npitch < 0x80000000ull &&
-                 (W % 16) == 0 && V <= 4096;
-    const uint32_t abys = (uint32_t)((e0->ny + kBrickY - 1) / kBrickY), abzs = (uint32_t)((e0->nz + kBrickZ - 1) / kBrickZ);
-    fused = fused && (uint64_t)e0->planes * abys * abzs < 0x80000000ull;
+    const AvgPlan ap = avg_plan(e0);
+    const uint32_t abys = ap.bricks_y, abzs = ap.bricks_z, anb = ap.nbricks;
+    bool fused = L >= 2 && L <= kMaxLabels && V > 1 && e0->avg_brick && ap.fits && (W % 16) == 0 && V <= 4096;
     for (int l = 0; l < L && fused; ++l) {
         const sc_engine *e = engines[l];
         fused = e->device == e0->device && e->nx == e0->nx && e->ny == e0->ny && e->nz == e0->nz && e->i0 == e0->i0 &&
@@ -620,15 +619,14 @@ int sc_average_labels(sc_engine *const *engines, int L, int V, const float *K, c
     } guard{engines, own, L};
     for (int l = 0; l < L; ++l) engines[l]->stream = main;
     const GridDesc g = grid_desc(e0);
-    const uint32_t anb = (uint32_t)((uint64_t)e0->planes * abys * abzs);
     const size_t need = (size_t)anb * (size_t)V;
     const ViewDesc *vd[64];
     rc = SC_OK;
     for (int l = 0; l < L && rc == SC_OK; ++l) {
         sc_engine *e = engines[l];
-        rc = enqueue_tile8(e, V, K, R, t, masks_dev[l], H, W, row, view);
+        rc = enqueue_tiles(e, kFormU8Strips, V, K, R, t, masks_dev[l], H, W, row, view);
         if (rc) break;
-        if (e->pending[0].occ == nullptr) { rc = fail(SC_ERR_STATE, "no uniformity flags"); break; }
+        if (!brick_view(e, e->pending[0])) { rc = fail(SC_ERR_STATE, "no uniformity flags"); break; }
         const ViewDesc *pin;
         rc = stage_descriptors(e, (size_t)V, &vd[l < 64 ? l : 0], &pin);
         if (rc) break;

@@ -2,17 +2,17 @@
 // sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- average (backprojection.c:36-55): mask forms, flat-footprint verdicts, one label or several per launch.
 
 // average (backprojection.c:36-55): value += mask[v][u] for every in-image view, in the
-// order given (float32 sum, order matters).  Two mask forms (ViewDesc::pad):
-//   0  float32 [H][W] row-major, the value itself (what cl.py:205-215 hands the kernel);
-//   1  the ORIGINAL uint8 mask in 16x8-pixel tiles (one 128-byte line per tile) plus a
+// order given (float32 sum, order matters).  Three mask forms (ViewDesc::form):
+//   kFormRows      float32 [H][W] row-major, the value itself (what cl.py:205-215 hands the kernel);
+//   kFormU8Strips  the ORIGINAL uint8 mask in 16x8-pixel tiles (one 128-byte line per tile) plus a
 //      256-entry float table: table[b] is what the host conversion (img_as_float32, log)
 //      makes of byte b, so table[mask] is the same float32 the reference would upload, at
 //      a quarter of the bytes and with tile-coherent gathers.  The table sits in LDS.
 constexpr int kATileW = 16, kATileH = 8;
-//   2  float32 in 8x4-pixel tiles (32 floats = one 128-byte line per tile; tilef_kernel)
+//   kFormF32Tiles  float32 in 8x4-pixel tiles (32 floats = one 128-byte line per tile; tilef_kernel)
 constexpr int kFTileW = 8, kFTileH = 4;
 // (round 5: strips as for the bytes below -- 8 pixels wide, a strip's rows one after the other, 32 bytes a row, so a
-// 128-byte line is still an 8x4 tile; `strip` = the floats of a strip = 8 x its rows, ViewDesc::tiles_x holds it)
+// 128-byte line is still an 8x4 tile; `strip` = the floats of a strip = 8 x its rows; the averaging forms keep it in ViewDesc::tiles_x)
 __device__ __forceinline__ uint32_t ftile_offset(int u, int v, int strip) {
     return __umul24((uint32_t)u >> 3, (uint32_t)strip) + (((uint32_t)v << 3) | ((uint32_t)u & 7u));
 }
@@ -23,10 +23,65 @@ __device__ __forceinline__ uint32_t ftile_offset(int u, int v, int strip) {
 //     (u >> 4) * strip + v * 16 + (u & 15)          (strip = 16 bytes x the strip's rows; ViewDesc::tiles_x holds it)
 // four vector instructions where the row-major order of the tiles ((v >> 3) * tiles_x + (u >> 4)) * 128 + (v & 7) * 16
 // + (u & 15) took nine (round 5: the averaging kernel is bound by what it issues, 37 instructions per voxel.view).
-// Both factors of the product are below 2^24 and the offset below 2^31: enqueue_tile8 refuses pictures beyond that
+// Both factors of the product are below 2^24 and the offset below 2^31: enqueue_tiles refuses pictures beyond that
 // (a million rows, or 2 GiB of pixels).
 __device__ __forceinline__ uint32_t u8strip_offset(int u, int v, uint32_t strip) {
     return __umul24((uint32_t)u >> 4, strip) + (((uint32_t)v << 4) | ((uint32_t)u & 15u));
+}
+
+// The float32 a uint8 mask stands for at byte `off` (u8strip_offset): the byte is loaded only if ok, the table looked
+// up whatever -- no branch around the LDS read.
+__device__ __forceinline__ float table_at(const void *mask, const float *lut_s, uint32_t off, bool ok) {
+    uint32_t b = 0;
+    if (ok) b = load_mask_byte(mask, off);
+    return lut_s[b];
+}
+// The float32 the mask of view d, of form FORM, holds at pixel (u, v): the one place a form's offset and load are
+// written.  ok == false: the pixel is not loaded, and the value is not to be added.
+template <int FORM>
+__device__ __forceinline__ float mask_at(const ViewDesc &d, const float *lut_s, int u, int v, bool ok) {
+    if (FORM == kFormU8Strips) return table_at(d.mask, lut_s, u8strip_offset(u, v, (uint32_t)d.tiles_x), ok);
+    float add = 0.0f;
+    if (ok) {
+        if (FORM == kFormF32Tiles) add = load_mask_float(d.mask, (int64_t)ftile_offset(u, v, d.tiles_x));
+        else add = load_mask_float(d.mask, (int64_t)v * d.W + u);  // kFormRows: nearest texel
+    }
+    return add;
+}
+
+// The pixel of a voxel that is KNOWN to lie in front of a certified camera and inside the picture (kVerdictInside): the
+// arithmetic of project()'s short path (backprojection.c:11-21, the correctly rounded shared-reciprocal division) without
+// the tests of :13 and :23-31, which hold.
+__device__ __forceinline__ void project_inside(float ax, float ay, float az, float z, const ViewDesc &d, int &u, int &v) {
+    const float pz = (az + d.R[8] * z) + d.t[2];  // :11
+    const float px = (ax + d.R[2] * z) + d.t[0];  // :17
+    const float py = (ay + d.R[5] * z) + d.t[1];  // :18
+    const float r = refined_rcp(pz);
+    u = (int)(div_by_rcp(px, pz, r) * d.K[0] + d.K[2]);  // :20
+    v = (int)(div_by_rcp(py, pz, r) * d.K[1] + d.K[3]);  // :21
+}
+
+// What one view of form FORM adds to a lane's four voxels (the first `nvalid` of them exist): project, fetch, add
+// where in-image (:54).  INSIDE: every voxel is known to be in-image -- no test, no branch around the gather.
+template <int FORM, bool INSIDE>
+__device__ __forceinline__ void add_view(const ViewDesc &d, const float *lut_s, float ax, float ay, float az,
+                                         const float (&z)[4], int nvalid, float (&val)[4]) {
+    bool ok[4];
+    float add[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        int u, v;
+        if (INSIDE) {
+            project_inside(ax, ay, az, z[e], d, u, v);
+            ok[e] = true;
+        } else {
+            ok[e] = project(ax, ay, az, z[e], d, u, v) & (e < nvalid);
+        }
+        add[e] = mask_at<FORM>(d, lut_s, u, v, ok[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (ok[e]) val[e] = val[e] + add[e];  // :54
 }
 
 // (rows are padded to a multiple of 64 voxels: a group's four values are read and written as one float4)
@@ -62,41 +117,10 @@ __device__ __forceinline__ void average_body(float *__restrict__ values, const G
         float ax = d.R[0] * vx.x + d.R[1] * vx.y;
         float ay = d.R[3] * vx.x + d.R[4] * vx.y;
         float az = d.R[6] * vx.x + d.R[7] * vx.y;
-        bool ok[4];
-        float add[4];
-        if (d.pad == 1) {  // wave-uniform
-            const uint8_t *m = static_cast<const uint8_t *>(d.mask);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int u, v;
-                ok[e] = project(ax, ay, az, z[e], d, u, v) & (e < (int)vx.nvalid);
-                uint32_t off = u8strip_offset(u, v, (uint32_t)d.tiles_x);
-                uint32_t b = 0;
-                if (ok[e]) b = load_mask_byte(m, off);
-                add[e] = lut_s[b];
-            }
-        } else if (d.pad == 2) {  // float32 in 8x4 tiles
-            const float *m = static_cast<const float *>(d.mask);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int u, v;
-                ok[e] = project(ax, ay, az, z[e], d, u, v) & (e < (int)vx.nvalid);
-                add[e] = 0.0f;
-                if (ok[e]) add[e] = load_mask_float(m, (int64_t)ftile_offset(u, v, d.tiles_x));
-            }
-        } else {
-            const float *m = static_cast<const float *>(d.mask);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int u, v;
-                ok[e] = project(ax, ay, az, z[e], d, u, v) & (e < (int)vx.nvalid);
-                add[e] = 0.0f;
-                if (ok[e]) add[e] = load_mask_float(m, (int64_t)v * d.W + u);  // nearest texel
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (ok[e]) val[e] = val[e] + add[e];  // :54
+        // (the form is wave-uniform)
+        if (d.form == kFormU8Strips) add_view<kFormU8Strips, false>(d, lut_s, ax, ay, az, z, (int)vx.nvalid, val);
+        else if (d.form == kFormF32Tiles) add_view<kFormF32Tiles, false>(d, lut_s, ax, ay, az, z, (int)vx.nvalid, val);
+        else add_view<kFormRows, false>(d, lut_s, ax, ay, az, z, (int)vx.nvalid, val);
     }
     *reinterpret_cast<float4 *>(p) = make_float4(val[0], val[1], val[2], val[3]);
 }
@@ -228,8 +252,8 @@ __global__ __launch_bounds__(kBlock) void uniform_f32_kernel(const float *__rest
 // nothing but 0, every voxel of the brick is in-image and adds table[0] for that view; over tiles of
 // nothing but 255, table[255]: the same float32 addition the reference performs
 // (backprojection.c:54), in the same view order, without projecting anything.  Only views whose
-// footprint is mixed are projected voxel by voxel; a view that does not see the brick at all (verdict 4,
-// OUTSIDE) is skipped.
+// footprint is mixed are projected voxel by voxel; a view that does not see the brick at all (kVerdictOutside)
+// is skipped.
 __global__ __launch_bounds__(kBlock) void avg_flags_kernel(GridDesc g, const ViewDesc *__restrict__ views,
                                                            int nviews, uint32_t bricks_y, uint32_t bricks_z,
                                                            uint32_t nbricks, uint8_t *__restrict__ verd,
@@ -241,33 +265,21 @@ __global__ __launch_bounds__(kBlock) void avg_flags_kernel(GridDesc g, const Vie
     const uint32_t by = at.by, bz = at.bz;
     const float x = plane_x(g, at.il);
     const ViewDesc d = views[vi];
-    // Verdict 5 (round 5): the footprint is MIXED -- the voxels have to be projected -- but lies wholly inside the picture
+    // kVerdictInside (round 5): the footprint is MIXED -- the voxels have to be projected -- but lies wholly inside the picture
     // (rect_box: every voxel of the brick in front of the camera, its pixel inside the picture, rounding included):
     // the averaging kernel then projects without the picture test (backprojection.c:13, :23-31 hold for every voxel).
     bool all_inside = false;
-    if (d.pad == 2) {  // tiled float32 mask: flat when every region under the brick holds one value
+    if (d.form == kFormF32Tiles) {  // flat when every region under the brick holds one value
         uint32_t bits;
         uint32_t v = brick_flat_f32(d, g, x, (int)(by * kBrickY), (int)(bz * kBrickZ), bits, &all_inside);
-        if (v == 0u && all_inside && d.safe != 0) v = 5u;
+        if (v == kVerdictMixed && all_inside && d.safe != 0) v = kVerdictInside;
         verd[(size_t)lb * (uint32_t)nviews + vi] = (uint8_t)v;
         if (verdf != nullptr) verdf[(size_t)lb * (uint32_t)nviews + vi] = bits;
         return;
     }
     uint32_t v = brick_verdict(d, g, x, (int)(by * kBrickY), (int)(bz * kBrickZ), (d.W + 31) >> 5, &all_inside);
-    if (v == 0u && all_inside && d.safe != 0) v = 5u;  // (d.safe: the short division needs no operand test, project())
+    if (v == kVerdictMixed && all_inside && d.safe != 0) v = kVerdictInside;  // (d.safe: the short division needs no operand test, project())
     verd[(size_t)lb * (uint32_t)nviews + vi] = (uint8_t)v;
-}
-
-// The pixel of a voxel that is KNOWN to lie in front of a certified camera and inside the picture (verdict 5): the
-// arithmetic of project()'s short path (backprojection.c:11-21, the correctly rounded shared-reciprocal division) without
-// the tests of :13 and :23-31, which hold.
-__device__ __forceinline__ void project_inside(float ax, float ay, float az, float z, const ViewDesc &d, int &u, int &v) {
-    const float pz = (az + d.R[8] * z) + d.t[2];  // :11
-    const float px = (ax + d.R[2] * z) + d.t[0];  // :17
-    const float py = (ay + d.R[5] * z) + d.t[1];  // :18
-    const float r = refined_rcp(pz);
-    u = (int)(div_by_rcp(px, pz, r) * d.K[0] + d.K[2]);  // :20
-    v = (int)(div_by_rcp(py, pz, r) * d.K[1] + d.K[3]);  // :21
 }
 
 template <bool FRESH>
@@ -287,21 +299,11 @@ __global__ __launch_bounds__(kBlock) void average_brick_kernel(float *__restrict
     const uint32_t j = at.by * kBrickY + wave * 4 + (lane >> 4);
     const uint32_t k0 = at.bz * kBrickZ + (lane & 15) * 4;
     const bool inside = j < g.ny && k0 < g.nz;
-    const int nvalid = inside ? (int)min(4u, g.nz - k0) : 0;
-    const bool vec = (g.nzp & 3u) == 0;
-    float *p = values + ((uint64_t)il * g.ny + j) * g.nzp + k0;
+    float *p = values + ((uint64_t)il * g.ny + j) * g.nzp + k0;  // (GridDesc::nzp % 64 == 0: the group is one aligned float4)
     float val[4] = {init, init, init, init};
-    if (!FRESH) {
-        if (vec) {
-            if (inside) {
-                float4 q = *reinterpret_cast<const float4 *>(p);
-                val[0] = q.x; val[1] = q.y; val[2] = q.z; val[3] = q.w;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < nvalid) val[e] = p[e];
-        }
+    if (!FRESH && inside) {
+        const float4 q = *reinterpret_cast<const float4 *>(p);
+        val[0] = q.x; val[1] = q.y; val[2] = q.z; val[3] = q.w;
     }
     const float x = plane_x(g, il);
     const float y = g.oy + (float)(int)j * g.vs;  // backprojection.c:72-73
@@ -318,66 +320,26 @@ __global__ __launch_bounds__(kBlock) void average_brick_kernel(float *__restrict
         const uint32_t minef = (myverdf != nullptr && (int)lane < nv) ? myverdf[v0 + (int)lane] : 0u;
         for (int q = 0; q < nv; ++q) {
             const uint32_t c = __builtin_amdgcn_readlane(mine, q);  // wave-uniform (brick-uniform)
-            if (c == 4u) continue;  // OUTSIDE: no voxel of the brick is in the picture, the view adds nothing (:50-52)
-            if (c != 0u && c != 5u) {
-                const float add = c == 1u ? add0 : (c == 2u ? add255 : __uint_as_float(__builtin_amdgcn_readlane(minef, q)));
+            if (c == kVerdictOutside) continue;  // no voxel of the brick is in the picture, the view adds nothing (:50-52)
+            if (c != kVerdictMixed && c != kVerdictInside) {
+                const float add = c == kVerdictEmpty ? add0 : (c == kVerdictFull ? add255 : __uint_as_float(__builtin_amdgcn_readlane(minef, q)));
 #pragma unroll
                 for (int e = 0; e < 4; ++e) val[e] = val[e] + add;  // :54, every voxel is in-image
                 continue;
             }
             const ViewDesc d = views[v0 + q];
             const float ax = d.R[0] * x + d.R[1] * y, ay = d.R[3] * x + d.R[4] * y, az = d.R[6] * x + d.R[7] * y;
-            if (c == 5u) {  // mixed, and every voxel of the brick inside the picture: no test, no branch around the gather
-                if (d.pad == 2) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        int u, v;
-                        project_inside(ax, ay, az, z[e], d, u, v);
-                        val[e] = val[e] + load_mask_float(d.mask, (int64_t)ftile_offset(u, v, d.tiles_x));  // :54
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        int u, v;
-                        project_inside(ax, ay, az, z[e], d, u, v);
-                        const uint32_t off = u8strip_offset(u, v, (uint32_t)d.tiles_x);
-                        val[e] = val[e] + lut_s[load_mask_byte(d.mask, off)];  // :54
-                    }
-                }
-                continue;
-            }
-            if (d.pad == 2) {  // tiled float32 mask (wave-uniform)
-                const float *mf = static_cast<const float *>(d.mask);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    int u, v;
-                    const bool ok = project(ax, ay, az, z[e], d, u, v);
-                    float add = 0.0f;
-                    if (ok) add = load_mask_float(mf, (int64_t)ftile_offset(u, v, d.tiles_x));
-                    if (ok) val[e] = val[e] + add;  // :54
-                }
-                continue;
-            }
-            const uint8_t *m = static_cast<const uint8_t *>(d.mask);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int u, v;
-                const bool ok = project(ax, ay, az, z[e], d, u, v);
-                const uint32_t off = u8strip_offset(u, v, (uint32_t)d.tiles_x);
-                uint32_t b = 0;
-                if (ok) b = load_mask_byte(m, off);
-                const float add = lut_s[b];
-                if (ok) val[e] = val[e] + add;  // :54
+            const bool f32 = d.form == kFormF32Tiles;  // wave-uniform; else kFormU8Strips (average_batch)
+            if (c == kVerdictInside) {
+                if (f32) add_view<kFormF32Tiles, true>(d, lut_s, ax, ay, az, z, 4, val);
+                else add_view<kFormU8Strips, true>(d, lut_s, ax, ay, az, z, 4, val);
+            } else {
+                if (f32) add_view<kFormF32Tiles, false>(d, lut_s, ax, ay, az, z, 4, val);
+                else add_view<kFormU8Strips, false>(d, lut_s, ax, ay, az, z, 4, val);
             }
         }
     }
-    if (vec) {
-        if (inside) *reinterpret_cast<float4 *>(p) = make_float4(val[0], val[1], val[2], val[3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (e < nvalid) p[e] = val[e];
-    }
+    if (inside) *reinterpret_cast<float4 *>(p) = make_float4(val[0], val[1], val[2], val[3]);
 }
 
 // ---- several labels at once --------------------------------------------------------------------------------
@@ -413,7 +375,7 @@ __global__ __launch_bounds__(kBlock) void avg_flags_multi_kernel(MultiArgs a, Gr
     const int occ_tx = (d.W + 31) >> 5;
     uint32_t v[L];
 #pragma unroll
-    for (int l = 0; l < L; ++l) v[l] = fpr.outside ? 4u : 0u;
+    for (int l = 0; l < L; ++l) v[l] = fpr.outside ? kVerdictOutside : kVerdictMixed;
     if (!fpr.outside && fpr.ok) {
         uint32_t any[L], all[L];
 #pragma unroll
@@ -427,10 +389,10 @@ __global__ __launch_bounds__(kBlock) void avg_flags_multi_kernel(MultiArgs a, Gr
                     all[l] &= o;
                 }
             }
-        // (5: mixed, but every voxel of the brick inside the picture -- see avg_flags_kernel)
-        const uint32_t mixed = (fpr.inside && d.safe != 0) ? 5u : 0u;
+        // (mixed, but every voxel of the brick inside the picture -- see avg_flags_kernel)
+        const uint32_t mixed = (fpr.inside && d.safe != 0) ? kVerdictInside : kVerdictMixed;
 #pragma unroll
-        for (int l = 0; l < L; ++l) v[l] = (any[l] & 1u) == 0 ? 1u : ((all[l] & 2u) != 0 ? 2u : mixed);
+        for (int l = 0; l < L; ++l) v[l] = (any[l] & 1u) == 0 ? kVerdictEmpty : ((all[l] & 2u) != 0 ? kVerdictFull : mixed);
     }
 #pragma unroll
     for (int l = 0; l < L; ++l) const_cast<uint8_t *>(a.verd[l])[(size_t)lb * (uint32_t)nviews + vi] = (uint8_t)v[l];
@@ -450,7 +412,7 @@ __global__ __launch_bounds__(kBlock) void average_multi_kernel(MultiArgs a, Grid
     const uint32_t j = at.by * kBrickY + wave * 4 + (lane >> 4);
     const uint32_t k0 = at.bz * kBrickZ + (lane & 15) * 4;
     const bool inside = j < g.ny && k0 < g.nz;
-    const uint64_t elem = ((uint64_t)il * g.ny + j) * g.nzp + k0;  // the pitch is a multiple of 64: 16-byte groups
+    const uint64_t elem = ((uint64_t)il * g.ny + j) * g.nzp + k0;  // (GridDesc::nzp % 64 == 0: 16-byte groups)
     float val[L][4];
 #pragma unroll
     for (int l = 0; l < L; ++l) {
@@ -478,14 +440,14 @@ __global__ __launch_bounds__(kBlock) void average_multi_kernel(MultiArgs a, Grid
 #pragma unroll
             for (int l = 0; l < L; ++l) {
                 c[l] = __builtin_amdgcn_readlane(mine[l], q);  // wave-uniform (brick-uniform)
-                mixed |= c[l] == 0u || c[l] == 5u;
-                inside5 |= c[l] == 5u;  // (a matter of the pose: the same for every label whose footprint is mixed)
+                mixed |= c[l] == kVerdictMixed || c[l] == kVerdictInside;
+                inside5 |= c[l] == kVerdictInside;  // (a matter of the pose: the same for every label whose footprint is mixed)
             }
-            if (c[0] == 4u) continue;  // OUTSIDE is a matter of the pose: no label's picture holds a voxel of the brick (:50-52)
+            if (c[0] == kVerdictOutside) continue;  // OUTSIDE is a matter of the pose: no label's picture holds a voxel of the brick (:50-52)
             if (!mixed) {  // every label's footprint is flat: the labels' table values, nothing projected
 #pragma unroll
                 for (int l = 0; l < L; ++l) {
-                    const float add = c[l] == 1u ? lut_s[l][0] : lut_s[l][255];
+                    const float add = c[l] == kVerdictEmpty ? lut_s[l][0] : lut_s[l][255];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) val[l][e] = val[l][e] + add;  // :54, every voxel is in-image
                 }
@@ -494,7 +456,7 @@ __global__ __launch_bounds__(kBlock) void average_multi_kernel(MultiArgs a, Grid
             const ViewDesc d = a.views[0][v0 + q];  // the pose, and the picture's geometry
             const float ax = d.R[0] * x + d.R[1] * y, ay = d.R[3] * x + d.R[4] * y, az = d.R[6] * x + d.R[7] * y;
             bool ok[4];
-            uint32_t off[4];
+            uint32_t off[4];  // the pixel's place in every label's strips
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 int u, v;
@@ -508,18 +470,16 @@ __global__ __launch_bounds__(kBlock) void average_multi_kernel(MultiArgs a, Grid
             }
 #pragma unroll
             for (int l = 0; l < L; ++l) {
-                if (c[l] != 0u && c[l] != 5u) {  // flat for this label: every voxel is in-image and adds the one value
-                    const float add = c[l] == 1u ? lut_s[l][0] : lut_s[l][255];
+                if (c[l] != kVerdictMixed && c[l] != kVerdictInside) {  // flat for this label: every voxel is in-image and adds the one value
+                    const float add = c[l] == kVerdictEmpty ? lut_s[l][0] : lut_s[l][255];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) val[l][e] = val[l][e] + add;
                     continue;
                 }
-                const uint8_t *m = static_cast<const uint8_t *>(a.views[l][v0 + q].mask);
+                const void *m = a.views[l][v0 + q].mask;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    uint32_t b = 0;
-                    if (ok[e]) b = load_mask_byte(m, off[e]);
-                    const float add = lut_s[l][b];
+                    const float add = table_at(m, lut_s[l], off[e], ok[e]);
                     if (ok[e]) val[l][e] = val[l][e] + add;  // :54
                 }
             }

@@ -417,7 +417,7 @@ void fill_desc(const sc_engine *e, ViewDesc &d, const float *K, const float *R, 
     d.W = W;
     d.H = H;
     d.tiles_x = (W + kTile - 1) / kTile;
-    d.pad = 0;
+    d.form = kFormRows;
     d.occ = occ;
     d.Wf = (float)W;
     d.Hf = (float)H;
@@ -425,7 +425,7 @@ void fill_desc(const sc_engine *e, ViewDesc &d, const float *K, const float *R, 
     d.safe = certify_view(K, R, t, e->origin, e->vs, first, last);
     d.strip = ((H + kTile - 1) / kTile) * kTile;  // the words of a strip of the bit tiles (carve masks)
     d.cmask = nullptr;
-    d.reserved = 0;
+    d.reach = 0;
 }
 
 size_t packed_words(int H, int W) {
@@ -569,97 +569,64 @@ int enqueue_pack(sc_engine *e, int V, const float *K, const float *R, const floa
     return SC_OK;
 }
 
-// averaging, uint8 + table form: raw device bytes [V][H][W] -> 16x8 tiles; appends V pending views
-int enqueue_tile8(sc_engine *e, int V, const float *K, const float *R, const float *t,
-                  const void *raw_dev, int H, int W, int64_t row_stride, int64_t view_stride) {
-    int tiles_x = (W + kATileW - 1) / kATileW, tiles_y = (H + kATileH - 1) / kATileH;
-    size_t per_view = (size_t)tiles_x * tiles_y * 128;
-    // (u8strip_offset: a 24-bit product of the strip's number and its bytes, offsets below 2^31)
-    if (per_view >= ((size_t)1 << 31) || (size_t)tiles_y * 128 >= ((size_t)1 << 24))
-        return fail(SC_ERR_INVALID, "mask too large for the byte gather (%d x %d)", W, H);
+// averaging, the tiled forms: raw device pixels [V][H][W] -> kFormU8Strips (bytes, 16x8 tiles, for the table) or
+// kFormF32Tiles (floats, 8x4 tiles), with the uniformity of every 32x32-pixel region for the brick form; appends V
+// pending views
+int enqueue_tiles(sc_engine *e, int32_t form, int V, const float *K, const float *R, const float *t, const void *raw_dev,
+                  int H, int W, int64_t row_stride, int64_t view_stride) {
+    const bool f32 = form == kFormF32Tiles;
+    const size_t es = f32 ? 4 : 1;
+    const int run = (int)(16 / es);  // the pixels of a 16-byte run: a quarter of a tile's row, what a lane moves
+    const int tiles_x = f32 ? (W + kFTileW - 1) / kFTileW : (W + kATileW - 1) / kATileW;
+    const int tiles_y = f32 ? (H + kFTileH - 1) / kFTileH : (H + kATileH - 1) / kATileH;
+    const size_t per_view = (size_t)tiles_x * tiles_y * 128, strip = (size_t)tiles_y * (128 / es);  // in bytes; in elements
+    // (u8strip_offset, ftile_offset: a 24-bit product of the strip's number and its elements, element indices below 2^31)
+    if (per_view / es >= ((size_t)1 << 31) || strip >= ((size_t)1 << 24))
+        return fail(SC_ERR_INVALID, "mask too large for the %s gather (%d x %d)", f32 ? "float" : "byte", W, H);
     void *tiled = nullptr;
     int rc = arena_alloc(e, per_view * (size_t)V, &tiled);
     if (rc) return rc;
-    int fast = (W % 16) == 0 && (row_stride % 16) == 0 && (view_stride % 16) == 0 &&
-               (reinterpret_cast<uintptr_t>(raw_dev) % 16) == 0;
-    int64_t total = (int64_t)V * H * ((W + 15) / 16);
-    int64_t blocks = (total + kBlock - 1) / kBlock;
+    const int fast = (W % run) == 0 && (row_stride % 16) == 0 && (view_stride % 16) == 0 &&
+                     (reinterpret_cast<uintptr_t>(raw_dev) % 16) == 0;
+    const int64_t total = (int64_t)V * H * ((W + run - 1) / run);
+    const int64_t blocks = (total + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffLL) return fail(SC_ERR_INVALID, "mask batch too large");
-    // per 32x32-pixel tile: is it all 0 / all 255?  (brick form of the averaging kernel)
-    const size_t uni_per_view = (size_t)((W + 31) / 32) * (size_t)((H + 31) / 32);
+    // per 32x32-pixel region -- bytes: is it all 0 / all 255, one flag byte, for the brick form only (whole 16-byte
+    // runs); floats: is it one value, the flag bytes and then the regions' values
+    const size_t nreg = (size_t)((W + 31) / 32) * (size_t)((H + 31) / 32);
+    const size_t uni_view = f32 ? ((nreg + 3) & ~(size_t)3) + nreg * 4 : nreg;
     uint8_t *uni = nullptr;
-    if (fast && e->avg_brick) {
+    if (f32 || (fast && e->avg_brick)) {
         void *u = nullptr;
-        size_t bytes = (uni_per_view * (size_t)V + 3) & ~(size_t)3;
-        rc = arena_alloc(e, bytes, &u);
+        rc = arena_alloc(e, (uni_view * (size_t)V + 3) & ~(size_t)3, &u);
         if (rc) return rc;
         uni = static_cast<uint8_t *>(u);
     }
     LaunchTimer lt{e, SC_KERNEL_PACK};
     rc = lt.begin();
     if (rc) return rc;
-    hipLaunchKernelGGL(tile8_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, e->stream,
-                       static_cast<const uint8_t *>(raw_dev), row_stride, view_stride, W, H, V, tiles_x,
-                       tiles_y, static_cast<uint8_t *>(tiled), fast);
-    if (uni) {
-        int64_t ntiles = (int64_t)V * (int64_t)uni_per_view;
-        hipLaunchKernelGGL(uniform_tiles_kernel, dim3((uint32_t)((ntiles + 3) / 4)), dim3(kBlock), 0, e->stream,
-                           static_cast<const uint8_t *>(tiled), W, H, V, tiles_x, tiles_y, uni);
+    const dim3 grid((uint32_t)blocks), ugrid((uint32_t)(((int64_t)V * (int64_t)nreg + 3) / 4)), block(kBlock);
+    if (f32) {
+        hipLaunchKernelGGL(tilef_kernel, grid, block, 0, e->stream, static_cast<const float *>(raw_dev), row_stride,
+                           view_stride, W, H, V, tiles_x, tiles_y, static_cast<float *>(tiled), fast);
+        hipLaunchKernelGGL(uniform_f32_kernel, ugrid, block, 0, e->stream, static_cast<const float *>(tiled), W, H, V,
+                           tiles_x, tiles_y, uni, uni_view);
+    } else {
+        hipLaunchKernelGGL(tile8_kernel, grid, block, 0, e->stream, static_cast<const uint8_t *>(raw_dev), row_stride,
+                           view_stride, W, H, V, tiles_x, tiles_y, static_cast<uint8_t *>(tiled), fast);
+        if (uni)
+            hipLaunchKernelGGL(uniform_tiles_kernel, ugrid, block, 0, e->stream, static_cast<const uint8_t *>(tiled), W, H,
+                               V, tiles_x, tiles_y, uni);
     }
-    HIP_TRY(hipGetLastError());
-    rc = lt.end();
-    if (rc) return rc;
-    for (int q = 0; q < V; ++q) {
-        ViewDesc d;
-        fill_desc(e, d, K + 4 * q, R + 9 * q, t + 3 * q, static_cast<uint8_t *>(tiled) + (size_t)q * per_view, H, W,
-                  uni ? uni + (size_t)q * uni_per_view : nullptr);
-        d.tiles_x = tiles_y * 128;  // uint8 + table form: the bytes of a 16-pixel strip (u8strip_offset), not a tile count
-        d.pad = 1;
-        e->pending.push_back(d);
-    }
-    return SC_OK;
-}
-
-// averaging, float32 masks: raw device floats [V][H][W] -> 8x4 tiles + per-region uniformity; appends V
-// pending views (ViewDesc::pad == 2)
-int enqueue_tilef32(sc_engine *e, int V, const float *K, const float *R, const float *t, const void *raw_dev,
-                    int H, int W, int64_t row_stride, int64_t view_stride) {
-    const int tiles_x = (W + kFTileW - 1) / kFTileW, tiles_y = (H + kFTileH - 1) / kFTileH;
-    const size_t per_view = (size_t)tiles_x * tiles_y * 128;
-    // (ftile_offset: a 24-bit product of the strip's number and its floats, element indices below 2^32)
-    if (per_view >= ((size_t)1 << 33) || (size_t)tiles_y * 32 >= ((size_t)1 << 24))
-        return fail(SC_ERR_INVALID, "mask too large for the float gather (%d x %d)", W, H);
-    void *tiled = nullptr;
-    int rc = arena_alloc(e, per_view * (size_t)V, &tiled);
-    if (rc) return rc;
-    const int fast = (W % 4) == 0 && (row_stride % 16) == 0 && (view_stride % 16) == 0 &&
-                     (reinterpret_cast<uintptr_t>(raw_dev) % 16) == 0;
-    const int64_t total = (int64_t)V * H * ((W + 3) / 4);
-    const int64_t blocks = (total + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffLL) return fail(SC_ERR_INVALID, "mask batch too large");
-    const size_t nreg = (size_t)((W + 31) / 32) * (size_t)((H + 31) / 32);
-    const size_t uni_view = ((nreg + 3) & ~(size_t)3) + nreg * 4;  // flags, then the regions' values
-    void *u = nullptr;
-    rc = arena_alloc(e, uni_view * (size_t)V, &u);
-    if (rc) return rc;
-    uint8_t *uni = static_cast<uint8_t *>(u);
-    LaunchTimer lt{e, SC_KERNEL_PACK};
-    rc = lt.begin();
-    if (rc) return rc;
-    hipLaunchKernelGGL(tilef_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, e->stream, static_cast<const float *>(raw_dev),
-                       row_stride, view_stride, W, H, V, tiles_x, tiles_y, static_cast<float *>(tiled), fast);
-    const int64_t regs = (int64_t)V * (int64_t)nreg;
-    hipLaunchKernelGGL(uniform_f32_kernel, dim3((uint32_t)((regs + 3) / 4)), dim3(kBlock), 0, e->stream,
-                       static_cast<const float *>(tiled), W, H, V, tiles_x, tiles_y, uni, uni_view);
     HIP_TRY(hipGetLastError());
     rc = lt.end();
     if (rc) return rc;
     for (int q = 0; q < V; ++q) {
         ViewDesc d;
         fill_desc(e, d, K + 4 * q, R + 9 * q, t + 3 * q, static_cast<char *>(tiled) + (size_t)q * per_view, H, W,
-                  uni + (size_t)q * uni_view);
-        d.tiles_x = tiles_y * 32;  // float32 tiles: the floats of an 8-pixel strip (ftile_offset), not a tile count
-        d.pad = 2;
+                  uni ? uni + (size_t)q * uni_view : nullptr);
+        d.form = form;
+        d.tiles_x = (int32_t)strip;  // (the averaging forms: see ViewDesc::tiles_x)
         e->pending.push_back(d);
     }
     return SC_OK;

@@ -43,7 +43,7 @@ struct Ride {
     bool ordered;  // the pending views are in the order they will be applied already
 };
 
-// The REACH RECTANGLE of a view (ViewDesc::reserved): the 32x32 tiles of its picture that a voxel of this engine --
+// The REACH RECTANGLE of a view (ViewDesc::reach): the 32x32 tiles of its picture that a voxel of this engine --
 // planes i0 + k istride, every column, every voxel -- or a verdict about a brick or a unit of it can look at.  Readers
 // take whole bricks, those that stick out of the grid at its far y / z faces included, so the box is the engine's
 // planes x whole bricks.  Under a certified view with every corner well in front of the camera the image of that
@@ -132,11 +132,11 @@ int pack_deferred(sc_engine *e, size_t nv, Ride *r) {
     for (size_t q = 0; q < nv; ++q) {
         ViewDesc &d = e->pending[q];
         // (a slot the job has no room for is packed whole, and its descriptor says so: field and arena agree)
-        d.reserved = (e->pack_reach && q < (size_t)kReachViews) ? reach_rect(e, d) : 0;
+        d.reach = (e->pack_reach && q < (size_t)kReachViews) ? reach_rect(e, d) : 0;
         if (q < (size_t)kReachViews)
-            for (int w = 0; w < 4; ++w) pj.reach[q][w] = (uint16_t)(d.reserved >> (16 * w));
+            for (int w = 0; w < 4; ++w) pj.reach[q][w] = (uint16_t)(d.reach >> (16 * w));
         if ((int)q < ahead) {
-            const TileRect rc = rect_unpack(d.reserved, pj.tiles_x, pj.tiles_y);
+            const TileRect rc = rect_unpack(d.reach, pj.tiles_x, pj.tiles_y);
             e->pack_cnt[0] += (int64_t)std::max(0, rc.tx1 - rc.tx0) * std::max(0, rc.ty1 - rc.ty0);
             e->pack_cnt[1] += view_tiles;
         } else {
@@ -461,22 +461,41 @@ int grow_verdicts(sc_engine *e, size_t need, bool f32) {
     return SC_OK;
 }
 
+// The brick form of an averaging launch on this engine's grid (the carve's is FusedPlan): its bricks, and whether the
+// grid fits it -- element indices and brick numbers below 2^31.
+struct AvgPlan {
+    uint32_t bricks_y, bricks_z, nbricks;
+    bool fits;
+};
+AvgPlan avg_plan(const sc_engine *e) {
+    AvgPlan p{};
+    p.bricks_y = (uint32_t)((e->ny + kBrickY - 1) / kBrickY);
+    p.bricks_z = (uint32_t)((e->nz + kBrickZ - 1) / kBrickZ);
+    const uint64_t n = (uint64_t)e->planes * p.bricks_y * p.bricks_z;
+    p.fits = (uint64_t)e->npitch < 0x80000000ull && n < 0x80000000ull;
+    p.nbricks = (uint32_t)n;
+    return p;
+}
+// A view the brick form can take: tiled, with its uniformity flags, and bytes with their table.
+bool brick_view(const sc_engine *e, const ViewDesc &d) {
+    return d.occ != nullptr && ((d.form == kFormU8Strips && e->lut_dev != nullptr) || d.form == kFormF32Tiles);
+}
+
 // The brick averaging form of `nv` views (descriptors at vd, verdict buffers grown: grow_verdicts): the uniformity verdicts of every
 // (brick, view), then the bricks.  `timed`: each launch under its kernel timer.
 int launch_average_bricks(sc_engine *e, const GridDesc &g, const ViewDesc *vd, int nv, uint32_t *verdf, bool timed) {
-    const uint32_t abys = (uint32_t)((e->ny + kBrickY - 1) / kBrickY), abzs = (uint32_t)((e->nz + kBrickZ - 1) / kBrickZ);
-    const uint32_t anb = (uint32_t)((uint64_t)e->planes * abys * abzs);
+    const AvgPlan ap = avg_plan(e);
     LaunchTimer ltf{e, SC_KERNEL_FLAGS}, lta{e, SC_KERNEL_AVERAGE};
     int rc = timed ? ltf.begin() : SC_OK;
     if (rc) return rc;
-    hipLaunchKernelGGL(avg_flags_kernel, dim3((anb + kBlock - 1) / kBlock, (uint32_t)nv), dim3(kBlock), 0, e->stream,
-                       g, vd, nv, abys, abzs, anb, e->verd, verdf);
+    hipLaunchKernelGGL(avg_flags_kernel, dim3((ap.nbricks + kBlock - 1) / kBlock, (uint32_t)nv), dim3(kBlock), 0, e->stream,
+                       g, vd, nv, ap.bricks_y, ap.bricks_z, ap.nbricks, e->verd, verdf);
     rc = ltf.end();
     if (rc) return rc;
     rc = timed ? lta.begin() : SC_OK;
     if (rc) return rc;
-    hipLaunchKernelGGL(e->fresh ? average_brick_kernel<true> : average_brick_kernel<false>, dim3(anb), dim3(kBlock), 0, e->stream,
-                       static_cast<float *>(e->state.get()), g, vd, nv, e->default_value, e->lut_dev, abys, abzs, e->verd, verdf);
+    hipLaunchKernelGGL(e->fresh ? average_brick_kernel<true> : average_brick_kernel<false>, dim3(ap.nbricks), dim3(kBlock), 0, e->stream,
+                       static_cast<float *>(e->state.get()), g, vd, nv, e->default_value, e->lut_dev, ap.bricks_y, ap.bricks_z, e->verd, verdf);
     HIP_TRY(hipGetLastError());
     return lta.end();
 }
@@ -487,17 +506,15 @@ int average_batch(sc_engine *e, size_t nv, const GridDesc &g, const ViewDesc *vd
     if (vd != nullptr)
         HIP_TRY(hipMemcpyAsync(const_cast<ViewDesc *>(vd), vpin, nv * sizeof(ViewDesc), hipMemcpyHostToDevice, e->stream));
     int rc;
-    const uint32_t abys = (uint32_t)((e->ny + kBrickY - 1) / kBrickY), abzs = (uint32_t)((e->nz + kBrickZ - 1) / kBrickZ);
-    bool abrick = nv > 1 && e->avg_brick && (uint64_t)e->npitch < 0x80000000ull &&
-                  (uint64_t)e->planes * abys * abzs < 0x80000000ull;
+    const AvgPlan ap = avg_plan(e);
+    bool abrick = nv > 1 && e->avg_brick && ap.fits;
     bool any_f32 = false;
     for (size_t q = 0; q < nv && abrick; ++q) {
-        const ViewDesc &pd = e->pending[q];
-        abrick = (pd.pad == 1 && e->lut_dev != nullptr && pd.occ != nullptr) || (pd.pad == 2 && pd.occ != nullptr);
-        any_f32 |= pd.pad == 2;
+        abrick = brick_view(e, e->pending[q]);
+        any_f32 |= e->pending[q].form == kFormF32Tiles;
     }
     if (abrick) {
-        const size_t need = (size_t)e->planes * abys * abzs * nv;  // (the flat values of float32 views as well)
+        const size_t need = (size_t)ap.nbricks * nv;  // (the flat values of float32 views as well)
         rc = grow_verdicts(e, need, any_f32);
         if (rc) return rc;
         return launch_average_bricks(e, g, vd, (int)nv, any_f32 ? e->verdf.get() : nullptr, true);

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void project_selftest_kernel(uint64_t count
             for (int q = 0; q < 9; ++q) d.R[q] = r.R[q];
 #pragma unroll
             for (int q = 0; q < 3; ++q) d.t[q] = r.t[q];
-            d.mask = nullptr; d.occ = nullptr; d.W = r.W; d.H = r.H; d.tiles_x = 0; d.pad = 0;
+            d.mask = nullptr; d.occ = nullptr; d.W = r.W; d.H = r.H; d.tiles_x = 0; d.form = kFormRows;
             d.safe = r.pad[0]; d.strip = 0;  // certified by the host for the box the samples come from
             d.Wf = (float)r.W; d.Hf = (float)r.H;
             // exactly what the voxel kernels do: coordinates as backprojection.c:71-73, the x / y

@@ -51,7 +51,7 @@ struct PackJob {
     int32_t slot0, nslots;
     uint16_t order[kPackOrderMax];
     int32_t reach_on;   // SC_OPT_PACK_REACH: 0 packs whole pictures
-    uint16_t reach[kReachViews][4];  // tx0, tx1, ty0, ty1 of slot s < kReachViews (ViewDesc::reserved).  In the kernel
+    uint16_t reach[kReachViews][4];  // tx0, tx1, ty0, ty1 of slot s < kReachViews (ViewDesc::reach).  In the kernel
                                      // arguments, for the riders too: a rider that fetched its rectangle from memory
                                      // (its descriptor, or anything else) cost the dense kernel 15 vector registers --
                                      // 74 -> 89, a wavefront per SIMD less for the walkers (DESIGN_APPENDIX.md 14)

@@ -2,23 +2,35 @@
 // sc_stream, sc_pack, sc_verdicts, sc_bricks, sc_lists, sc_average, sc_misc) -- the layouts both sides share: view and grid descriptors, the control block of the survivor lists.
 
 
+// The form of a view's mask (ViewDesc::form).  Carve masks are bit tiles whatever it says (kFormRows); the averaging
+// forms are described at the top of sc_average.h.
+constexpr int32_t kFormRows = 0;      // average: float32 [H][W] row-major
+constexpr int32_t kFormU8Strips = 1;  // average: uint8 in strips of 16x8-pixel tiles, plus the 256-entry table
+constexpr int32_t kFormF32Tiles = 2;  // average: float32 in strips of 8x4-pixel tiles
+
 struct ViewDesc {   // 128 bytes, read with scalar loads (the view index is wave-uniform)
     float K[4];     // fx fy cx cy
     float R[9];     // row-major
     float t[3];
     const void *mask;  // carve: bit words, 32 x 32-pixel tiles strip by strip (tile (tx, ty) at word tx * strip + 32 ty); average: tiled bytes / floats
     int32_t W, H;
-    int32_t tiles_x;
-    int32_t pad;
+    int32_t tiles_x;     // carve, kFormRows: columns of 32x32-pixel tiles across the picture = (W + 31) / 32, the row pitch
+                         // of `occ` and `cmask`.  kFormU8Strips / kFormF32Tiles: NOT a tile count but the size of a strip of
+                         // the tiles -- the bytes of a 16-pixel-wide strip (u8strip_offset) / the floats of an 8-pixel-wide
+                         // one (ftile_offset); their kernels work (W + 31) >> 5 out.  (Kept here, not in `strip`: read
+                         // from there, average_multi_kernel<4, *> allocates its registers another way and takes 2.8 %
+                         // longer -- profiles/average_forms_ab.json)
+    int32_t form;        // kFormRows / kFormU8Strips / kFormF32Tiles
     float Wf, Hf;
-    const uint8_t *occ;  // carve: one byte per 32x32 tile: bit 0 some foreground, bit 1 only foreground
+    const uint8_t *occ;  // carve: one byte per 32x32 tile: bit 0 some foreground, bit 1 only foreground; average: the
+                         // uniformity flags per 32x32 region (uniform_tiles_kernel, uniform_f32_kernel), null: none
     int32_t safe;        // certify_view(): every voxel centre of the grid has 2^-10 < pz and |px|, |py|, pz < 2^30
                          // under this pose, and the intrinsics are finite and below 2^30 (see project())
     int32_t strip;       // carve: the words of a 32-pixel-wide STRIP of the bit tiles = 32 x tile rows (mask_byte_offset)
     const uint32_t *cmask;  // carve, 16-byte pack form: per 32x32 tile the 4x4 map of its 8x8-pixel CELLS -- bits 0..15
                             // "cell holds some foreground", bits 16..31 "cell holds some background" (cell (cx, cy) of
                             // the tile at bit cy * 4 + cx; padding counts as background); null: no cell level
-    uint64_t reserved;   // carve, a batch packed at its flush: the REACH RECTANGLE of the view in 32x32 tiles, four
+    uint64_t reach;      // carve, a batch packed at its flush: the REACH RECTANGLE of the view in 32x32 tiles, four
                          // uint16 -- tx0 | tx1 << 16 | ty0 << 32 | ty1 << 48, tiles [tx0, tx1) x [ty0, ty1) -- outside of
                          // which no voxel of the engine can land (reach_rect, sc_flush.inl) and the packed arena holds
                          // whatever an earlier batch left; tx1 == 0: the whole picture -- also for a view the
@@ -26,6 +38,9 @@ struct ViewDesc {   // 128 bytes, read with scalar loads (the view index is wave
                          // reads it here), which is packed whole.
 };
 static_assert(sizeof(ViewDesc) == 128, "ViewDesc layout");
+static_assert(offsetof(ViewDesc, tiles_x) == 80 && offsetof(ViewDesc, form) == 84 && offsetof(ViewDesc, strip) == 108 &&
+                  offsetof(ViewDesc, reach) == 120,
+              "ViewDesc layout: no field moved when `pad` and `reserved` got their names");
 // Descriptor `i` (wave-uniform) by SCALAR loads, whatever the compiler knows about the pointer: through the constant
 // address space.  A pointer that reaches a kernel inside a struct carries no no-alias promise, so its loads are kept
 // coherent with the kernel's own stores -- seven vector loads per lane for a descriptor (round 4: 9 M of them per
@@ -54,7 +69,8 @@ struct GridDesc {
     uint64_t ngroups;   // columns owned * gpc
     uint32_t istride;   // global x step between the engine's planes (1: slab, W: plane-cyclic)
     uint32_t nzp;       // row pitch of the state in voxels: nz rounded up to a multiple of 64 (a row = one
-                        // (plane, column) run of nz voxels, 256-byte aligned; the padding is never read back)
+                        // (plane, column) run of nz voxels, 256-byte aligned; the padding is never read back).
+                        // nzp % 64 == 0 is create()'s doing: every 4-voxel group is one aligned int4 / float4
     FastDiv by_nzp, by_ny;  // for the survivor stages' decode of an entry (an element index below 2^31)
 };
 

@@ -138,6 +138,15 @@ __device__ __forceinline__ Footprint brick_footprint(const ViewDesc &d, const Gr
     return fpr;
 }
 
+// What a view says about a brick (brick_verdict, brick_flat_f32, the averaging flags kernels) or a rectangle of voxels
+// (rect_verdict_cells):
+constexpr uint32_t kVerdictMixed = 0u;    // nothing known: the voxels are projected one by one
+constexpr uint32_t kVerdictEmpty = 1u;    // every voxel in-image over background only (carve: all carved; average: table[0])
+constexpr uint32_t kVerdictFull = 2u;     // every voxel in-image over foreground only (carve: all kept; average: table[255])
+constexpr uint32_t kVerdictFlat = 3u;     // average, float32 masks: every voxel in-image over ONE value, whose bits come along
+constexpr uint32_t kVerdictOutside = 4u;  // no voxel is in front of the camera and inside the picture: the view does nothing
+constexpr uint32_t kVerdictInside = 5u;   // average: mixed, but every voxel inside the picture -- projected without its test
+
 // Verdict of a view about a rectangle of voxels at the CELL level (8x8 pixels, ViewDesc::cmask): every voxel
 // of the rectangle lands in-image on a pixel of the box, so when no cell under the box holds foreground the
 // view carves them all (EMPTY, 1: backprojection.c:79), when none holds background it keeps them all (FULL,
@@ -183,8 +192,8 @@ __device__ __forceinline__ void window_cells(const ViewDesc &d, int cx0, int cx1
 __device__ __forceinline__ uint32_t rect_verdict_cells(const ViewDesc &d, const GridDesc &g, float x, int j0, int j1,
                                                        int k0, int k1) {
     const PixelBox bx = rect_box(d, g, x, j0, j1, k0, k1);
-    if (bx.outside) return 4u;
-    if (!bx.inside) return 0u;
+    if (bx.outside) return kVerdictOutside;
+    if (!bx.inside) return kVerdictMixed;
     const int cx0 = (int)bx.umin >> kCellShift, cx1 = (int)bx.umax >> kCellShift;
     const int cy0 = (int)bx.vmin >> kCellShift, cy1 = (int)bx.vmax >> kCellShift;
     const int tx0 = cx0 >> 2, ty0 = cy0 >> 2;
@@ -192,21 +201,21 @@ __device__ __forceinline__ uint32_t rect_verdict_cells(const ViewDesc &d, const 
     // a 3 x 3 window or one of three shapes of 16 tiles; the lanes of a wavefront ask about one rectangle of
     // voxels from cameras of one rig, so they mostly agree on the shape and one of the four runs
     const int shape = (nxw <= 3 && nyw <= 3) ? 4 : ((nxw <= 2 && nyw <= 8) ? 1 : ((nxw <= 4 && nyw <= 4) ? 2 : ((nxw <= 8 && nyw <= 2) ? 3 : 0)));
-    if (shape == 0) return 0u;
+    if (shape == 0) return kVerdictMixed;
     uint32_t fg = 0, bg = 0;
     if (shape == 4) window_cells<3, 3>(d, cx0, cx1, cy0, cy1, tx0, ty0, nxw, nyw, fg, bg);  // the usual one: a square unit
     if (shape == 1) window_cells<2, 8>(d, cx0, cx1, cy0, cy1, tx0, ty0, nxw, nyw, fg, bg);
     if (shape == 2) window_cells<4, 4>(d, cx0, cx1, cy0, cy1, tx0, ty0, nxw, nyw, fg, bg);
     if (shape == 3) window_cells<8, 2>(d, cx0, cx1, cy0, cy1, tx0, ty0, nxw, nyw, fg, bg);
-    return fg == 0u ? 1u : (bg == 0u ? 2u : 0u);
+    return fg == 0u ? kVerdictEmpty : (bg == 0u ? kVerdictFull : kVerdictMixed);
 }
 
 __device__ __forceinline__ uint32_t brick_verdict(const ViewDesc &d, const GridDesc &g, float x, int j0,
                                                   int k0, int occ_tx, bool *all_inside = nullptr) {
     const Footprint fpr = brick_footprint(d, g, x, j0, k0);
     if (all_inside != nullptr) *all_inside = fpr.inside;  // (for the averaging kernel: no voxel needs its picture test)
-    if (fpr.outside) return 4u;  // OUTSIDE: the view does nothing to the brick
-    if (!fpr.ok) return 0u;
+    if (fpr.outside) return kVerdictOutside;  // the view does nothing to the brick
+    if (!fpr.ok) return kVerdictMixed;
     uint32_t any = 0, all = 3;
     if (occ_tx >= 8) {
         // A tile row's bytes lie side by side: EIGHT of them in one (unaligned) load, four tile rows per turn -- the
@@ -239,20 +248,20 @@ __device__ __forceinline__ uint32_t brick_verdict(const ViewDesc &d, const GridD
     }
     // every voxel of the brick lands in-image on a pixel of these tiles: all of them background
     // (EMPTY: the view carves the whole brick) or all of them foreground (FULL: the view keeps it)
-    return (any & 1u) == 0 ? 1u : ((all & 2u) != 0 ? 2u : 0u);
+    return (any & 1u) == 0 ? kVerdictEmpty : ((all & 2u) != 0 ? kVerdictFull : kVerdictMixed);
 }
 
-// float32 masks of the averaging kernel (tiled form, ViewDesc::pad == 2): behind the per-region flags
+// float32 masks of the averaging kernel (kFormF32Tiles): behind the per-region flags
 // (d.occ: 1 = every pixel of the 32x32 region holds the same float, bit for bit) come the regions'
 // values.  A footprint over regions that all hold ONE value adds that value to every voxel of the brick
-// (backprojection.c:54) without projecting any: returns 3 and the value's bits, else 0.
+// (backprojection.c:54) without projecting any: kVerdictFlat and the value's bits, else kVerdictMixed.
 __device__ __forceinline__ uint32_t brick_flat_f32(const ViewDesc &d, const GridDesc &g, float x, int j0, int k0,
                                                    uint32_t &bits, bool *all_inside = nullptr) {
     const Footprint fpr = brick_footprint(d, g, x, j0, k0);
     if (all_inside != nullptr) *all_inside = fpr.inside;
     bits = 0u;
-    if (fpr.outside) return 4u;  // the view adds nothing to the brick
-    if (!fpr.ok) return 0u;
+    if (fpr.outside) return kVerdictOutside;  // the view adds nothing to the brick
+    if (!fpr.ok) return kVerdictMixed;
     const int otx = (d.W + 31) >> 5, oty = (d.H + 31) >> 5;
     const uint32_t *val = reinterpret_cast<const uint32_t *>(d.occ + (((size_t)otx * oty + 3) & ~(size_t)3));
     const uint32_t first = load_cells(val, (uint32_t)(fpr.ty0 * otx + fpr.tx0));
@@ -261,7 +270,7 @@ __device__ __forceinline__ uint32_t brick_flat_f32(const ViewDesc &d, const Grid
         for (int tx = fpr.tx0; tx <= fpr.tx1; ++tx)
             flat &= load_occ(d.occ, (uint32_t)(ty * otx + tx)) != 0 && load_cells(val, (uint32_t)(ty * otx + tx)) == first;
     bits = first;
-    return flat ? 3u : 0u;
+    return flat ? kVerdictFlat : kVerdictMixed;
 }
 
 // The emptiness verdict of every brick ahead of the dense kernel: flags[brick] = 1 when ANY of the

@@ -1784,3 +1784,34 @@ def test_average_of_bricks_no_view_sees(gpu_device, form, log):
             got = e.get_values()
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (form, log, default_value, vpl)
             e.close()
+
+
+def test_average_brick_form_on_stored_sums_with_mixed_forms(gpu_device):
+    """One batch that mixes uint8 + table views (odd) and float32 views (even: flat, grey, flat, grey) goes through the
+    brick form twice: on the fresh volume, and again on the stored sums -- the float32 tiled form and the mixed batch
+    in the brick kernel with the sums read back.  Bricks stick out in y and z, nz % 4 != 0, whole 16-pixel rows (the
+    uint8 views get their uniformity flags).  Both volumes equal the oracle's bit for bit, brick form on and off."""
+    shape = (5, 37, 131)
+    _, origin, vs, views = scene(shape, 7, "plant", width=208, height=96, fx=150.0, fy=150.0, cx=100.0, cy=45.0)
+    table = averaging_table(False)
+    rng = np.random.default_rng(17)
+    masks = []
+    for q, (_, _, _, m) in enumerate(views):
+        if q % 2:
+            masks.append(np.ascontiguousarray(m))                       # uint8 binary
+        elif q % 4 == 0:
+            masks.append(np.ascontiguousarray(img_as_float32(m)))       # float32, flat nearly everywhere
+        else:
+            masks.append(rng.random(m.shape, dtype=np.float32))         # float32, grey
+    fviews = [(K, R, t, table[m] if m.dtype == np.uint8 else m) for (K, R, t, _), m in zip(views, masks)]
+    want1 = oracle_c.average(list(shape), origin, vs, fviews, default_value=0.25)
+    want2 = oracle_c.average(list(shape), origin, vs, fviews + fviews, default_value=0.25)
+    for brick in (1, 0):
+        e = nat.Engine(shape, origin, vs, nat.SC_MODE_AVERAGE, default_value=0.25)
+        e.set_option(nat.SC_OPT_AVG_BRICK, brick)
+        e.set_lut(table)
+        for want, state in ((want1, "fresh"), (want2, "stored")):
+            for (K, R, t, _), m in zip(views, masks):
+                e.process_view(K, R, t, m, nat.SC_MASK_U8_LUT if m.dtype == np.uint8 else nat.SC_MASK_F32)
+            assert np.array_equal(e.get_values().view(np.uint32), want.view(np.uint32)), (brick, state)
+        e.close()
