@@ -723,6 +723,45 @@ int sc_nearest_confusion(const int32_t *index, const int32_t *query_labels, int 
 const char *sc_nearest_last_error(void);
 void sc_nearest_release(void);
 
+/*
+ * The k nearest points of another cloud: what open3d's KDTreeFlann.search_knn_vector_3d(p, k) computes
+ * for the reference's knn_graph (plant3dvision/proc3d.py:160-183) and the stem walk of
+ * angles_and_internodes_from_point_cloud (plant3dvision/arabidopsis.py:417-433), for Q queries at once, on the GPU.
+ * Parity unpinned as above: the rules restate nanoflann's search in an order-free form.
+ *   K1. d2 is N1's, bit for bit;
+ *   K2. the key of a target is (d2, index), compared lexicographically; the answer for a query is the
+ *       min(k, matched targets) smallest keys IN RISING KEY ORDER.  Keys are distinct, so the answer does not depend
+ *       on the order of visiting; a tie at the k-th place goes to the smaller index;
+ *   K3. with max_distance > 0 only targets with d2 < max_distance * max_distance count (strict, the product rounded
+ *       once, as N3);
+ *   K4. row q of index_out and d2_out has k places; the unused ones, after the used ones, hold index -1 and
+ *       d2 = +inf.  P == 0: every place is unused and no device call is made (device outputs are refused then);
+ *       Q == 0: nothing is written;
+ *   K5. refused (SC_ERR_INVALID, before any device call): what N5 and sc_nearest refuse, k outside 1 .. SC_KNN_MAX,
+ *       Q * k >= 2^31, a NULL index_out or d2_out.  Non-finite coordinates in device arrays are refused by the first
+ *       kernels, as in sc_nearest;
+ *   K6. k == 1 gives exactly sc_nearest's index and d2.
+ * The search is exact for every finite input: sc_nearest's grid, planned for about `aim` targets per cell (a function
+ * of k), one wavefront per query with its sorted list of k keys in LDS (12 k bytes), rings of cells until the proved
+ * lower bound on what is unvisited exceeds the k-th d2 strictly, and for queries that four rings do not settle a pass
+ * over all P targets, one wavefront per query.
+ *
+ * index_out [Q][k] int32 and d2_out [Q][k] double live where out_on_device says.  far_out: NULL, or one host int64
+ * that receives the number of queries the pass over all targets took: the call then ends in a wait, as it does with
+ * host outputs; otherwise it returns with the rest enqueued after its one mid-way wait (the finite flags and the box).
+ * Errors are read with sc_nearest_last_error; the work buffers are sc_nearest's (plus 12 k bytes per query for host
+ * outputs) and sc_nearest_release gives them back.
+ * sc_knn_set_aim: the targets per cell the grid aims at, for measurements (tools/bench_knn.py); 0 restores the
+ * built-in function of k.  No answer depends on it.
+ */
+#define SC_KNN_MAX 512 /* the reference's largest k (300) rounded up to a power of two */
+int sc_knn(const double *queries, int queries_on_device, int64_t Q,
+           const double *targets, int targets_on_device, int64_t P,
+           int k, double max_distance, int device,
+           int32_t *index_out /* [Q, k] */, double *d2_out /* [Q, k] */, int out_on_device,
+           int64_t *far_out /* host, may be null */, void *hip_stream);
+void sc_knn_set_aim(int aim);
+
 /* Page-locked host memory for the read-back of sc_get_values (no reference counterpart: the
  * reference's values_h is a pageable NumPy array, cl.py:173).  A 512 MiB volume reads back in
  * ~10 ms into such a buffer against ~50 ms into pageable memory, but allocating it takes ~0.1 s

@@ -19,11 +19,15 @@
 // only traffic between blocks inside a launch is integer atomics (the histogram, the cursors, the far list's
 // length, the confusion counts), and nothing depends on their order.  Stand-alone unit: nothing shared with the engine;
 // N1 (dist2), the finite launch and the host's judge of non-finite coordinates are sc_points.h, shared with dbscan.hip.
+//
+// sc_knn (rules K1-K6 in include/spacecarve.h) is the same search for the k nearest: the same launches up
+// to the scatter on a grid planned for fewer, fuller cells, then knn_rings and knn_far, one wavefront per query.
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -177,6 +181,148 @@ __global__ __launch_bounds__(kB) void nearest_far_kernel(const double *__restric
     }
 }
 
+// ---- the k nearest: one wavefront per query --------------------------------------------------------------
+// The list of a query -- up to k keys (d2, index) in rising order, sc_nearest.h's KList -- lives in LDS, private to its
+// wavefront: k doubles and k ints of the block's dynamic LDS (12 k bytes per wavefront, 24 KiB per block at SC_KNN_MAX).
+// Lanes exchange list entries through LDS only; lds_order() stands between every write of one lane and the read of
+// another: a wavefront-scope fence, which keeps the compiler from moving a lane's accesses across it (the hardware
+// runs a wavefront's LDS instructions in order), and the wavefront barrier.  Blocks and wavefronts never wait on one
+// another: there is no __syncthreads() in these kernels, so a wavefront without a query simply leaves.
+__device__ __forceinline__ void lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+
+struct WaveList {
+    double *ld;     // LDS, [k]
+    int *li;        // LDS, [k]
+    int k, n, lane; // n: keys held, the same in every lane
+    double kd;      // the k-th key once n == k, the same in every lane
+    int ki;
+    double md2;
+
+    // Every lane brings one key or none (`have`).  Keys not below md2 (K3) or not below the k-th of a full list are
+    // dropped by comparison; the survivors, found by ballot, are inserted one after the other, each tested again
+    // against the k-th as it stands by then.  An insertion walks the list from its top in pieces of 64 places: a piece
+    // is read, its keys above the new one are written one place up (the one pushed past place k - 1 is dropped), and
+    // the first piece that holds a key below the new one gives its place.  At most ceil(k / 64) pieces per insertion.
+    __device__ __forceinline__ void offer(double d, int i, bool have) {
+        unsigned long long m = __ballot(have && d < md2 && (n < k || nn::key_less(d, i, kd, ki)));
+        while (m) {
+            const int src = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const double bd = __shfl(d, src, 64);
+            const int bi = __shfl(i, src, 64);
+            if (n == k && !nn::key_less(bd, bi, kd, ki)) continue;
+            int pos = 0;
+            for (int c = (n - 1) >> 6; c >= 0; --c) {  // n = 0: no piece
+                const int j = (c << 6) + lane;
+                const bool in = j < n;
+                const double ed = in ? ld[j] : 0.0;
+                const int ei = in ? li[j] : 0;
+                const bool below = in && nn::key_less(ed, ei, bd, bi);  // a prefix of the piece: the list is sorted
+                lds_order();
+                if (in && !below && j + 1 < k) {
+                    ld[j + 1] = ed;
+                    li[j + 1] = ei;
+                }
+                lds_order();
+                const int cnt = __popcll(__ballot(below));
+                if (cnt) {
+                    pos = (c << 6) + cnt;
+                    break;
+                }
+            }
+            if (lane == 0) {  // pos < k: the new key is below the k-th of a full list, or the list has room
+                ld[pos] = bd;
+                li[pos] = bi;
+            }
+            lds_order();
+            if (n < k) n = __builtin_amdgcn_readfirstlane(n + 1);
+            if (n == k) {
+                kd = ld[k - 1];
+                ki = li[k - 1];
+            }
+        }
+    }
+
+    // row q of the outputs: the keys held, then K4's unused places
+    __device__ __forceinline__ void write_row(int32_t *__restrict__ index, double *__restrict__ d2, uint32_t q) const {
+        for (int j = lane; j < k; j += 64) {
+            index[(size_t)q * k + j] = j < n ? li[j] : -1;
+            d2[(size_t)q * k + j] = j < n ? ld[j] : HUGE_VAL;
+        }
+    }
+};
+
+__device__ __forceinline__ WaveList wave_list(int k, double md2) {
+    extern __shared__ double knn_lds[];  // [kB / 64][k] doubles, then as many ints
+    const int wave = (int)(threadIdx.x >> 6);
+    WaveList l;
+    l.ld = knn_lds + (size_t)wave * k;
+    l.li = reinterpret_cast<int *>(knn_lds + (size_t)(kB / 64) * k) + (size_t)wave * k;
+    l.k = k;
+    l.n = 0;
+    l.lane = (int)(threadIdx.x & 63);
+    l.kd = HUGE_VAL;
+    l.ki = 0x7fffffff;
+    l.md2 = md2;
+    return l;
+}
+
+// rings: the walk of sc_nearest.h's knn_ring_search with the 64 lanes on 64 sorted slots at a time.  A settled query
+// writes its own row; an unsettled one appends its number to the far list (capacity Q) and writes nothing.  nfar is
+// only added to here and only read by the next launch.  The grid is not capped: ceil(Q / 4) blocks, below 2^29.
+__global__ __launch_bounds__(kB) void knn_rings_kernel(const double *__restrict__ qs, int Q, nn::Grid g, const uint32_t *__restrict__ start,
+                                                       const double *__restrict__ spts, const int *__restrict__ sidx, int k,
+                                                       int32_t *__restrict__ index, double *__restrict__ d2, int *__restrict__ far,
+                                                       unsigned int *nfar) {
+    const uint32_t q = blockIdx.x * (kB / 64) + (threadIdx.x >> 6);  // the same in every lane of a wavefront
+    if (q >= (uint32_t)Q) return;
+    WaveList list = wave_list(k, g.md2);
+    const double qx = qs[3 * (size_t)q], qy = qs[3 * (size_t)q + 1], qz = qs[3 * (size_t)q + 2];
+    const int cx = nn::cell_of(qx, g.lo[0], g.h, g.n[0]), cy = nn::cell_of(qy, g.lo[1], g.h, g.n[1]), cz = nn::cell_of(qz, g.lo[2], g.h, g.n[2]);
+    const int last = nn::last_ring(g, cx, cy, cz);
+    bool settled = false;
+    for (int r = 0; r <= nn::kNearRings && !settled; ++r) {
+        nn::for_ring_runs(g, cx, cy, cz, r, start, [&](uint32_t t0, uint32_t t1) {
+            for (uint32_t b = t0; b < t1; b += 64) {  // t1 <= P < 2^31: b + 64 does not wrap
+                const uint32_t t = b + list.lane;
+                const bool have = t < t1;
+                const size_t s = have ? t : t0;
+                list.offer(nn::dist2(qx, qy, qz, spts[3 * s], spts[3 * s + 1], spts[3 * s + 2]), sidx[s], have);
+            }
+        });
+        settled = nn::knn_settled(g, r, last, list.n == list.k, list.kd);
+    }
+    if (settled)
+        list.write_row(index, d2, q);
+    else if (list.lane == 0)
+        far[atomicAdd(nfar, 1u)] = (int)q;
+}
+
+// far: one wavefront per query of the far list, the list started empty, all P targets in their original order.
+// O(P) per query whatever the data are.
+__global__ __launch_bounds__(kB) void knn_far_kernel(const double *__restrict__ qs, const double *__restrict__ pts, int P, double md2, int k,
+                                                     const int *__restrict__ far, const unsigned int *__restrict__ nfar,
+                                                     int32_t *__restrict__ index, double *__restrict__ d2) {
+    const unsigned int n = *nfar, waves = gridDim.x * (kB / 64);
+    for (unsigned int w = blockIdx.x * (kB / 64) + (threadIdx.x >> 6); w < n; w += waves) {
+        const int q = far[w];
+        const double qx = qs[3 * (size_t)q], qy = qs[3 * (size_t)q + 1], qz = qs[3 * (size_t)q + 2];
+        WaveList list = wave_list(k, md2);
+        for (uint32_t b = 0; b < (uint32_t)P; b += 64) {
+            const uint32_t t = b + list.lane;
+            const bool have = t < (uint32_t)P;
+            const size_t s = have ? t : 0;
+            list.offer(nn::dist2(qx, qy, qz, pts[3 * s], pts[3 * s + 1], pts[3 * s + 2]), (int)s, have);
+        }
+        list.write_row(index, d2, (uint32_t)q);
+        lds_order();  // the next query's list takes the same places
+    }
+}
+
 // ---- sums (N6) -----------------------------------------------------------------------------------------------------------
 // A thread adds its queries in rising index, a block adds its threads by a tree, and block b leaves its three partials
 // at partial[3 b]: the order is a function of Q, kB and the block count.
@@ -257,6 +403,8 @@ __global__ __launch_bounds__(kB) void nearest_confusion_kernel(const int32_t *__
 // ---- host side -----------------------------------------------------------------------------------------------------------
 // Work buffers are kept per device: the slot protocol of sc_unit.h.  Both entries share the slot.
 WorkSlot g_slots[kUnitDevices];
+
+std::atomic<int> g_knn_aim{0};  // sc_knn_set_aim: targets per cell sc_knn's grid aims at; 0: nn::knn_aim(k)
 
 }  // namespace
 
@@ -369,6 +517,120 @@ int sc_nearest(const double *queries, int queries_on_device, int64_t Q, const do
             UNIT_TRY(hipStreamSynchronize(stream));
             if (sums_out)
                 for (int k = 0; k < 3; ++k) sums_out[k] = hh.sums[k];
+        }
+    }
+
+done:
+    return rc;
+}
+
+void sc_knn_set_aim(int aim) { g_knn_aim.store(aim > 0 ? aim : 0); }
+
+int sc_knn(const double *queries, int queries_on_device, int64_t Q, const double *targets, int targets_on_device, int64_t P, int k,
+           double max_distance, int device, int32_t *index_out, double *d2_out, int out_on_device, int64_t *far_out, void *hip_stream) {
+    // every argument is judged before the first device call
+    if (Q < 0 || Q >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "Q must be 0 .. 2^31 - 1");
+    if (P < 0 || P >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "P must be 0 .. 2^31 - 1");
+    if (k < 1 || k > SC_KNN_MAX) return g_err.fail(SC_ERR_INVALID, "k must be 1 .. SC_KNN_MAX (512)");
+    if (Q * k >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "Q * k must be below 2^31");
+    if ((Q > 0 && !queries) || (P > 0 && !targets)) return g_err.fail(SC_ERR_INVALID, "null argument (queries, targets)");
+    if (!index_out || !d2_out) return g_err.fail(SC_ERR_INVALID, "null argument (index_out, d2_out)");
+    if (!std::isfinite(max_distance)) return g_err.fail(SC_ERR_INVALID, "max_distance must be finite (<= 0: unbounded)");
+    if (max_distance > 0.0 && (!(max_distance * max_distance >= DBL_MIN) || !std::isfinite(max_distance * max_distance)))
+        return g_err.fail(SC_ERR_INVALID, "max_distance * max_distance must be a normal number (max_distance out of range)");
+    if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
+    if (P == 0 && Q > 0 && out_on_device) return g_err.fail(SC_ERR_INVALID, "P == 0 makes no device call: device outputs cannot be filled");
+    if (!queries_on_device && first_non_finite(g_err, queries, Q, "query") != SC_OK) return SC_ERR_INVALID;
+    if (!targets_on_device && first_non_finite(g_err, targets, P, "target") != SC_OK) return SC_ERR_INVALID;
+    if (far_out) *far_out = 0;
+    if (Q == 0) return SC_OK;
+    const int64_t words = Q * k;  // below 2^31
+    if (P == 0) {  // K4
+        for (int64_t w = 0; w < words; ++w) {
+            index_out[w] = -1;
+            d2_out[w] = HUGE_VAL;
+        }
+        return SC_OK;
+    }
+
+    const int nq = (int)Q, np = (int)P;
+    const int64_t cap = nn::cell_cap(P);
+    const uint32_t pblocks = (uint32_t)((P + kB - 1) / kB), qwave_blocks = (uint32_t)((Q + kB / 64 - 1) / (kB / 64));
+    const int box_parts = (int)std::min<uint32_t>(pblocks, kPartials);
+    const size_t lds = (size_t)(kB / 64) * (size_t)k * 12;  // the lists of a block: at most 24 KiB
+    const int set_aim = g_knn_aim.load(), aim = set_aim > 0 ? set_aim : nn::knn_aim(k);
+
+    int rc = SC_OK;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    UnitCall call(g_err, g_slots, device, stream, rc);
+    size_t tmp = 0;
+    Header hh;
+    nn::Grid g;
+
+    // layout of the work buffer: sc_nearest's, with k places per query in the staged outputs
+    Layout lay;
+    const size_t o_hdr = lay.take(sizeof(Header)), o_part = lay.take((size_t)kPartials * 6 * 8);
+    const size_t o_count = lay.take(((size_t)cap + 1) * 4), o_start = lay.take(((size_t)cap + 1) * 4), o_cursor = lay.take(((size_t)cap + 1) * 4);
+    const size_t o_spts = lay.take((size_t)P * 24), o_sidx = lay.take((size_t)P * 4), o_far = lay.take((size_t)Q * 4);
+    const size_t o_qs = lay.take(queries_on_device ? 0 : (size_t)Q * 24), o_ts = lay.take(targets_on_device ? 0 : (size_t)P * 24);
+    const size_t o_idx = lay.take(out_on_device ? 0 : (size_t)words * 4), o_d2 = lay.take(out_on_device ? 0 : (size_t)words * 8);
+    size_t o_tmp = 0;  // the scan's temporary storage: the last buffer, sized below
+
+    if ((rc = call.enter()) != SC_OK) goto done;
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(cap + 1), stream));
+    o_tmp = lay.take(tmp);
+    if ((rc = call.grow(lay.total)) != SC_OK) goto done;
+    {
+        char *const w = call.sl.base;
+        Header *hdr = reinterpret_cast<Header *>(w + o_hdr);
+        double *partial = reinterpret_cast<double *>(w + o_part);
+        uint32_t *count = reinterpret_cast<uint32_t *>(w + o_count), *start = reinterpret_cast<uint32_t *>(w + o_start),
+                 *cursor = reinterpret_cast<uint32_t *>(w + o_cursor);
+        double *spts = reinterpret_cast<double *>(w + o_spts);
+        int *sidx = reinterpret_cast<int *>(w + o_sidx), *far = reinterpret_cast<int *>(w + o_far);
+        const double *qs_d = queries_on_device ? queries : reinterpret_cast<const double *>(w + o_qs);
+        const double *ts_d = targets_on_device ? targets : reinterpret_cast<const double *>(w + o_ts);
+        int32_t *idx_d = out_on_device ? index_out : reinterpret_cast<int32_t *>(w + o_idx);
+        double *d2_d = out_on_device ? d2_out : reinterpret_cast<double *>(w + o_d2);
+        void *tmp_d = w + o_tmp;
+
+        UNIT_TRY(call.sl.wait(stream));
+        if (!queries_on_device) UNIT_TRY(hipMemcpyAsync(w + o_qs, queries, (size_t)Q * 24, hipMemcpyHostToDevice, stream));
+        if (!targets_on_device) UNIT_TRY(hipMemcpyAsync(w + o_ts, targets, (size_t)P * 24, hipMemcpyHostToDevice, stream));
+        UNIT_TRY(hipMemsetAsync(hdr, 0, sizeof(Header), stream));
+        hipLaunchKernelGGL(nearest_box_kernel, dim3(box_parts), dim3(kB), 0, stream, ts_d, np, &hdr->bad_targets, partial);
+        hipLaunchKernelGGL(nearest_box_final_kernel, dim3(1), dim3(kB), 0, stream, partial, box_parts, hdr->box);
+        launch_points_finite(stream, qs_d, Q, &hdr->bad_queries);
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpyAsync(&hh, hdr, sizeof(Header), hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(call.sl.record(stream));
+        UNIT_TRY(hipStreamSynchronize(stream));  // the call's one mid-way wait
+        if (hh.bad_queries != 0u || hh.bad_targets != 0u) {  // device points: the first kernels are the judge
+            rc = g_err.fail(SC_ERR_INVALID, hh.bad_queries ? "non-finite coordinate in the device queries" : "non-finite coordinate in the device targets");
+            goto done;
+        }
+        nn::plan_grid(hh.box, hh.box + 3, std::max<int64_t>(1, P / aim), max_distance, g);  // about `aim` targets per cell
+        const int ncell = g.n[0] * g.n[1] * g.n[2];  // <= cell_cap(P / aim) <= cap
+
+        UNIT_TRY(hipMemsetAsync(count, 0, ((size_t)ncell + 1) * 4, stream));
+        hipLaunchKernelGGL(nearest_hist_kernel, dim3(pblocks), dim3(kB), 0, stream, ts_d, np, g, count);
+        UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp, count, start, ncell + 1, stream));
+        UNIT_TRY(hipMemcpyAsync(cursor, start, (size_t)ncell * 4, hipMemcpyDeviceToDevice, stream));
+        hipLaunchKernelGGL(nearest_scatter_kernel, dim3(pblocks), dim3(kB), 0, stream, ts_d, np, g, cursor, spts, sidx);
+        hipLaunchKernelGGL(knn_rings_kernel, dim3(qwave_blocks), dim3(kB), lds, stream, qs_d, nq, g, start, spts, sidx, k, idx_d, d2_d, far,
+                           &hdr->nfar);
+        hipLaunchKernelGGL(knn_far_kernel, dim3(std::min<uint32_t>(qwave_blocks, kFarBlocks)), dim3(kB), lds, stream, qs_d, ts_d, np, g.md2, k, far,
+                           &hdr->nfar, idx_d, d2_d);
+        UNIT_TRY(hipGetLastError());
+        if (!out_on_device) {
+            UNIT_TRY(hipMemcpyAsync(index_out, idx_d, (size_t)words * 4, hipMemcpyDeviceToHost, stream));
+            UNIT_TRY(hipMemcpyAsync(d2_out, d2_d, (size_t)words * 8, hipMemcpyDeviceToHost, stream));
+        }
+        if (far_out) UNIT_TRY(hipMemcpyAsync(&hh.nfar, &hdr->nfar, 4, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(call.sl.record(stream));
+        if (far_out || !out_on_device) {
+            UNIT_TRY(hipStreamSynchronize(stream));
+            if (far_out) *far_out = (int64_t)hh.nfar;
         }
     }
 

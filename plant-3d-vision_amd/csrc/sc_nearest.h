@@ -2,7 +2,8 @@
 // plan of the dense grid over the targets, the cell of a coordinate, the ring walk of one query with its stop rule.
 // (N1's dist2 is sc_points.h's, shared with dbscan.hip.)
 // Host and device: nearest.hip runs it one thread per query; tools/nearest_rehearsal.cpp runs the same text on the
-// CPU, one query after the other, against all pairs.
+// CPU, one query after the other, against all pairs.  The k nearest follow at the end: the stop rule
+// for the k-th place, the enumeration of a ring's runs, and the serial form of the list nearest.hip keeps per wavefront.
 #pragma once
 
 #include <cfloat>
@@ -179,5 +180,96 @@ SC_HD bool ring_search(const Grid &g, const uint32_t *__restrict__ start, const 
     }
     return false;
 }
+
+// ---- the k nearest --------------------------------------------------------------------------------
+// K2: the key of a target is (d2, index), compared lexicographically; keys of one query are distinct.
+SC_HD bool key_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
+
+// The least ring that reaches the grid's far faces on every axis: after it nothing is unvisited.
+SC_HD int last_ring(const Grid &g, int cx, int cy, int cz) {
+    int last = cx > g.n[0] - 1 - cx ? cx : g.n[0] - 1 - cx;
+    last = cy > last ? cy : last;
+    last = g.n[1] - 1 - cy > last ? g.n[1] - 1 - cy : last;
+    last = cz > last ? cz : last;
+    return g.n[2] - 1 - cz > last ? g.n[2] - 1 - cz : last;
+}
+
+// The stop rule after ring r, the claim above put to use for the k-th place: every unvisited target has a computed
+// d2 >= ring_bound(h, r).  The search is over when the list is full and the bound exceeds the k-th d2 STRICTLY (at
+// equality an unvisited target of a smaller index would take the k-th place, K2), when the bound has reached md2
+// (nothing unvisited counts, K3), or when ring r reached the far faces.  With k = 1 this is ring_search's rule.
+SC_HD bool knn_settled(const Grid &g, int r, int last, bool full, double kth_d2) {
+    if (r >= last) return true;
+    const double b = ring_bound(g.h, r);
+    return (full && b > kth_d2) || b >= g.md2;
+}
+
+// Calls f(t0, t1) for every run of sorted slots of ring r: visit_ring's enumeration (a face row whole, of an inner
+// row its two end cells), without what is done per slot.
+template <class F>
+SC_HD void for_ring_runs(const Grid &g, int cx, int cy, int cz, int r, const uint32_t *__restrict__ start, F &&f) {
+    const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
+    const int x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < nx - 1 ? cx + r : nx - 1;
+    const int y0 = cy - r > 0 ? cy - r : 0, y1 = cy + r < ny - 1 ? cy + r : ny - 1;
+    const int z0 = cz - r > 0 ? cz - r : 0, z1 = cz + r < nz - 1 ? cz + r : nz - 1;
+    for (int z = z0; z <= z1; ++z)
+        for (int y = y0; y <= y1; ++y) {
+            const int row = (z * ny + y) * nx;
+            const bool face = z - cz == r || cz - z == r || y - cy == r || cy - y == r;
+            if (face) {
+                f(start[row + x0], start[row + x1 + 1]);
+            } else {
+                if (cx - r >= 0) f(start[row + cx - r], start[row + cx - r + 1]);
+                if (r > 0 && cx + r <= nx - 1) f(start[row + cx + r], start[row + cx + r + 1]);
+            }
+        }
+}
+
+// The serial form of the list: up to k keys in rising order in the caller's arrays.  offer() keeps the k smallest of
+// the keys below md2 it was given, whatever their order (K2, K3).  nearest.hip holds the same list in LDS and inserts
+// with a wavefront; the answer is the same set in the same order.
+struct KList {
+    double *d2;
+    int *idx;
+    int k, n;
+    SC_HD bool full() const { return n == k; }
+    SC_HD double kth() const { return n == k ? d2[k - 1] : HUGE_VAL; }
+    SC_HD void offer(double d, int i, double md2) {
+        if (!(d < md2) || (n == k && !key_less(d, i, d2[k - 1], idx[k - 1]))) return;
+        int j = n < k ? n : k - 1;  // the place that is freed: behind the list, or the k-th
+        for (; j > 0 && key_less(d, i, d2[j - 1], idx[j - 1]); --j) {
+            d2[j] = d2[j - 1];
+            idx[j] = idx[j - 1];
+        }
+        d2[j] = d;
+        idx[j] = i;
+        if (n < k) ++n;
+    }
+};
+
+// The ring walk of one query for its k nearest, serial.  True when the list is final; false when kNearRings rings did
+// not settle it: the far pass then starts again from an empty list over all P targets.
+SC_HD bool knn_ring_search(const Grid &g, const uint32_t *__restrict__ start, const double *__restrict__ spts,
+                           const int *__restrict__ sidx, double qx, double qy, double qz, KList &list) {
+    const int cx = cell_of(qx, g.lo[0], g.h, g.n[0]), cy = cell_of(qy, g.lo[1], g.h, g.n[1]), cz = cell_of(qz, g.lo[2], g.h, g.n[2]);
+    const int last = last_ring(g, cx, cy, cz);
+    list.n = 0;
+    for (int r = 0; r <= kNearRings; ++r) {
+        for_ring_runs(g, cx, cy, cz, r, start, [&](uint32_t t0, uint32_t t1) {
+            for (uint32_t t = t0; t < t1; ++t)
+                list.offer(dist2(qx, qy, qz, spts[3 * (size_t)t], spts[3 * (size_t)t + 1], spts[3 * (size_t)t + 2]), sidx[t], g.md2);
+        });
+        if (knn_settled(g, r, last, list.full(), list.kth())) return true;
+    }
+    return false;
+}
+
+// The grid of a k-nearest call aims at `aim` targets per cell, so that four rings can hold k of them: plan_grid is
+// given max(1, P / aim) as its count.  cell_cap is monotone, so the cells stay under cell_cap(P), from which the
+// buffer was sized, and no target is clamped whatever the count is (plan_grid's n[a] comes from the box alone).
+// Measured (tools/bench_knn.py, a surface cloud of 226 689 points): at k = 1, 8, 16 and 32 the least
+// aim tried, 1, was the fastest and sent nothing to the far pass; at k = 300 aims of 16 and 32 were equal within 1 %
+// and 64 slower, and k / 10 lies between them.  Between 32 and 300 nothing was measured: k / 10 is used there too.
+inline int knn_aim(int k) { return k <= 32 ? 1 : k / 10; }
 
 }  // namespace nn

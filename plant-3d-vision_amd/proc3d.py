@@ -413,3 +413,104 @@ def nearest_confusion(index, query_labels, target_labels, n_labels, device=0):
     nat.unit_call("sc_nearest_confusion", i.ptr, q.ptr, i.on_device, i.n, t.ptr, t.on_device, t.n, L, int(device), nat.addr(counts),
                   int(stream))
     return counts
+
+
+def knn_points(queries, targets, k, max_distance=None, device=0, return_far=False):
+    """For every query its ``k`` nearest points of ``targets`` and their squared distances, on the GPU (``sc_knn``,
+    ``csrc/nearest.hip``): open3d's ``KDTreeFlann.search_knn_vector_3d(p, k)`` for all queries at once.
+
+    queries, targets : as for :func:`nearest_points` -- array-likes ``[n, 3]``, :class:`PointCloud` objects or anything
+        with ``.points`` -> NumPy ``(index int32 [Q, k], d2 float64 [Q, k])``; or two contiguous float64 CUDA torch
+        tensors ``[n, 3]`` on one device, read in place on torch's current stream -> CUDA tensors on that device.  Mixed
+        kinds raise ``ValueError``.
+    k : 1 .. ``SC_KNN_MAX`` (512); ``Q * k`` must be below 2^31.
+    max_distance : ``None`` (unbounded) or a positive finite number.
+    return_far : also return the number of queries the pass over all targets took (the call then waits at its end).
+
+    PARITY UNPINNED: open3d is not available here.  The rules restate nanoflann's search in an
+    order-free form: K1 ``d2`` is N1's ``((dx dx) + (dy dy)) + (dz dz)`` in float64; K2 a target's key is ``(d2, index)``,
+    compared lexicographically, and row ``q`` holds the ``min(k, matched targets)`` smallest keys in rising key order -- a
+    tie at the k-th place goes to the smaller index; K3 with ``max_distance`` only targets with
+    ``d2 < max_distance * max_distance`` count (strict); K4 unused places, after the used ones, hold ``-1`` and ``+inf``
+    (no target: every place); K5 non-finite coordinates, a bad ``max_distance``, ``k`` outside ``1..SC_KNN_MAX`` and
+    ``Q * k >= 2^31`` raise ``ValueError``; K6 ``k = 1`` gives exactly ``nearest_points``' answer.  No CPU fallback."""
+    from . import _native as nat, _operands as ops
+
+    md = _max_distance_arg(max_distance)
+    k = int(k)
+    if not 1 <= k <= nat.SC_KNN_MAX:
+        raise ValueError(f"k must be 1 .. {nat.SC_KNN_MAX}")
+    q, t = ops.points(queries, "queries"), ops.points(targets, "targets")
+    if q.on_device != t.on_device:
+        raise ValueError("queries and targets must both be arrays (or clouds) or both CUDA tensors")
+    Q, P = q.n, t.n
+    if Q * k >= 2 ** 31:
+        raise ValueError("Q * k must be below 2^31")
+    far = np.zeros(1, dtype=np.int64)
+    fptr = nat.addr(far) if return_far else 0
+
+    def call(*args):  # sc_knn is an entry of the nearest unit: its errors are read with that unit's getter
+        nat.check(nat.backend().call("sc_knn", *args), "sc_knn", "sc_nearest_last_error")
+
+    if q.on_device:
+        import torch
+        if q.points.device != t.points.device:
+            raise ValueError("queries and targets must be on one device")
+        index = torch.full((Q, k), -1, dtype=torch.int32, device=q.points.device)
+        d2 = torch.full((Q, k), float("inf"), dtype=torch.float64, device=q.points.device)
+        if Q and P:  # rule K4 otherwise: the outputs are filled already
+            dev, stream = ops.tensor_place(q.points)
+            call(q.ptr, 1, Q, t.ptr, 1, P, k, md, int(dev), index.data_ptr(), d2.data_ptr(), 1, fptr, int(stream))
+    else:
+        index = np.full((max(Q, 1), k), -1, dtype=np.int32)
+        d2 = np.full((max(Q, 1), k), np.inf, dtype=np.float64)
+        call(q.ptr, 0, Q, t.ptr, 0, P, k, md, int(device), nat.addr(index), nat.addr(d2), 0, fptr, 0)
+        index, d2 = index[:Q], d2[:Q]
+    return (index, d2, int(far[0])) if return_far else (index, d2)
+
+
+def knn_edges(points, k, device=0, knn_fn=None):
+    """The edge set of the reference's ``knn_graph`` (``plant3dvision/proc3d.py:160-183``): for every point ``i`` of the
+    cloud and each of its ``k`` nearest points ``j`` of the same cloud -- ``i`` itself among them, as in the reference,
+    which adds the self-loop ``i-i`` of weight 0 -- the pair ``(min(i, j), max(i, j))``.
+
+    Returns ``(edges int32 [E, 2], weights float64 [E])``: the pairs deduplicated and sorted lexicographically, the
+    weight ``sqrt(d2)`` (``d2`` is bitwise symmetric under rule N1, so both directions of an edge carry one weight).
+    The search is :func:`knn_points` on the GPU (``knn_fn(points, points, k)`` replaces it in tests); removing the
+    duplicates is host NumPy."""
+    from . import _operands as ops
+
+    if knn_fn is None:
+        def knn_fn(a, b, kk):
+            return knn_points(a, b, kk, device=device)
+    p = ops.points(points, "points")
+    if p.on_device:
+        raise ValueError("knn_edges takes host points (the edges are deduplicated on the host)")
+    index, d2 = knn_fn(p.points, p.points, int(k))
+    index, d2 = np.asarray(index), np.asarray(d2)
+    i = np.broadcast_to(np.arange(p.n, dtype=np.int64)[:, None], index.shape)
+    used = index >= 0
+    i, j, w = i[used], index[used].astype(np.int64), np.sqrt(d2[used])
+    lo, hi = np.minimum(i, j), np.maximum(i, j)
+    key, first = np.unique(lo * max(p.n, 1) + hi, return_index=True)  # rising key: lexicographic in (lo, hi)
+    edges = np.stack([key // max(p.n, 1), key % max(p.n, 1)], axis=1).astype(np.int32).reshape(-1, 2)
+    return edges, np.ascontiguousarray(w[first])
+
+
+def knn_graph(pcd, k, device=0, knn_fn=None):
+    """``plant3dvision/proc3d.py:160-183``: the weighted undirected ``networkx.Graph`` that connects every point to its
+    ``k`` nearest neighbours (itself included: a self-loop of weight 0).  Node ``i`` carries ``center`` (the point),
+    an edge ``weight`` (the distance).  Built from :func:`knn_edges`; raises ``ImportError`` without networkx."""
+    try:
+        import networkx as nx
+    except ImportError as e:
+        raise ImportError("knn_graph needs networkx (knn_edges returns the same edges as arrays without it)") from e
+    from . import _operands as ops
+
+    pts = ops.points(pcd, "points").points
+    edges, weights = knn_edges(pts, k, device=device, knn_fn=knn_fn)
+    g = nx.Graph()
+    for i in range(len(pts)):
+        g.add_node(i, center=pts[i])
+    g.add_weighted_edges_from((int(a), int(b), float(w)) for (a, b), w in zip(edges.tolist(), weights.tolist()))
+    return g
