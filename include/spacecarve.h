@@ -762,6 +762,50 @@ int sc_knn(const double *queries, int queries_on_device, int64_t Q,
            int64_t *far_out /* host, may be null */, void *hip_stream);
 void sc_knn_set_aim(int aim);
 
+/*
+ * All points of another cloud within a radius: what open3d's KDTreeFlann.search_radius_vector_3d(p, r)
+ * computes for the reference's radius_graph (plant3dvision/proc3d.py:186-209), for Q queries at once, on the GPU.
+ * Parity unpinned as above: nanoflann's RadiusResultSet restated in an order-free form.
+ *   R1. d2 is N1's, bit for bit;
+ *   R2. target t is a neighbour of query q iff d2(q, t) < fl(radius * radius): strict, the product rounded once (a
+ *       target at exactly `radius` is not a neighbour); this is N3 and sc_dbscan's rule 2;
+ *   R3. row q holds ALL its neighbours in rising key (d2, index), compared lexicographically; keys are distinct, so
+ *       the row does not depend on the order of visiting;
+ *   R4. the answer is in CSR form: offsets int64 [Q + 1], offsets[0] = 0, offsets[q + 1] - offsets[q] the length of
+ *       row q; index int32 [E] and d2 double [E], E = offsets[Q]; counts int32 [Q], the lengths alone.  Q == 0:
+ *       offsets = {0}; P == 0: every count 0; neither makes a device call (device outputs are refused then);
+ *   R5. refused (SC_ERR_INVALID, before the first device call wherever a host can judge): non-finite coordinates (host
+ *       arrays naming the first bad point, device arrays by the first kernels as in sc_nearest), a radius that is not
+ *       finite and positive (there is no "unbounded" here) or whose square is not a normal number, Q or P outside
+ *       0 .. 2^31 - 1, NULL queries / targets / total_out, index_out without d2_out or the reverse, a negative
+ *       capacity, the device ordinal;
+ *   R6. capacity is the number of places in index_out and d2_out.  The call always computes the counts, the offsets and
+ *       *total_out = E; it writes the rows iff capacity >= E.  With capacity < E it returns SC_OK, leaves index_out
+ *       and d2_out untouched and still reports E: the caller asks once without rows, allocates, and asks again;
+ *   R7. on one cloud searched against itself counts[i] >= min_points is exactly sc_dbscan's core test.
+ * The search is exact for every finite input: sc_nearest's grid with an edge of at least the radius (so that rings 0
+ * and 1 hold every neighbour in the ordinary case), one wavefront per query, rings of cells until the proved lower
+ * bound on what is unvisited reaches radius^2 or nothing is unvisited -- no cap on the rings, no pass over all targets.
+ * One launch counts, a scan makes the offsets, the call waits for E and the longest row, one launch fills: rows of up
+ * to SC_RADIUS_LDS_ROW keys are sorted in LDS and written once, longer ones in place in global memory by a third
+ * launch; *long_out (NULL, or one host int64: the call then ends in a wait) receives how many rows went that way.
+ *
+ * counts_out, offsets_out, index_out, d2_out may be NULL (the last two both or neither) and live where out_on_device
+ * says.  The call waits twice (the finite flags and the box; E) and, with rows on the host or long_out, at its end.
+ * Errors are read with sc_nearest_last_error; the work buffers are sc_knn's plus 4 Q bytes of counts, 8 (Q + 1) of
+ * offsets and, for host rows, 12 capacity bytes; sc_nearest_release gives them back.
+ */
+#define SC_RADIUS_LDS_ROW 1024 /* the longest row sorted in LDS: 12 KiB per wavefront, 48 KiB per block */
+int sc_radius(const double *queries, int queries_on_device, int64_t Q,
+              const double *targets, int targets_on_device, int64_t P,
+              double radius, int device,
+              int32_t *counts_out /* [Q] or NULL */, int64_t *offsets_out /* [Q + 1] or NULL */,
+              int32_t *index_out, double *d2_out, int64_t capacity /* both or neither */,
+              int out_on_device /* where the four arrays above live */,
+              int64_t *total_out /* host, required */,
+              int64_t *long_out /* host, optional: rows the long-row launch sorted */,
+              void *hip_stream);
+
 /* Page-locked host memory for the read-back of sc_get_values (no reference counterpart: the
  * reference's values_h is a pageable NumPy array, cl.py:173).  A 512 MiB volume reads back in
  * ~10 ms into such a buffer against ~50 ms into pageable memory, but allocating it takes ~0.1 s

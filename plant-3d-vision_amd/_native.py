@@ -50,6 +50,7 @@ SC_OPT_PACK_REACH = 48
 SC_FILTER_LINEAR, SC_FILTER_EXCESS_GREEN = 0, 1
 SC_EVAL_F32, SC_EVAL_F64, SC_EVAL_U8 = 1, 2, 3
 SC_KNN_MAX = 512  # the largest k of sc_knn
+SC_RADIUS_LDS_ROW = 1024  # the longest row sc_radius sorts in LDS
 SC_FOOT = {"t0": 0, "t90": 1, "t180": 2, "t270": 3, "diamond": 4, "square": 5}  # SC_FOOT_*: names of masks2d._FOOTPRINTS
 
 # name -> (restype, [argtypes]); 'p' pointer, 'i' int, 'q' int64, 'f' float, 's' const char*
@@ -154,6 +155,7 @@ _SIGNATURES = {
     "sc_nearest_release": ("v", []),
     "sc_knn": ("i", ["p", "i", "q", "p", "i", "q", "i", "d", "i", "p", "p", "i", "p", "p"]),
     "sc_knn_set_aim": ("v", ["i"]),
+    "sc_radius": ("i", ["p", "i", "q", "p", "i", "q", "d", "i", "p", "p", "p", "p", "q", "i", "p", "p", "p"]),
     "sc_vol2pcd_class": ("i", ["p", "i", "i", "q", "q", "q", "p", "d", "d", "p", "i", "p", "p", "p"]),
     "sc_create_sharded": ("i", ["p", "q", "q", "q", "p", "f", "i", "f", "p", "i", "i"]),
     "sc_group_destroy": ("v", ["p"]),

@@ -22,6 +22,11 @@
 //
 // sc_knn (rules K1-K6 in include/spacecarve.h) is the same search for the k nearest: the same launches up
 // to the scatter on a grid planned for fewer, fuller cells, then knn_rings and knn_far, one wavefront per query.
+//
+// sc_radius (rules R1-R7 in include/spacecarve.h) returns ALL targets within a radius, nearest first, in
+// CSR form: the same launches up to the scatter on a grid whose cells are at least the radius wide, then radius_count,
+// a scan of the row lengths, a wait for their sum, radius_fill (rows sorted in LDS) and radius_long (longer rows,
+// sorted in place in global memory), one wavefront per query.
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -50,6 +55,7 @@ struct Header {
     unsigned int bad_targets, bad_queries, bad_labels, nfar;
     double box[6];   // lo x y z, hi x y z
     double sums[3];  // n, sum d2, sum sqrt(d2)
+    unsigned int longest, nlong;  // sc_radius: the longest row, the rows on the long list
 };
 
 // ---- box: whether every target coordinate is finite, and the targets' bounding box --------------------------------
@@ -323,6 +329,115 @@ __global__ __launch_bounds__(kB) void knn_far_kernel(const double *__restrict__ 
     }
 }
 
+// ---- all targets within a radius: one wavefront per query ---------------------------------------------------
+// The walk of sc_nearest.h's radius_search with the 64 lanes on 64 sorted slots at a time: f(slot, d2, in) is called by
+// the whole wavefront for every piece of every run, `in` being R2's predicate of the lane's slot.  The rings go on
+// until radius_settled: at most last_ring + 1 of them.
+template <class F>
+__device__ __forceinline__ void radius_walk(const nn::Grid &g, const uint32_t *__restrict__ start, const double *__restrict__ spts,
+                                            double qx, double qy, double qz, int lane, F &&f) {
+    const int cx = nn::cell_of(qx, g.lo[0], g.h, g.n[0]), cy = nn::cell_of(qy, g.lo[1], g.h, g.n[1]), cz = nn::cell_of(qz, g.lo[2], g.h, g.n[2]);
+    const int last = nn::last_ring(g, cx, cy, cz);
+    for (int r = 0;; ++r) {
+        nn::for_ring_runs(g, cx, cy, cz, r, start, [&](uint32_t t0, uint32_t t1) {
+            for (uint32_t b = t0; b < t1; b += 64) {  // t1 <= P < 2^31: b + 64 does not wrap
+                const uint32_t t = b + lane;
+                const bool have = t < t1;
+                const size_t s = have ? t : t0;
+                const double d = nn::dist2(qx, qy, qz, spts[3 * s], spts[3 * s + 1], spts[3 * s + 2]);
+                f(s, d, have && d < g.md2);
+            }
+        });
+        if (nn::radius_settled(g, r, last)) return;
+    }
+}
+
+// count: the length of every row.  Lane 0 writes it twice -- counts[q], and as a 64-bit number offsets[q], which the
+// scan behind this launch turns into the row's first place -- and raises the header's longest row by an integer
+// atomicMax: nothing depends on the order.  The atomic is skipped when a relaxed load already shows a row as long: the
+// word only grows, so a stale value costs an atomic and changes nothing (one atomic per query on one word took 2.3 of
+// the launch's 2.8 ms on the 226 689-point cloud of DESIGN.md 19).
+__global__ __launch_bounds__(kB) void radius_count_kernel(const double *__restrict__ qs, int Q, nn::Grid g, const uint32_t *__restrict__ start,
+                                                          const double *__restrict__ spts, int32_t *__restrict__ counts,
+                                                          int64_t *__restrict__ offsets, unsigned int *longest) {
+    const uint32_t q = blockIdx.x * (kB / 64) + (threadIdx.x >> 6);  // the same in every lane of a wavefront
+    if (q >= (uint32_t)Q) return;
+    const int lane = (int)(threadIdx.x & 63);
+    int n = 0;  // at most P < 2^31
+    radius_walk(g, start, spts, qs[3 * (size_t)q], qs[3 * (size_t)q + 1], qs[3 * (size_t)q + 2], lane,
+                [&](size_t, double, bool in) { n += __popcll(__ballot(in)); });
+    if (lane == 0) {
+        counts[q] = n;
+        offsets[q] = n;
+        if ((unsigned int)n > __hip_atomic_load(longest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(longest, (unsigned int)n);
+    }
+}
+
+// What stands between a lane's store to global memory and another lane's load of that word in radius_long_kernel: an
+// agent-scope fence -- the stores are drained to the L2 and this compute unit's vector L1 is invalidated, so the load
+// that follows cannot be served from a line fetched before the store -- and the wavefront barrier, which keeps the
+// compiler from moving a lane's accesses across (the wavefront-scope fence behind it does the same for what follows and
+// emits nothing).  lds_order()'s wavefront-scope fences emit no instruction: enough for LDS, which a wavefront accesses
+// in order, not for loads and stores that return out of order through a cache.
+__device__ __forceinline__ void global_order() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+
+// fill: the same enumeration and the same predicate as count; the row's length n and first place are known.  A
+// survivor's place is its rank among the ballot's set bits plus a running base.  Rows of up to lds_row keys (the
+// places this launch gave each wavefront: min(SC_RADIUS_LDS_ROW, the longest row rounded up to a power of two)) are
+// gathered in the wavefront's private piece of LDS, sorted there and written once, coalesced.  Longer rows go to
+// their places in global memory in visiting order and onto the long list (capacity Q; only added to here, only read
+// by the next launch).  `pos < n` holds by construction; the test keeps every write inside the row all the same.
+__global__ __launch_bounds__(kB) void radius_fill_kernel(const double *__restrict__ qs, int Q, nn::Grid g, const uint32_t *__restrict__ start,
+                                                         const double *__restrict__ spts, const int *__restrict__ sidx,
+                                                         const int64_t *__restrict__ offsets, int lds_row, int32_t *__restrict__ index,
+                                                         double *__restrict__ d2, int *__restrict__ longlist, unsigned int *nlong) {
+    extern __shared__ double radius_lds[];  // [kB / 64][lds_row] doubles, then as many ints
+    const uint32_t q = blockIdx.x * (kB / 64) + (threadIdx.x >> 6);
+    if (q >= (uint32_t)Q) return;
+    const int64_t first = offsets[q], len = offsets[q + 1] - first;
+    if (len <= 0) return;
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    const int n = (int)len;  // a row holds at most P < 2^31 keys
+    const bool in_lds = n <= lds_row;
+    double *kd = in_lds ? radius_lds + (size_t)wave * lds_row : d2 + first;
+    int *ki = in_lds ? reinterpret_cast<int *>(radius_lds + (size_t)(kB / 64) * lds_row) + (size_t)wave * lds_row : index + first;
+    int base = 0;
+    radius_walk(g, start, spts, qs[3 * (size_t)q], qs[3 * (size_t)q + 1], qs[3 * (size_t)q + 2], lane, [&](size_t s, double d, bool in) {
+        const unsigned long long m = __ballot(in);
+        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+        if (in && pos < n) {
+            kd[pos] = d;
+            ki[pos] = sidx[s];
+        }
+        base += __popcll(m);
+    });
+    if (!in_lds) {
+        if (lane == 0) longlist[atomicAdd(nlong, 1u)] = (int)q;
+        return;
+    }
+    nn::sort_row(kd, ki, n, lane, 64, [] { lds_order(); });
+    for (int j = lane; j < n; j += 64) {
+        index[first + j] = ki[j];
+        d2[first + j] = kd[j];
+    }
+}
+
+// long: one wavefront per row of the long list, grid-stride; the same network over the row in place in global memory.
+__global__ __launch_bounds__(kB) void radius_long_kernel(const int64_t *__restrict__ offsets, const int *__restrict__ longlist,
+                                                         const unsigned int *__restrict__ nlong, int32_t *index, double *d2) {
+    const int lane = (int)(threadIdx.x & 63);
+    const unsigned int rows = *nlong, waves = gridDim.x * (kB / 64);
+    for (unsigned int w = blockIdx.x * (kB / 64) + (threadIdx.x >> 6); w < rows; w += waves) {
+        const int q = longlist[w];
+        const int64_t first = offsets[q];
+        nn::sort_row(d2 + first, index + first, (int)(offsets[q + 1] - first), lane, 64, [] { global_order(); });
+    }
+}
+
 // ---- sums (N6) -----------------------------------------------------------------------------------------------------------
 // A thread adds its queries in rising index, a block adds its threads by a tree, and block b leaves its three partials
 // at partial[3 b]: the order is a function of Q, kB and the block count.
@@ -405,6 +520,12 @@ __global__ __launch_bounds__(kB) void nearest_confusion_kernel(const int32_t *__
 WorkSlot g_slots[kUnitDevices];
 
 std::atomic<int> g_knn_aim{0};  // sc_knn_set_aim: targets per cell sc_knn's grid aims at; 0: nn::knn_aim(k)
+
+uint32_t pow2ceil(uint32_t n) {  // the least power of two >= n, n <= 2^31
+    uint32_t m = 1;
+    while (m < n) m <<= 1;
+    return m;
+}
 
 }  // namespace
 
@@ -631,6 +752,141 @@ int sc_knn(const double *queries, int queries_on_device, int64_t Q, const double
         if (far_out || !out_on_device) {
             UNIT_TRY(hipStreamSynchronize(stream));
             if (far_out) *far_out = (int64_t)hh.nfar;
+        }
+    }
+
+done:
+    return rc;
+}
+
+int sc_radius(const double *queries, int queries_on_device, int64_t Q, const double *targets, int targets_on_device, int64_t P,
+              double radius, int device, int32_t *counts_out, int64_t *offsets_out, int32_t *index_out, double *d2_out, int64_t capacity,
+              int out_on_device, int64_t *total_out, int64_t *long_out, void *hip_stream) {
+    // every argument is judged before the first device call
+    if (Q < 0 || Q >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "Q must be 0 .. 2^31 - 1");
+    if (P < 0 || P >= ((int64_t)1 << 31)) return g_err.fail(SC_ERR_INVALID, "P must be 0 .. 2^31 - 1");
+    if ((Q > 0 && !queries) || (P > 0 && !targets) || !total_out) return g_err.fail(SC_ERR_INVALID, "null argument (queries, targets, total_out)");
+    if (!index_out != !d2_out) return g_err.fail(SC_ERR_INVALID, "index_out and d2_out are given both or neither");
+    if (capacity < 0) return g_err.fail(SC_ERR_INVALID, "capacity must not be negative");
+    if (!std::isfinite(radius) || !(radius > 0.0)) return g_err.fail(SC_ERR_INVALID, "radius must be finite and positive");
+    if (!(radius * radius >= DBL_MIN) || !std::isfinite(radius * radius))
+        return g_err.fail(SC_ERR_INVALID, "radius * radius must be a normal number (radius out of range)");
+    if (device < 0 || device >= kUnitDevices) return g_err.fail(SC_ERR_INVALID, "device ordinal out of range");
+    if ((Q == 0 || P == 0) && out_on_device && (offsets_out || (Q > 0 && counts_out)))
+        return g_err.fail(SC_ERR_INVALID, "Q == 0 or P == 0 makes no device call: device outputs cannot be filled");
+    if (!queries_on_device && first_non_finite(g_err, queries, Q, "query") != SC_OK) return SC_ERR_INVALID;
+    if (!targets_on_device && first_non_finite(g_err, targets, P, "target") != SC_OK) return SC_ERR_INVALID;
+    *total_out = 0;
+    if (long_out) *long_out = 0;
+    if (Q == 0 || P == 0) {  // R4: empty rows; host outputs (device ones were refused above)
+        if (offsets_out)
+            for (int64_t q = 0; q <= Q; ++q) offsets_out[q] = 0;
+        if (counts_out)
+            for (int64_t q = 0; q < Q; ++q) counts_out[q] = 0;
+        return SC_OK;
+    }
+
+    const int nq = (int)Q, np = (int)P;
+    const int64_t cap = nn::cell_cap(P);
+    const uint32_t pblocks = (uint32_t)((P + kB - 1) / kB), qwave_blocks = (uint32_t)((Q + kB / 64 - 1) / (kB / 64));
+    const int box_parts = (int)std::min<uint32_t>(pblocks, kPartials);
+    const bool rows = index_out != nullptr, stage_rows = rows && !out_on_device;
+
+    int rc = SC_OK;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    UnitCall call(g_err, g_slots, device, stream, rc);
+    size_t tmp = 0, tmp2 = 0;
+    Header hh;
+    nn::Grid g;
+    int64_t total = 0;
+
+    // layout of the work buffer: sc_knn's (the far list is the long list), then the counts, the offsets and, for host
+    // outputs, the staged rows
+    Layout lay;
+    const size_t o_hdr = lay.take(sizeof(Header)), o_part = lay.take((size_t)kPartials * 6 * 8);
+    const size_t o_count = lay.take(((size_t)cap + 1) * 4), o_start = lay.take(((size_t)cap + 1) * 4), o_cursor = lay.take(((size_t)cap + 1) * 4);
+    const size_t o_spts = lay.take((size_t)P * 24), o_sidx = lay.take((size_t)P * 4), o_long = lay.take((size_t)Q * 4);
+    const size_t o_qs = lay.take(queries_on_device ? 0 : (size_t)Q * 24), o_ts = lay.take(targets_on_device ? 0 : (size_t)P * 24);
+    const size_t o_cnt = lay.take(counts_out && out_on_device ? 0 : (size_t)Q * 4);
+    const size_t o_off = lay.take(offsets_out && out_on_device ? 0 : ((size_t)Q + 1) * 8);
+    const size_t o_idx = lay.take(stage_rows ? (size_t)capacity * 4 : 0), o_d2 = lay.take(stage_rows ? (size_t)capacity * 8 : 0);
+    size_t o_tmp = 0;  // the scans' temporary storage: the last buffer, sized below
+
+    if ((rc = call.enter()) != SC_OK) goto done;
+    // the temporary storage of the larger of the two scans (size queries: no device work)
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(cap + 1), stream));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (int64_t *)nullptr, (int64_t *)nullptr, (size_t)Q + 1, stream));
+    tmp = std::max(tmp, tmp2);
+    o_tmp = lay.take(tmp);
+    if ((rc = call.grow(lay.total)) != SC_OK) goto done;
+    {
+        char *const w = call.sl.base;
+        Header *hdr = reinterpret_cast<Header *>(w + o_hdr);
+        double *partial = reinterpret_cast<double *>(w + o_part);
+        uint32_t *count = reinterpret_cast<uint32_t *>(w + o_count), *start = reinterpret_cast<uint32_t *>(w + o_start),
+                 *cursor = reinterpret_cast<uint32_t *>(w + o_cursor);
+        double *spts = reinterpret_cast<double *>(w + o_spts);
+        int *sidx = reinterpret_cast<int *>(w + o_sidx), *longlist = reinterpret_cast<int *>(w + o_long);
+        const double *qs_d = queries_on_device ? queries : reinterpret_cast<const double *>(w + o_qs);
+        const double *ts_d = targets_on_device ? targets : reinterpret_cast<const double *>(w + o_ts);
+        int32_t *cnt_d = counts_out && out_on_device ? counts_out : reinterpret_cast<int32_t *>(w + o_cnt);
+        int64_t *off_d = offsets_out && out_on_device ? offsets_out : reinterpret_cast<int64_t *>(w + o_off);
+        int32_t *idx_d = stage_rows ? reinterpret_cast<int32_t *>(w + o_idx) : index_out;
+        double *d2_d = stage_rows ? reinterpret_cast<double *>(w + o_d2) : d2_out;
+        void *tmp_d = w + o_tmp;
+
+        UNIT_TRY(call.sl.wait(stream));
+        if (!queries_on_device) UNIT_TRY(hipMemcpyAsync(w + o_qs, queries, (size_t)Q * 24, hipMemcpyHostToDevice, stream));
+        if (!targets_on_device) UNIT_TRY(hipMemcpyAsync(w + o_ts, targets, (size_t)P * 24, hipMemcpyHostToDevice, stream));
+        UNIT_TRY(hipMemsetAsync(hdr, 0, sizeof(Header), stream));
+        hipLaunchKernelGGL(nearest_box_kernel, dim3(box_parts), dim3(kB), 0, stream, ts_d, np, &hdr->bad_targets, partial);
+        hipLaunchKernelGGL(nearest_box_final_kernel, dim3(1), dim3(kB), 0, stream, partial, box_parts, hdr->box);
+        launch_points_finite(stream, qs_d, Q, &hdr->bad_queries);
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpyAsync(&hh, hdr, sizeof(Header), hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(call.sl.record(stream));
+        UNIT_TRY(hipStreamSynchronize(stream));  // the call's first wait: the finite flags and the box
+        if (hh.bad_queries != 0u || hh.bad_targets != 0u) {  // device points: the first kernels are the judge
+            rc = g_err.fail(SC_ERR_INVALID, hh.bad_queries ? "non-finite coordinate in the device queries" : "non-finite coordinate in the device targets");
+            goto done;
+        }
+        nn::plan_radius_grid(hh.box, hh.box + 3, P, radius, g);
+        const int ncell = g.n[0] * g.n[1] * g.n[2];  // <= cap
+
+        UNIT_TRY(hipMemsetAsync(count, 0, ((size_t)ncell + 1) * 4, stream));
+        hipLaunchKernelGGL(nearest_hist_kernel, dim3(pblocks), dim3(kB), 0, stream, ts_d, np, g, count);
+        UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp, count, start, ncell + 1, stream));
+        UNIT_TRY(hipMemcpyAsync(cursor, start, (size_t)ncell * 4, hipMemcpyDeviceToDevice, stream));
+        hipLaunchKernelGGL(nearest_scatter_kernel, dim3(pblocks), dim3(kB), 0, stream, ts_d, np, g, cursor, spts, sidx);
+        UNIT_TRY(hipMemsetAsync(off_d + Q, 0, 8, stream));  // the scan reads Q + 1 lengths
+        hipLaunchKernelGGL(radius_count_kernel, dim3(qwave_blocks), dim3(kB), 0, stream, qs_d, nq, g, start, spts, cnt_d, off_d, &hdr->longest);
+        UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(tmp_d, tmp, off_d, off_d, (size_t)Q + 1, stream));  // in place: lengths to first places
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpyAsync(&hh.longest, &hdr->longest, 4, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(hipMemcpyAsync(&total, off_d + Q, 8, hipMemcpyDeviceToHost, stream));
+        if (counts_out && !out_on_device) UNIT_TRY(hipMemcpyAsync(counts_out, cnt_d, (size_t)Q * 4, hipMemcpyDeviceToHost, stream));
+        if (offsets_out && !out_on_device) UNIT_TRY(hipMemcpyAsync(offsets_out, off_d, ((size_t)Q + 1) * 8, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(call.sl.record(stream));
+        UNIT_TRY(hipStreamSynchronize(stream));  // the call's second wait: E and the longest row
+        *total_out = total;
+        if (!rows || capacity < total || total == 0) goto done;  // R6: the rows are written iff they fit
+
+        const int lds_row = (int)std::min<uint32_t>(SC_RADIUS_LDS_ROW, pow2ceil(hh.longest));  // places per wavefront
+        hipLaunchKernelGGL(radius_fill_kernel, dim3(qwave_blocks), dim3(kB), (size_t)(kB / 64) * 12 * (size_t)lds_row, stream, qs_d, nq, g, start,
+                           spts, sidx, off_d, lds_row, idx_d, d2_d, longlist, &hdr->nlong);
+        if (hh.longest > (uint32_t)SC_RADIUS_LDS_ROW)
+            hipLaunchKernelGGL(radius_long_kernel, dim3(std::min<uint32_t>(qwave_blocks, kFarBlocks)), dim3(kB), 0, stream, off_d, longlist,
+                               &hdr->nlong, idx_d, d2_d);
+        UNIT_TRY(hipGetLastError());
+        if (stage_rows) {
+            UNIT_TRY(hipMemcpyAsync(index_out, idx_d, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+            UNIT_TRY(hipMemcpyAsync(d2_out, d2_d, (size_t)total * 8, hipMemcpyDeviceToHost, stream));
+        }
+        if (long_out) UNIT_TRY(hipMemcpyAsync(&hh.nlong, &hdr->nlong, 4, hipMemcpyDeviceToHost, stream));
+        UNIT_TRY(call.sl.record(stream));
+        if (long_out || stage_rows) {
+            UNIT_TRY(hipStreamSynchronize(stream));
+            if (long_out) *long_out = (int64_t)hh.nlong;
         }
     }
 

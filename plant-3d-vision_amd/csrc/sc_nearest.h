@@ -4,6 +4,7 @@
 // Host and device: nearest.hip runs it one thread per query; tools/nearest_rehearsal.cpp runs the same text on the
 // CPU, one query after the other, against all pairs.  The k nearest follow at the end: the stop rule
 // for the k-th place, the enumeration of a ring's runs, and the serial form of the list nearest.hip keeps per wavefront.
+// Last, all targets within a radius: its plan, its stop rule and the serial walk of one query.
 #pragma once
 
 #include <cfloat>
@@ -271,5 +272,91 @@ SC_HD bool knn_ring_search(const Grid &g, const uint32_t *__restrict__ start, co
 // aim tried, 1, was the fastest and sent nothing to the far pass; at k = 300 aims of 16 and 32 were equal within 1 %
 // and 64 slower, and k / 10 lies between them.  Between 32 and 300 nothing was measured: k / 10 is used there too.
 inline int knn_aim(int k) { return k <= 32 ? 1 : k / 10; }
+
+// ---- all targets within a radius ----------------------------------------------------------------------
+// R2: t is a neighbour of q iff d2(q, t) < md2 = fl(radius * radius), strict.  The claim above ring_bound holds for any
+// planned grid: after rings 0..r every unvisited target has a computed d2 >= ring_bound(h, r).  So the row of a query
+// is complete after the first ring r with ring_bound(h, r) >= md2 -- nothing unvisited can be a neighbour -- or with
+// r >= last_ring: nothing is unvisited.  There is no cap on the rings and no pass over all targets: the walk ends at
+// last_ring at the latest, which is below the largest cell count.  Correctness rests on this rule alone, whatever h is.
+SC_HD bool radius_settled(const Grid &g, int r, int last) { return r >= last || ring_bound(g.h, r) >= g.md2; }
+
+// The plan, for speed only: plan_grid as it is; then, if its cells are so small that ring 1 does not close the search
+// (ring_bound(h, 1) < md2), the edge is widened to just above the radius -- h = fl(radius (1 + 2^-18)), for which
+// ring_bound(h, 1) > radius^2 (1 + 2^-17) (1 - 2^-19) > md2; the inequality is tested, not trusted -- and the counts
+// are computed anew from the box and the new h, n[a] = floor(fl(ext[a] / h)) + 1, exactly as plan_grid does: NO TARGET
+// IS CLAMPED, whatever h is.  A wider edge can only shrink the product of the counts; it is compared with cell_cap(P)
+// all the same (plan_grid's one-cell answer has h = 1, which says nothing about the box).  Whatever does not fit --
+// h outside [kEdgeMin, kEdgeMax], an extent that is not finite, a product over the cap -- is ONE cell: ring 0 is then
+// the last ring.  Rings 0 and 1 (27 cells) are the whole search in every ordinary case.
+inline void plan_radius_grid(const double lo[3], const double hi[3], int64_t P, double radius, Grid &g) {
+    plan_grid(lo, hi, P, radius, g);
+    if (ring_bound(g.h, 1) >= g.md2) return;
+    const double h = radius * (1.0 + 0x1p-18);
+    double prod = 1.0, cnt[3] = {1.0, 1.0, 1.0};
+    bool ok = h >= kEdgeMin && h <= kEdgeMax && ring_bound(h, 1) >= g.md2;
+    for (int a = 0; a < 3 && ok; ++a) {
+        const double ext = hi[a] - lo[a];
+        if (!(ext >= 0.0) || !std::isfinite(ext)) ok = false;
+        cnt[a] = floor(ext / h) + 1.0;
+        prod *= cnt[a];
+    }
+    if (!ok || !(prod <= (double)cell_cap(P))) {  // also an infinite or NaN product
+        g.h = 1.0;
+        g.n[0] = g.n[1] = g.n[2] = 1;
+        return;
+    }
+    g.h = h;
+    for (int a = 0; a < 3; ++a) g.n[a] = (int)cnt[a];
+}
+
+// R3: n keys (d2, index) into rising order by a bitonic network over the next power of two whose comparators all point
+// upwards (a merge step's first exchange is with the mirror place i ^ (k - 1), the others with i ^ j): the places from
+// n on hold, virtually, the largest key (+inf, INT_MAX), which such a comparator never moves, so an exchange with a
+// place >= n is simply skipped.  Lane `lane` of `lanes` takes the places i = lane, lane + lanes, ... whose partner lies
+// above them; within a step every place belongs to one pair, so only between steps does a lane read what another one
+// wrote: order() stands there (nearest.hip: a fence fit for where the keys live; the rehearsal, one lane, nothing).
+// ceil(log2 n) (ceil(log2 n) + 1) / 2 steps of at most ceil(n / lanes) exchanges per lane; n < 2^31.
+template <class Order>
+SC_HD void sort_row(double *kd, int *ki, int n, int lane, int lanes, Order &&order) {
+    const uint32_t un = (uint32_t)n;
+    for (uint32_t k = 2; (k >> 1) < un; k <<= 1)  // k <= 2^31
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            order();
+            const uint32_t flip = j == (k >> 1) ? k - 1 : j;
+            for (uint32_t i = (uint32_t)lane; i < un; i += (uint32_t)lanes) {
+                const uint32_t l = i ^ flip;
+                if (l > i && l < un) {
+                    const double di = kd[i], dl = kd[l];
+                    const int ii = ki[i], il = ki[l];
+                    if (key_less(dl, il, di, ii)) {
+                        kd[i] = dl;
+                        ki[i] = il;
+                        kd[l] = di;
+                        ki[l] = ii;
+                    }
+                }
+            }
+        }
+    order();
+}
+
+// The serial walk of one query: f(d2, index) for every neighbour (R2), in visiting order (R3's order is the caller's
+// sort).  Every loop is bounded by the cell counts or P.
+template <class F>
+SC_HD void radius_search(const Grid &g, const uint32_t *__restrict__ start, const double *__restrict__ spts,
+                         const int *__restrict__ sidx, double qx, double qy, double qz, F &&f) {
+    const int cx = cell_of(qx, g.lo[0], g.h, g.n[0]), cy = cell_of(qy, g.lo[1], g.h, g.n[1]), cz = cell_of(qz, g.lo[2], g.h, g.n[2]);
+    const int last = last_ring(g, cx, cy, cz);
+    for (int r = 0;; ++r) {
+        for_ring_runs(g, cx, cy, cz, r, start, [&](uint32_t t0, uint32_t t1) {
+            for (uint32_t t = t0; t < t1; ++t) {
+                const double d = dist2(qx, qy, qz, spts[3 * (size_t)t], spts[3 * (size_t)t + 1], spts[3 * (size_t)t + 2]);
+                if (d < g.md2) f(d, sidx[t]);
+            }
+        });
+        if (radius_settled(g, r, last)) return;
+    }
+}
 
 }  // namespace nn

@@ -490,10 +490,17 @@ def knn_edges(points, k, device=0, knn_fn=None):
     index, d2 = np.asarray(index), np.asarray(d2)
     i = np.broadcast_to(np.arange(p.n, dtype=np.int64)[:, None], index.shape)
     used = index >= 0
-    i, j, w = i[used], index[used].astype(np.int64), np.sqrt(d2[used])
+    return _fold_edges(i[used], index[used], d2[used], p.n)
+
+
+def _fold_edges(i, j, d2, n):
+    """The tail ``knn_edges`` and ``radius_edges`` share: the directed pairs ``i -> j`` (flat arrays, ``d2`` beside them)
+    of a cloud of ``n`` points become ``(edges int32 [E, 2], weights float64 [E])`` -- ``(min, max)``, deduplicated,
+    sorted lexicographically, weight ``sqrt(d2)`` of the first pair of each edge (``d2`` is bitwise symmetric)."""
+    i, j, w = np.asarray(i, dtype=np.int64), np.asarray(j).astype(np.int64), np.sqrt(d2)
     lo, hi = np.minimum(i, j), np.maximum(i, j)
-    key, first = np.unique(lo * max(p.n, 1) + hi, return_index=True)  # rising key: lexicographic in (lo, hi)
-    edges = np.stack([key // max(p.n, 1), key % max(p.n, 1)], axis=1).astype(np.int32).reshape(-1, 2)
+    key, first = np.unique(lo * max(n, 1) + hi, return_index=True)  # rising key: lexicographic in (lo, hi)
+    edges = np.stack([key // max(n, 1), key % max(n, 1)], axis=1).astype(np.int32).reshape(-1, 2)
     return edges, np.ascontiguousarray(w[first])
 
 
@@ -512,5 +519,132 @@ def knn_graph(pcd, k, device=0, knn_fn=None):
     g = nx.Graph()
     for i in range(len(pts)):
         g.add_node(i, center=pts[i])
+    g.add_weighted_edges_from((int(a), int(b), float(w)) for (a, b), w in zip(edges.tolist(), weights.tolist()))
+    return g
+
+
+def _radius_operands(queries, targets, radius):
+    """What ``radius_counts`` and ``radius_points`` share: the radius judged (rule R5), the two clouds through
+    ``_operands.points``, their kinds and devices compared.  ``(q, t, radius, place)``; ``place`` is ``None`` for host
+    arrays, else ``(device index, torch's current stream there)``."""
+    from . import _operands as ops
+
+    r = float(radius)
+    if not (r > 0.0 and r != float("inf")):
+        raise ValueError("radius must be positive and finite")
+    q, t = ops.points(queries, "queries"), ops.points(targets, "targets")
+    if q.on_device != t.on_device:
+        raise ValueError("queries and targets must both be arrays (or clouds) or both CUDA tensors")
+    if q.on_device and q.points.device != t.points.device:
+        raise ValueError("queries and targets must be on one device")
+    return q, t, r, (ops.tensor_place(q.points) if q.on_device else None)
+
+
+def _radius_call(q, t, r, place, device, counts=None, offsets=None, index=None, d2=None, want_long=False):
+    """One ``sc_radius`` call on non-empty clouds: ``(E, rows the long-row launch sorted)``.  The outputs given are
+    filled; ``index`` / ``d2`` hold ``capacity = len(index)`` places."""
+    from . import _native as nat, _operands as ops
+
+    out = np.zeros(2, dtype=np.int64)  # total_out, long_out
+    dev, stream = place if place is not None else (int(device), 0)
+    ptr = [0 if a is None else ops.ptr_of(a) for a in (counts, offsets, index, d2)]
+    # sc_radius is an entry of the nearest unit: its errors are read with that unit's getter
+    nat.check(nat.backend().call("sc_radius", q.ptr, q.on_device, q.n, t.ptr, t.on_device, t.n, r, int(dev), ptr[0], ptr[1], ptr[2], ptr[3],
+                                 0 if index is None else int(index.shape[0]), q.on_device, nat.addr(out),
+                                 nat.addr(out) + 8 if want_long else 0, int(stream)), "sc_radius", "sc_nearest_last_error")
+    return int(out[0]), int(out[1])
+
+
+def _radius_array(q, n, dtype, zero=False):
+    """An output of ``n`` places of the queries' kind: a CUDA tensor on their device, or a NumPy array."""
+    if q.on_device:
+        import torch
+        make = torch.zeros if zero else torch.empty
+        return make((n,), dtype=getattr(torch, np.dtype(dtype).name), device=q.points.device)
+    return (np.zeros if zero else np.empty)(n, dtype=dtype)
+
+
+def radius_counts(queries, targets, radius, device=0):
+    """For every query the number of points of ``targets`` within ``radius`` (rule R2: ``d2 < radius * radius``,
+    strict), on the GPU: one ``sc_radius`` call without row outputs.  int32 ``[Q]``, a NumPy array or a
+    CUDA tensor as the inputs are (see :func:`radius_points`).  On one cloud searched against itself
+    ``radius_counts(p, p, eps) >= min_points`` is exactly ``cluster_dbscan``'s core test (rule R7)."""
+    q, t, r, place = _radius_operands(queries, targets, radius)
+    counts = _radius_array(q, q.n, np.int32, zero=True)
+    if q.n and t.n:  # rule R4 otherwise: no device call, the zeros stand
+        _radius_call(q, t, r, place, device, counts=counts)
+    return counts
+
+
+def radius_points(queries, targets, radius, device=0, return_long=False):
+    """For every query ALL points of ``targets`` within ``radius``, nearest first, on the GPU (``sc_radius``,
+    ``csrc/nearest.hip``): open3d's ``KDTreeFlann.search_radius_vector_3d(p, radius)`` for all queries
+    at once.  (``search_hybrid_vector_3d(p, radius, max_nn)`` is ``knn_points(..., k=max_nn, max_distance=radius)``.)
+
+    queries, targets : as for :func:`nearest_points` -- array-likes ``[n, 3]``, :class:`PointCloud` objects or anything
+        with ``.points`` -> NumPy arrays; or two contiguous float64 CUDA torch tensors ``[n, 3]`` on one device, read in
+        place on torch's current stream -> CUDA tensors on that device.  Mixed kinds raise ``ValueError``.
+    radius : positive and finite.
+    return_long : also return the number of rows longer than ``SC_RADIUS_LDS_ROW``, which the long-row launch sorted.
+
+    Returns ``(offsets int64 [Q + 1], index int32 [E], d2 float64 [E])``, the rows in CSR form: row ``q`` is
+    ``index[offsets[q]:offsets[q + 1]]``, ``E = offsets[Q]``.  Two calls are made: one for ``E``, one that fills arrays
+    of exactly ``E`` places; inputs changed in between (another total) raise ``RuntimeError``.
+
+    PARITY UNPINNED: open3d is not available here.  The rules restate nanoflann's search in an
+    order-free form: R1 ``d2`` is N1's ``((dx dx) + (dy dy)) + (dz dz)`` in float64; R2 a target is a neighbour iff
+    ``d2 < radius * radius`` (strict, the product rounded once: a target at exactly ``radius`` is not); R3 a row holds
+    all neighbours in rising ``(d2, index)``; R4 no query: ``offsets = [0]``, no target: empty rows; R5 non-finite
+    coordinates and a ``radius`` that is not positive and finite raise ``ValueError``.  No CPU fallback."""
+    q, t, r, place = _radius_operands(queries, targets, radius)
+    total = nlong = 0
+    if q.n and t.n:
+        total, _ = _radius_call(q, t, r, place, device)
+    offsets = _radius_array(q, q.n + 1, np.int64, zero=True)
+    index, d2 = _radius_array(q, total, np.int32), _radius_array(q, total, np.float64)
+    if total:  # otherwise every row is empty and the zeros stand: no zero-length array goes to the library
+        again, nlong = _radius_call(q, t, r, place, device, offsets=offsets, index=index, d2=d2, want_long=return_long)
+        if again != total:
+            raise RuntimeError(f"radius_points: {total} neighbours on the first call, {again} on the second: the inputs were changed in between")
+    return (offsets, index, d2, nlong) if return_long else (offsets, index, d2)
+
+
+def radius_edges(points, r, device=0, radius_fn=None):
+    """The edge set of the reference's ``radius_graph`` (``plant3dvision/proc3d.py:186-209``): for every point ``i`` of
+    the cloud and every point ``j`` of the same cloud within ``r`` of it -- ``i`` itself among them (``d2 = 0 < r * r``),
+    as the reference's loop adds the self-loop ``i-i`` -- the pair ``(min(i, j), max(i, j))``.
+
+    Returns ``(edges int32 [E', 2], weights float64 [E'])`` as :func:`knn_edges` does: deduplicated, sorted
+    lexicographically, weight ``sqrt(d2)``.  The search is :func:`radius_points` on the GPU (``radius_fn(points, points,
+    r)`` replaces it in tests); removing the duplicates is host NumPy."""
+    from . import _operands as ops
+
+    if radius_fn is None:
+        def radius_fn(a, b, rr):
+            return radius_points(a, b, rr, device=device)
+    p = ops.points(points, "points")
+    if p.on_device:
+        raise ValueError("radius_edges takes host points (the edges are deduplicated on the host)")
+    offsets, index, d2 = radius_fn(p.points, p.points, float(r))
+    offsets, index, d2 = np.asarray(offsets), np.asarray(index), np.asarray(d2)
+    i = np.repeat(np.arange(p.n, dtype=np.int64), np.diff(offsets))
+    return _fold_edges(i, index, d2, p.n)
+
+
+def radius_graph(pcd, r, device=0, radius_fn=None):
+    """``plant3dvision/proc3d.py:186-209``: the weighted undirected ``networkx.Graph`` that connects every point to all
+    points within ``r`` of it (itself included: a self-loop of weight 0).  Nodes are ``0..n-1`` and carry no attribute
+    (the reference's ``radius_graph`` sets no ``center``), an edge carries ``weight`` (the distance).  Built from
+    :func:`radius_edges`; raises ``ImportError`` without networkx."""
+    try:
+        import networkx as nx
+    except ImportError as e:
+        raise ImportError("radius_graph needs networkx (radius_edges returns the same edges as arrays without it)") from e
+    from . import _operands as ops
+
+    pts = ops.points(pcd, "points").points
+    edges, weights = radius_edges(pts, r, device=device, radius_fn=radius_fn)
+    g = nx.Graph()
+    g.add_nodes_from(range(len(pts)))
     g.add_weighted_edges_from((int(a), int(b), float(w)) for (a, b), w in zip(edges.tolist(), weights.tolist()))
     return g

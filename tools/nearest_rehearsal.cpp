@@ -5,6 +5,9 @@
 // A query the ring walk does not settle is counted as "far" (the device's far pass IS the all-pairs loop below).
 // Every cloud is then searched for its k nearest, k = 1, 2, 5, 64, 300: the serial list and the stop
 // rule of sc_nearest.h against all pairs sorted by (d2, index).
+// And for all targets within a radius: nn::radius_search on nn::plan_radius_grid, the row sorted by
+// nn::sort_row, against all pairs filtered by R2 and sorted by R3, at radii below, at and above the planned cell edge
+// and at one larger than the box (a grid of one cell).  No row may differ.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +28,7 @@ struct Sorted {
     std::vector<int> sidx;
 };
 
-static bool sort_targets(const char *name, const Cloud &ts, double max_distance, int64_t count, Sorted &s) {
+static bool sort_targets(const char *name, const Cloud &ts, double max_distance, int64_t count, Sorted &s, bool radius_plan = false) {
     const int64_t P = (int64_t)ts.size() / 3;
     double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
     for (int64_t t = 0; t < P; ++t)
@@ -34,7 +37,10 @@ static bool sort_targets(const char *name, const Cloud &ts, double max_distance,
             hi[a] = fmax(hi[a], ts[3 * t + a]);
         }
     nn::Grid &g = s.g;
-    nn::plan_grid(lo, hi, count, max_distance, g);
+    if (radius_plan)
+        nn::plan_radius_grid(lo, hi, count, max_distance, g);
+    else
+        nn::plan_grid(lo, hi, count, max_distance, g);
     const int64_t ncell = (int64_t)g.n[0] * g.n[1] * g.n[2];
     if (ncell > nn::cell_cap(P) || ncell < 1) {
         printf("%s: %lld cells over the cap\n", name, (long long)ncell);
@@ -110,6 +116,48 @@ static void run_knn(const char *name, const Cloud &qs, const Cloud &ts, double m
     if (wrong) ++g_fail;
 }
 
+// All targets within a radius: radius_search on the grid of plan_radius_grid (sort_targets checks per
+// target that none is clamped), the row put in order by sort_row, against all pairs under R2 and R3.
+static void run_radius(const char *name, const Cloud &qs, const Cloud &ts, double radius, const char *what) {
+    if (!(radius * radius >= DBL_MIN) || !std::isfinite(radius * radius)) return;  // R5: sc_radius refuses it
+    const int64_t Q = (int64_t)qs.size() / 3, P = (int64_t)ts.size() / 3;
+    Sorted s;
+    if (!sort_targets(name, ts, radius, P, s, true)) return;
+    const nn::Grid &g = s.g;
+    std::vector<double> all_d(P), kd;
+    std::vector<int> order, ki;
+    int64_t wrong = 0, total = 0, longest = 0, at_radius = 0;
+    for (int64_t q = 0; q < Q; ++q) {
+        order.clear();
+        for (int64_t t = 0; t < P; ++t) {
+            all_d[t] = nn::dist2(qs[3 * q], qs[3 * q + 1], qs[3 * q + 2], ts[3 * t], ts[3 * t + 1], ts[3 * t + 2]);
+            if (all_d[t] < g.md2) order.push_back((int)t);
+            at_radius += all_d[t] == g.md2;
+        }
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return nn::key_less(all_d[a], a, all_d[b], b); });
+        kd.clear();
+        ki.clear();
+        nn::radius_search(g, s.start.data(), s.spts.data(), s.sidx.data(), qs[3 * q], qs[3 * q + 1], qs[3 * q + 2], [&](double d, int i) {
+            kd.push_back(d);
+            ki.push_back(i);
+        });
+        nn::sort_row(kd.data(), ki.data(), (int)kd.size(), 0, 1, [] {});
+        bool ok = kd.size() == order.size();
+        for (size_t j = 0; ok && j < order.size(); ++j) ok = ki[j] == order[j] && kd[j] == all_d[order[j]];
+        if (!ok) ++wrong;
+        total += (int64_t)order.size();
+        longest = std::max<int64_t>(longest, (int64_t)order.size());
+    }
+    printf("%-28s radius %-10s %.4g Q %6lld P %6lld grid %d x %d x %d h %.4g: pairs %lld, longest row %lld, at the radius %lld, wrong %lld\n", name,
+           what, radius, (long long)Q, (long long)P, g.n[0], g.n[1], g.n[2], g.h, (long long)total, (long long)longest, (long long)at_radius,
+           (long long)wrong);
+    if (wrong) ++g_fail;
+    if (what[0] == 'o' && (g.n[0] != 1 || g.n[1] != 1 || g.n[2] != 1)) {  // "over the box": one cell
+        printf("%s: a radius larger than the box did not give a grid of one cell\n", name);
+        ++g_fail;
+    }
+}
+
 static void run(const char *name, const Cloud &qs, const Cloud &ts, double max_distance) {
     const int64_t Q = (int64_t)qs.size() / 3, P = (int64_t)ts.size() / 3;
     Sorted s;
@@ -148,6 +196,13 @@ static void run(const char *name, const Cloud &qs, const Cloud &ts, double max_d
            (long long)P, g.n[0], g.n[1], g.n[2], g.h, (long long)far, (long long)ties, (long long)unmatched, (long long)wrong);
     if (wrong) ++g_fail;
     for (int k : {1, 2, 5, 64, 300}) run_knn(name, qs, ts, max_distance, k);
+    double ext = 0.0;  // the largest extent of the targets' box
+    for (int64_t t = 0; t < P; ++t)
+        for (int a = 0; a < 3; ++a) ext = fmax(ext, ts[3 * t + a] - g.lo[a]);
+    run_radius(name, qs, ts, 0.5 * g.h, "below h");
+    run_radius(name, qs, ts, g.h, "at h");
+    run_radius(name, qs, ts, 2.5 * g.h, "above h");
+    run_radius(name, qs, ts, 2.0 * ext + 1.0, "over the box");
 }
 
 int main() {
@@ -201,6 +256,9 @@ int main() {
     run("outlier at 1e12", box(500, -2.0, 12.0), outlier, 0.0);
     run("huge coordinates", box(300, -1e308, 1e308), box(300, -1e308, 1e308), 0.0);
     run("tiny extent", box(300, 0.0, 1e-300), box(300, 0.0, 1e-300), 0.0);
+    run_radius("lattice ties", centres, lattice, 0.5, "exact");          // the edge midpoints' two targets lie at exactly 0.5: out
+    run_radius("lattice ties", centres, lattice, 0.8660254037844386, "exact");  // fl(sqrt(0.75)): its square against 0.75 decides
+    run_radius("300 copies", one, one, 1e-3, "copies");                  // rows of 300 zeros in rising index
     printf(g_fail ? "FAILED\n" : "ok\n");
     return g_fail ? 1 : 0;
 }
