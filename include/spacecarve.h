@@ -806,6 +806,56 @@ int sc_radius(const double *queries, int queries_on_device, int64_t Q,
               int64_t *long_out /* host, optional: rows the long-row launch sorted */,
               void *hip_stream);
 
+/*
+ * Graph distances to a root and connected components: the two graph steps of the reference's XU
+ * skeleton (plant3dvision/proc3d.py:212-426) -- nx.dijkstra_predecessor_and_distance(g, root)'s distances and
+ * nx.connected_components, of the whole graph or of the nodes of one key -- over the rows sc_knn and sc_radius return,
+ * on the GPU.  The distances are PINNED: a label-correcting fixpoint in float64 gives Dijkstra's numbers bit for bit
+ * (tests/test_graph_host.py compares with networkx and scipy).
+ *
+ * The graph: N nodes and rows of arcs, in one of two forms --
+ *   CSR:          offsets int64 [N + 1], index int32 [E]            (sc_radius of a cloud against itself);
+ *   fixed length: offsets == NULL, row_len = k, index int32 [N][k], -1 in unused places, E = N * k   (sc_knn);
+ * then M extra pairs, extra int32 [M][2] with extra_w double [M] (plain weights), which may be NULL with M == 0.  All
+ * arrays, the outputs among them, live on the host or on the device as on_device says; device arrays are read in place
+ * on the given stream.
+ *   G1. every arc (i, j, w) with j != i is an undirected edge, usable in both directions (knn rows are not symmetric,
+ *       the reference's nx.Graph is).  Self-arcs and repeated arcs change nothing.  weights double [E] are taken as
+ *       they are, or with weights_squared as sqrt of the given d2: computed on the device in float64, correctly rounded;
+ *   G2. sc_graph_distances: d[root] = +0.0; d[v] is the least, over all walks root = v0 .. vm = v, of the left-to-right
+ *       float64 sum ((0 + w1) + w2) + ..; +inf where no walk exists.  This is what Dijkstra with a float64 accumulator
+ *       returns.  dist_out double [N].  rounds_out: NULL, or one host int64 that receives the number of rounds run.  The
+ *       call always ends in a wait (the rounds are counted on the host, SC_GRAPH_ROUNDS_PER_WAIT between two looks);
+ *   G3. sc_graph_components: without a key label[v] is the rank of v's component when components are ordered by their
+ *       smallest member (sc_dbscan's numbering).  With key int32 [N] an edge joins its ends only where
+ *       key[i] == key[j] >= 0; nodes with key < 0 get label -1 and arcs to them are ignored.  labels_out int32 [N];
+ *       ncomponents_out: NULL, or one host int32 (the call then ends in a wait, as it does with host arrays);
+ *   G4. refused (SC_ERR_INVALID, before the first device call for host arrays; for device arrays by a first kernel
+ *       that only judges, as sc_nearest does for coordinates): an index outside -1 .. N - 1 (-1 only in the fixed-length
+ *       form; an extra pair outside 0 .. N - 1), offsets that do not rise from 0 to E, weights that are NaN, negative or
+ *       infinite (places holding -1 are not looked at), root outside 0 .. N - 1, N, E or E + M outside 0 .. 2^31 - 1,
+ *       E != N * row_len in the fixed-length form, NULL arrays, the device ordinal.  N == 0 makes no device call.
+ * The frontier loop runs at most N rounds (a lowering walk has fewer than N arcs); a frontier left after that is
+ * SC_ERR_DEVICE.  Work buffers (the adjacency at 12 bytes per directed arc, two frontiers, stamps, scan storage; copies
+ * of host arrays) are kept per device between calls while they are at most 1 GiB, ordered across streams as
+ * sc_dbscan's are, and given back by sc_graph_release.  Errors are read with sc_graph_error (the unit's own last
+ * message).  sc_graph_set_blocks caps every grid of the unit, 0 restores the default: tests drive the grid-stride loops
+ * past their first trip with it; no answer depends on it.
+ */
+#define SC_GRAPH_ROUNDS_PER_WAIT 64
+int sc_graph_distances(int64_t N, const int64_t *offsets /* [N + 1] or NULL */, int row_len, const int32_t *index /* [E] */,
+                       const double *weights /* [E] */, int64_t E, int weights_squared,
+                       const int32_t *extra /* [M, 2] */, const double *extra_w /* [M] */, int64_t M,
+                       int on_device /* where every array and dist_out live */, int64_t root, int device,
+                       double *dist_out /* [N] */, int64_t *rounds_out /* host, may be null */, void *hip_stream);
+int sc_graph_components(int64_t N, const int64_t *offsets /* [N + 1] or NULL */, int row_len, const int32_t *index /* [E] */, int64_t E,
+                        const int32_t *extra /* [M, 2] */, int64_t M, const int32_t *key /* [N] or NULL */,
+                        int on_device /* where every array and labels_out live */, int device,
+                        int32_t *labels_out /* [N] */, int32_t *ncomponents_out /* host, may be null */, void *hip_stream);
+const char *sc_graph_error(void);
+void sc_graph_release(void);
+void sc_graph_set_blocks(int blocks);
+
 /* Page-locked host memory for the read-back of sc_get_values (no reference counterpart: the
  * reference's values_h is a pageable NumPy array, cl.py:173).  A 512 MiB volume reads back in
  * ~10 ms into such a buffer against ~50 ms into pageable memory, but allocating it takes ~0.1 s

@@ -51,6 +51,7 @@ SC_FILTER_LINEAR, SC_FILTER_EXCESS_GREEN = 0, 1
 SC_EVAL_F32, SC_EVAL_F64, SC_EVAL_U8 = 1, 2, 3
 SC_KNN_MAX = 512  # the largest k of sc_knn
 SC_RADIUS_LDS_ROW = 1024  # the longest row sc_radius sorts in LDS
+SC_GRAPH_ROUNDS_PER_WAIT = 64  # rounds sc_graph_distances enqueues between two looks at the frontier's length
 SC_FOOT = {"t0": 0, "t90": 1, "t180": 2, "t270": 3, "diamond": 4, "square": 5}  # SC_FOOT_*: names of masks2d._FOOTPRINTS
 
 # name -> (restype, [argtypes]); 'p' pointer, 'i' int, 'q' int64, 'f' float, 's' const char*
@@ -156,6 +157,11 @@ _SIGNATURES = {
     "sc_knn": ("i", ["p", "i", "q", "p", "i", "q", "i", "d", "i", "p", "p", "i", "p", "p"]),
     "sc_knn_set_aim": ("v", ["i"]),
     "sc_radius": ("i", ["p", "i", "q", "p", "i", "q", "d", "i", "p", "p", "p", "p", "q", "i", "p", "p", "p"]),
+    "sc_graph_distances": ("i", ["q", "p", "i", "p", "p", "q", "i", "p", "p", "q", "i", "q", "i", "p", "p", "p"]),
+    "sc_graph_components": ("i", ["q", "p", "i", "p", "q", "p", "q", "p", "i", "i", "p", "p", "p"]),
+    "sc_graph_error": ("s", []),
+    "sc_graph_release": ("v", []),
+    "sc_graph_set_blocks": ("v", ["i"]),
     "sc_vol2pcd_class": ("i", ["p", "i", "i", "q", "q", "q", "p", "d", "d", "p", "i", "p", "p", "p"]),
     "sc_create_sharded": ("i", ["p", "q", "q", "q", "p", "f", "i", "f", "p", "i", "i"]),
     "sc_group_destroy": ("v", ["p"]),

@@ -96,6 +96,67 @@ def ids(a, what):
     return SimpleNamespace(data=arr, n=len(arr), on_device=0, tdevice=None, ptr=nat.addr(arr) if arr.size else 0)
 
 
+def graph_rows(rows, n=None, extra=None):
+    """The rows of arcs the graph unit reads -- ``(index [N, k], d2 [N, k])`` as ``knn_points`` returns them or
+    ``(offsets [N + 1], index [E], d2 [E])`` as ``radius_points`` does -- and the optional extra pairs ``(edges [M, 2],
+    weights [M])``: all array-likes (converted to int64 offsets, int32 indices, float64 values) or all contiguous CUDA
+    tensors of those dtypes on one device, used in place.  ``n``, when given, must be the rows' node count.
+
+    Returns ``n``, ``E``, ``M``, ``row_len`` (0 for the CSR form), the addresses ``offsets`` (0 for the fixed form),
+    ``index``, ``values``, ``extra``, ``extra_w`` (0 where empty), ``arcs`` (the index array or tensor), ``on_device``,
+    ``tdevice`` (``None`` for arrays) and ``keep``, what the addresses point into."""
+    rows = tuple(rows)
+    if len(rows) not in (2, 3):
+        raise ValueError("rows must be (index, d2) or (offsets, index, d2)")
+    parts = list(rows) + (list(extra) if extra is not None else [])
+    if extra is not None and len(parts) != len(rows) + 2:
+        raise ValueError("extra must be (edges [M, 2], weights [M])")
+    kinds = [is_tensor(a) for a in parts]
+    if any(kinds) and not all(kinds):
+        raise ValueError("rows and extra must be all arrays or all CUDA tensors")
+    on_device = int(all(kinds))
+    tdev = None
+    if on_device:
+        import torch
+        want = [torch.int64] * (len(rows) - 2) + [torch.int32, torch.float64] + [torch.int32, torch.float64] * (extra is not None)
+        for a, dt in zip(parts, want):
+            if a.dtype != dt or not a.is_cuda or not a.is_contiguous():
+                raise ValueError("device rows must be contiguous CUDA tensors: int64 offsets, int32 indices, float64 values")
+        tdev = same([a.device for a in parts], "devices")
+    else:
+        want = [np.int64] * (len(rows) - 2) + [np.int32, np.float64] + [np.int32, np.float64] * (extra is not None)
+        parts = [np.ascontiguousarray(np.asarray(a, dtype=dt)) for a, dt in zip(parts, want)]
+    offsets = parts[0] if len(rows) == 3 else None
+    index, values = parts[len(rows) - 2], parts[len(rows) - 1]
+    if tuple(index.shape) != tuple(values.shape):
+        raise ValueError("index and d2 must have one shape")
+    if offsets is None:
+        if len(index.shape) != 2 or index.shape[1] < 1:
+            raise ValueError("rows of fixed length must be [N, k] with k at least 1")
+        nodes, row_len = int(index.shape[0]), int(index.shape[1])
+    else:
+        if len(offsets.shape) != 1 or offsets.shape[0] < 1 or len(index.shape) != 1:
+            raise ValueError("CSR rows must be offsets [N + 1], index [E], d2 [E]")
+        nodes, row_len = int(offsets.shape[0]) - 1, 0
+    if n is not None and int(n) != nodes:
+        raise ValueError(f"n is {int(n)}, the rows hold {nodes} nodes")
+    E = int(np.prod(index.shape))
+    M = 0
+    if extra is not None:
+        edges, weights = parts[-2], parts[-1]
+        M = int(weights.shape[0]) if len(weights.shape) == 1 else -1
+        if M and (M < 0 or tuple(edges.shape) != (M, 2)):
+            raise ValueError("extra must be (edges [M, 2], weights [M])")
+
+    def at(a, count):
+        return ptr_of(a) if count else 0
+
+    return SimpleNamespace(n=nodes, E=E, M=M, row_len=row_len, offsets=0 if offsets is None else ptr_of(offsets), index=at(index, E),
+                           values=at(values, E), extra=at(parts[-2], M) if M else 0, extra_w=at(parts[-1], M) if M else 0,
+                           arcs=index, offsets_data=offsets, extra_data=parts[-2] if M else None, on_device=on_device,
+                           tdevice=tdev, keep=parts)
+
+
 def same(things, what):
     """The one value all ``things`` share, or the refusal that lists the values they take."""
     if any(t != things[0] for t in things):

@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "sc_points.h"
+#include "sc_unionfind.h"
 #include "sc_unit.h"
 
 namespace {
@@ -143,33 +144,8 @@ __global__ __launch_bounds__(kB) void dbscan_core_kernel(int P, Grid g, int64_t 
 }
 
 // ---- link (rule 4) ---------------------------------------------------------------------------------------------
-// parent[] is indexed by ORIGINAL index and only ever holds a smaller-or-equal index of the same component: a root
-// (parent[a] == a) is hung under a smaller root with a compare-and-swap, so when the launch ends each component's
-// root is its smallest index whatever the order of the atomics was.  Blocks on different XCDs share parent[] inside
-// this launch and their L2s are not coherent: EVERY access here is a relaxed agent-scope atomic, none a plain load.
-#define DB_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ int find_root(int *parent, int a) {
-    for (;;) {
-        const int p = __hip_atomic_load(&parent[a], DB_RLX);
-        if (p == a) return a;
-        const int gp = __hip_atomic_load(&parent[p], DB_RLX);
-        if (gp != p) (void)__hip_atomic_fetch_min(&parent[a], gp, DB_RLX);  // path halving: a non-root only moves up
-        a = p;
-    }
-}
-
-__device__ __forceinline__ void unite(int *parent, int a, int b) {
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }  // a > b: hang a under b
-        int expect = a;
-        if (__hip_atomic_compare_exchange_strong(&parent[a], &expect, b, __ATOMIC_RELAXED, DB_RLX)) return;
-    }
-}
-
+// parent[] is indexed by ORIGINAL index; find_root / unite and the rule every access to it obeys inside this launch are
+// sc_unionfind.h, shared with graph.hip: min-index roots, so each component's root is its smallest index.
 __global__ __launch_bounds__(kB) void dbscan_link_kernel(int P, Grid g, const uint32_t *__restrict__ start, const uint4 *__restrict__ scell,
                                                          const double *__restrict__ spts, const uint8_t *__restrict__ core, int *parent) {
     const int s = (int)(blockIdx.x * kB + threadIdx.x);

@@ -1,6 +1,6 @@
-// sc_unit.h -- the host scaffold of the stand-alone device units (vol2pcd, label_points, masks_rgb, dbscan, evaluate, class_select, nearest, undistort): the
+// sc_unit.h -- the host scaffold of the stand-alone device units (vol2pcd, label_points, masks_rgb, dbscan, evaluate, class_select, nearest, undistort, graph): the
 // "last error" of a unit, the layout of a work buffer, the per-device work-buffer slot of DESIGN.md 12 and the scope
-// of one call on it.  (Device text that units share: sc_quads.h, sc_bitplane.h, sc_points.h.)
+// of one call on it.  (Device text that units share: sc_quads.h, sc_bitplane.h, sc_points.h, sc_unionfind.h.)
 // Host only, internal linkage: every unit that includes it has its own copy and its own state.
 #pragma once
 

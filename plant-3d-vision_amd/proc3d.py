@@ -54,6 +54,14 @@ def release_device_buffers():
         nat.backend().call(entry)
 
 
+def release_graph_buffers():
+    """Give back the device work buffers ``graph_distances`` and ``graph_components`` keep between calls
+    (``sc_graph_release``; they are kept only while they are at most 1 GiB).  It stands beside
+    ``release_device_buffers``, whose five entries in ``RELEASES`` stay what they are: call both to give everything back."""
+    from . import _native as nat
+    nat.backend().call("sc_graph_release")
+
+
 def set_scratch_limit(nbytes):
     """Largest device work buffers a ``vol2pcd`` call may take (default 8 GiB; 0 = no limit): a volume that needs
     more -- 49 bytes per voxel -- goes through in x-slabs with a halo, same points in the same order."""
@@ -648,3 +656,241 @@ def radius_graph(pcd, r, device=0, radius_fn=None):
     g.add_nodes_from(range(len(pts)))
     g.add_weighted_edges_from((int(a), int(b), float(w)) for (a, b), w in zip(edges.tolist(), weights.tolist()))
     return g
+
+
+# ---- the graph steps of the XU skeleton (plant3dvision/proc3d.py:212-426) ---------------------------------
+def _graph_call(entry, *args):
+    """One call of the graph unit; its errors are read with the unit's own getter, ``sc_graph_error``."""
+    from . import _native as nat
+    nat.check(nat.backend().call(entry, *args), entry, "sc_graph_error")
+
+
+def _graph_place(g, device):
+    """``(device index, stream)`` of a graph call: the tensors' device and torch's current stream there, or ``device``."""
+    from . import _operands as ops
+    return ops.tensor_place(g.arcs) if g.on_device else (int(device), 0)
+
+
+def graph_distances(rows, root, n=None, extra=None, device=0, return_rounds=False):
+    """Shortest-path distances from node ``root`` to every node of the graph the rows span, on the GPU
+    (``sc_graph_distances``, ``csrc/graph.hip``): the distances of
+    ``nx.dijkstra_predecessor_and_distance(g, root)`` over ``knn_graph`` / ``radius_graph`` (``proc3d.py:287``), without
+    the ``networkx.Graph``.
+
+    rows : ``(index [N, k], d2 [N, k])`` as :func:`knn_points` ``(p, p, k)`` returns them (``-1`` in unused places) or
+        ``(offsets, index, d2)`` as :func:`radius_points` ``(p, p, r)`` does: NumPy arrays -> a NumPy float64 ``[N]``; or
+        contiguous CUDA tensors on one device, read in place on torch's current stream -> a CUDA tensor there.  Mixed
+        kinds raise ``ValueError``.  The values are SQUARED distances; an arc's weight is their square root (rule G1).
+    extra : ``None`` or ``(edges int32 [M, 2], weights float64 [M])``, more edges with plain weights: what
+        :func:`connect_edges` returns.
+    n : the node count, when given checked against the rows.
+    return_rounds : also return the number of frontier rounds the device ran.
+
+    PINNED: rule G2 -- ``d[root] = 0``, ``d[v]`` the least left-to-right float64 sum over all walks, every
+    arc usable in both directions, ``+inf`` where no walk exists -- is what Dijkstra with a float64 accumulator returns,
+    bit for bit; ``tests/test_graph_host.py`` compares the checker with networkx and scipy.  Rule G4: an index out of
+    range, offsets that do not rise from 0 to E, a NaN, negative or infinite value and a bad root raise ``ValueError``.
+    No nodes: an empty result, no native call.  There is no CPU fallback."""
+    from . import _native as nat, _operands as ops
+
+    g = ops.graph_rows(rows, n, extra)
+    root = int(root)
+    if g.n and not 0 <= root < g.n:
+        raise ValueError(f"root must be 0 .. {g.n - 1}")
+    rounds = np.zeros(1, dtype=np.int64)
+    if g.on_device:
+        import torch
+        out = torch.empty((g.n,), dtype=torch.float64, device=g.tdevice)
+    else:
+        out = np.empty(g.n, dtype=np.float64)
+    if g.n:
+        dev, stream = _graph_place(g, device)
+        _graph_call("sc_graph_distances", g.n, g.offsets, g.row_len, g.index, g.values, g.E, 1, g.extra, g.extra_w, g.M, g.on_device,
+                    root, int(dev), ops.ptr_of(out), nat.addr(rounds) if return_rounds else 0, int(stream))
+    return (out, int(rounds[0])) if return_rounds else out
+
+
+def graph_components(rows, key=None, n=None, extra=None, device=0):
+    """Connected components of the graph the rows span, on the GPU (``sc_graph_components``, ``csrc/graph.hip``):
+    ``nx.connected_components`` of ``knn_graph`` / ``radius_graph`` (``proc3d.py:229``), or with ``key`` the components
+    of every ``g.subgraph(nodes of one key)`` at once (``proc3d.py:307-308``).
+
+    rows, extra, n : as for :func:`graph_distances` (the values are judged for shape only).
+    key : ``None`` or int32 ``[N]`` of the rows' kind: an edge joins its ends only where ``key[i] == key[j] >= 0``.
+
+    Returns ``(labels int32 [N], components)``: ``labels[v]`` is the rank of ``v``'s component when components are
+    ordered by their smallest member (``cluster_dbscan``'s numbering), ``-1`` for nodes whose key is negative (rule G3)."""
+    from . import _native as nat, _operands as ops
+
+    g = ops.graph_rows(rows, n, extra)
+    kptr = 0
+    if key is not None:
+        if ops.is_tensor(key) != bool(g.on_device):
+            raise ValueError("rows and key must be all arrays or all CUDA tensors")
+        k = ops.ids(key, "key")
+        if k.n != g.n:
+            raise ValueError("one key per node")
+        if k.on_device and k.tdevice != g.tdevice:
+            raise ValueError("rows and key must be on one device")
+        kptr = k.ptr
+    count = np.zeros(1, dtype=np.int32)
+    if g.on_device:
+        import torch
+        labels = torch.empty((g.n,), dtype=torch.int32, device=g.tdevice)
+    else:
+        labels = np.empty(g.n, dtype=np.int32)
+    if g.n:
+        dev, stream = _graph_place(g, device)
+        _graph_call("sc_graph_components", g.n, g.offsets, g.row_len, g.index, g.E, g.extra, g.M, kptr, g.on_device, int(dev),
+                    ops.ptr_of(labels), nat.addr(count), int(stream))
+    return labels, int(count[0])
+
+
+def connect_edges(points, labels, root_index, device=0):
+    """The edges the reference's ``connect_graph`` (``proc3d.py:212-263``) adds to make a graph connected, in an
+    order-free form.  ``labels``: the component of every point (:func:`graph_components`).  While a point lies outside
+    the root's component ``R``: among all pairs ``(i not in R, j in R)`` the one with the least key ``(d2, i, j)`` -- found
+    with :func:`nearest_points` ``(outside, inside)`` on the GPU -- becomes an edge of weight ``sqrt(d2)``, and the whole
+    component of ``i`` joins ``R`` (a host relabel).
+
+    Returns ``(edges int32 [M, 2], weights float64 [M])``, ``M = components - 1``, each edge as ``(i, j)``: feed them to
+    :func:`graph_distances` / :func:`graph_components` as ``extra``.
+
+    Deviation: the reference stores ``nnorm``, the norm of the LAST point its loop visited, as the new edge's weight where
+    it means ``minnorm`` (``proc3d.py:262-263``); ours is the minimum, the length of the edge."""
+    from . import _operands as ops
+
+    p = ops.points(points, "points")
+    if p.on_device:
+        raise ValueError("connect_edges takes host points (the components are relabelled on the host)")
+    lab = np.asarray(labels.cpu() if ops.is_tensor(labels) else labels).astype(np.int64).reshape(-1)
+    if lab.shape[0] != p.n:
+        raise ValueError("one label per point")
+    root = int(root_index)
+    if p.n and not 0 <= root < p.n:
+        raise ValueError(f"root_index must be 0 .. {p.n - 1}")
+    edges, weights = [], []
+    inside = lab == lab[root] if p.n else np.zeros(0, dtype=bool)
+    while not inside.all():
+        out_ids, in_ids = np.flatnonzero(~inside), np.flatnonzero(inside)
+        index, d2 = nearest_points(p.points[out_ids], p.points[in_ids], device=device)
+        a = int(np.argmin(d2))  # the first least d2: the smallest i; nearest_points gave it its smallest j (rule N2)
+        i, j = int(out_ids[a]), int(in_ids[index[a]])
+        edges.append((i, j))
+        weights.append(np.sqrt(d2[a]))
+        inside |= lab == lab[i]
+    return np.array(edges, dtype=np.int32).reshape(-1, 2), np.array(weights, dtype=np.float64)
+
+
+def _host(a):
+    from . import _operands as ops
+    return a.cpu().numpy() if ops.is_tensor(a) else np.asarray(a)
+
+
+def distance_to_root_clusters(points, rows, root_index, bin_size, extra=None, device=0):
+    """The clusters of the reference's ``distance_to_root_clusters`` (``proc3d.py:266-329``) as arrays: the nodes are cut
+    into bins of their distance to the root, a cluster is a connected component of one bin, and two clusters are joined
+    where an arc joins their nodes.  The distances and the components are computed on the GPU (:func:`graph_distances`,
+    :func:`graph_components` with the bins as keys); the bins are NumPy expressions (torch's for tensors), the
+    renumbering, the centres and the cluster edges host NumPy.
+
+    Returns ``(cluster, centers float64 [C, 3], cluster_edges int32 [K, 2], distances)``; ``cluster`` (int32 ``[N]``) and
+    ``distances`` (float64 ``[N]``) are NumPy arrays or CUDA tensors as the rows are:
+      * ``n_bins = max(1, ceil(max finite d / bin_size))``, ``bin = min(floor(d / bin_size), n_bins - 1)``, ``-1`` for
+        unreached nodes;
+      * clusters are numbered by ``(bin, smallest member)``; unreached nodes have cluster ``-1``;
+      * ``centers[c]`` is ``np.bincount(cluster, weights=coordinate) / count``;
+      * ``cluster_edges`` are the unique pairs ``(a < b)`` of distinct clusters joined by an arc, sorted.
+
+    Deviations: the reference function cannot be executed -- ``n = c[0]`` on a set raises ``TypeError`` on
+    the first component (``proc3d.py:320``); its ``bisect`` cut is shifted by one sorted place (the first node of a bin
+    falls into the bin before); it numbers components in set-iteration order.  Ours are the rules above."""
+    from . import _operands as ops
+
+    pts = ops.points(points, "points")
+    xyz = _host(pts.points)
+    g = ops.graph_rows(rows, pts.n, extra)
+    bin_size = float(bin_size)
+    if not (bin_size > 0.0 and bin_size != float("inf")):
+        raise ValueError("bin_size must be positive and finite")
+    d = graph_distances(rows, root_index, extra=extra, device=device)
+    if g.on_device:
+        import torch
+        finite = torch.isfinite(d)
+        n_bins = max(1, int(torch.ceil(d[finite].max() / bin_size).item())) if g.n else 1
+        bins = torch.clamp(torch.floor(torch.where(finite, d, torch.zeros_like(d)) / bin_size), max=n_bins - 1).to(torch.int32)
+        bins = torch.where(finite, bins, torch.full_like(bins, -1)).contiguous()
+    else:
+        finite = np.isfinite(d)
+        n_bins = max(1, int(np.ceil(d[finite].max() / bin_size))) if g.n else 1
+        bins = np.minimum(np.floor(np.where(finite, d, 0.0) / bin_size), n_bins - 1).astype(np.int32)
+        bins = np.where(finite, bins, np.int32(-1)).astype(np.int32)
+    labels, count = graph_components(rows, key=bins, extra=extra, device=device)
+
+    # the host tail: components by (bin, smallest member), centres, the quotient's edges
+    lab, hbins = _host(labels).astype(np.int64), _host(bins)
+    used = lab >= 0
+    _, first = np.unique(lab[used], return_index=True)  # labels rise with the smallest member: first[c] finds it
+    smallest = np.flatnonzero(used)[first]
+    order = np.lexsort((smallest, hbins[smallest]))
+    renumber = np.empty(count, dtype=np.int64)
+    renumber[order] = np.arange(count)
+    cluster = np.where(used, renumber[np.where(used, lab, 0)] if count else -1, -1).astype(np.int32)
+    counts = np.bincount(cluster[used], minlength=count).astype(np.float64)
+    centers = np.stack([np.bincount(cluster[used], weights=xyz[used, c], minlength=count) / counts for c in range(3)], axis=1).reshape(-1, 3)
+    index = _host(g.arcs).reshape(-1).astype(np.int64)
+    if g.row_len:
+        src = np.repeat(np.arange(g.n, dtype=np.int64), g.row_len)
+    else:
+        src = np.repeat(np.arange(g.n, dtype=np.int64), np.diff(_host(g.offsets_data)))
+    keep = index >= 0
+    src, dst = src[keep], index[keep]
+    if g.M:
+        more = _host(g.extra_data).astype(np.int64)
+        src, dst = np.concatenate([src, more[:, 0]]), np.concatenate([dst, more[:, 1]])
+    ca, cb = cluster[src].astype(np.int64), cluster[dst].astype(np.int64)
+    cross = (ca >= 0) & (cb >= 0) & (ca != cb)
+    lo, hi = np.minimum(ca[cross], cb[cross]), np.maximum(ca[cross], cb[cross])
+    pairs = np.unique(lo * max(count, 1) + hi)
+    cluster_edges = np.stack([pairs // max(count, 1), pairs % max(count, 1)], axis=1).astype(np.int32).reshape(-1, 2)
+    if g.on_device:
+        import torch
+        cluster = torch.from_numpy(cluster).to(g.tdevice)
+    return cluster, centers, cluster_edges, d
+
+
+def skeleton_from_distance_to_root_clusters(pcd, root_index, binsize, k, connect_all_points=True, device=0):
+    """The XU method (``proc3d.py:392-426``; same signature, ``device`` added): the k-nearest-neighbour graph of the cloud
+    (:func:`knn_points`), connected when ``connect_all_points`` (:func:`graph_components`, :func:`connect_edges`), its
+    nodes clustered by distance to ``root_index`` (:func:`distance_to_root_clusters`), and the minimum spanning tree of
+    the cluster graph.
+
+    Returns ``(tree, cluster_values)``: ``tree`` is ``nx.minimum_spanning_tree`` of the ``networkx.Graph`` whose nodes
+    ``0..C-1`` carry ``center`` and whose edges are the cluster edges in sorted order; ``cluster_values`` is the dict
+    ``{node: cluster}``, unreached nodes absent as in the reference.  Raises ``ImportError`` without networkx.
+
+    Deviation: the reference's ``quotient_graph`` weights a cluster edge with the sum of the arc weights between the two
+    clusters, added in set-iteration order; ours carry no weight (every edge counts 1), so the tree is Kruskal's over
+    the sorted pairs.  The deviations of :func:`distance_to_root_clusters` and :func:`connect_edges` hold here too."""
+    try:
+        import networkx as nx
+    except ImportError as e:
+        raise ImportError("skeleton_from_distance_to_root_clusters needs networkx (distance_to_root_clusters returns the clusters as "
+                          "arrays without it)") from e
+    from . import _operands as ops
+
+    pts = ops.points(pcd, "points")
+    if pts.on_device:
+        raise ValueError("skeleton_from_distance_to_root_clusters takes host points")
+    rows = knn_points(pts.points, pts.points, int(k), device=device)
+    extra = None
+    if connect_all_points and pts.n:
+        labels, count = graph_components(rows, device=device)
+        if count > 1:
+            extra = connect_edges(pts.points, labels, root_index, device=device)
+    cluster, centers, cluster_edges, _ = distance_to_root_clusters(pts.points, rows, root_index, binsize, extra=extra, device=device)
+    g = nx.Graph()
+    for c in range(len(centers)):
+        g.add_node(c, center=centers[c])
+    g.add_edges_from((int(a), int(b)) for a, b in cluster_edges.tolist())
+    return nx.minimum_spanning_tree(g), {int(v): int(c) for v, c in enumerate(cluster.tolist()) if c >= 0}
