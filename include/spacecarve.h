@@ -852,6 +852,53 @@ int sc_graph_components(int64_t N, const int64_t *offsets /* [N + 1] or NULL */,
                         const int32_t *extra /* [M, 2] */, int64_t M, const int32_t *key /* [N] or NULL */,
                         int on_device /* where every array and labels_out live */, int device,
                         int32_t *labels_out /* [N] */, int32_t *ncomponents_out /* host, may be null */, void *hip_stream);
+/*
+ * The quotient of the graph under a labelling: what the XU skeleton needs behind the components -- the
+ * clusters renumbered, their member counts and centres, and nx.quotient_graph's edges with their weights -- on the GPU.
+ * The graph, the extra pairs, on_device (one flag for every array and output), the slots, the error getter and the grid
+ * cap are sc_graph_distances'.  labels int32 [N] name a label 0 .. L - 1 per node, key int32 [N] (or NULL) and points
+ * double [N][3] (or NULL) belong to the nodes.
+ *   Q1. clusters: a node with labels[v] < 0 is outside: cluster_out[v] = -1, and arcs to it are ignored.  A label with
+ *       no member gets no cluster.  The labels that have members are ordered by (kmin, smallest): kmin the least key
+ *       over the label's members (signed compare; 0 without a key), smallest its least member.  cluster is the rank in
+ *       that order, C the number of such labels.  With G3's labels and key = the bins this is "numbered by (bin,
+ *       smallest member)"; without a key it is G3's numbering.  cluster_out int32 [N];
+ *   Q2. centres: counts_out[c] is the number of members; centers_out[c][a] is s / (double)counts[c], where s starts at
+ *       +0.0 and adds points[v][a] over the members in rising v, left to right in float64; the division is correctly
+ *       rounded.  This is np.bincount(cluster, weights=...) / count bit for bit.  Points are not judged: NaN and
+ *       infinities flow through as they do in NumPy.  counts_out int32 [L], centers_out double [L][3] (may be NULL
+ *       when points is NULL); rows C .. L - 1 of both are left untouched;
+ *   Q3. cluster edges: the pairs (a < b) of distinct clusters for which some arc, of the rows or extra and in either
+ *       direction, joins a member of a with a member of b; sorted lexicographically, K of them.  edges_out int32
+ *       [capacity][2];
+ *   Q4. weights: first the arcs fold into undirected node edges: every unordered node pair {i < j} with at least one arc
+ *       gets w{i,j}, the least of its arcs' weights (by G1 the square root of d2 when weights_squared; under N1 d2 is
+ *       bitwise symmetric, so for knn and radius rows all arcs of a pair agree, and the minimum makes the rule
+ *       order-free for anything else).  edge_w_out[e] starts at +0.0 and adds w{i,j} over the node pairs that join the
+ *       two clusters, in rising (i, j), left to right: the `weight` of nx.quotient_graph up to summation order.
+ *       edge_w_out double [capacity] or NULL; weights and extra_w may be NULL when it is NULL;
+ *   Q5. capacity is sc_radius's R6: the call always computes C, K, cluster_out, the counts and the centres; it writes
+ *       edges_out / edge_w_out iff capacity >= K, otherwise it returns SC_OK with *nedges_out = K and leaves them
+ *       untouched;
+ *   Q6. refused (SC_ERR_INVALID): what G4 refuses, the weights judged only when edge_w_out is given; L outside 0 .. N;
+ *       a label >= L (host arrays before the first device call, device arrays by the judging kernel); NULL labels,
+ *       cluster_out, counts_out (with L > 0), centers_out with points (with L > 0), nclusters_out or nedges_out; a
+ *       negative capacity, or a positive one with NULL edges_out; edge_w_out without edges_out, without weights (E > 0)
+ *       or without extra_w (M > 0).  N == 0 makes no device call and gives C = K = 0.
+ * nclusters_out (host int32) and nedges_out (host int64) are required, so the call ends in a wait.  Waits in all: with
+ * device arrays three (the judge's flag; C and the number of crossing arcs, which size the sorts; K), with host arrays
+ * two (the last two) and one more when edge rows go home.  No floating-point atomic: every sum has the one order of its
+ * rule.  Work buffers, on the slots as above: per label 48 bytes; per node, when centres are asked for, 40 bytes; per
+ * arc (E + M places) 24 bytes, 40 with weights; scan and sort storage; copies of host arrays and of host outputs.
+ */
+int sc_graph_quotient(int64_t N, const int64_t *offsets /* [N + 1] or NULL */, int row_len, const int32_t *index /* [E] */,
+                      const double *weights /* [E] or NULL */, int64_t E, int weights_squared,
+                      const int32_t *extra /* [M, 2] */, const double *extra_w /* [M] or NULL */, int64_t M,
+                      const int32_t *labels /* [N] */, int64_t L, const int32_t *key /* [N] or NULL */,
+                      const double *points /* [N, 3] or NULL */, int on_device /* where every array and output lives */, int device,
+                      int32_t *cluster_out /* [N] */, int32_t *counts_out /* [L] */, double *centers_out /* [L, 3] or NULL */,
+                      int32_t *edges_out /* [capacity, 2] */, double *edge_w_out /* [capacity] or NULL */, int64_t capacity,
+                      int32_t *nclusters_out /* host */, int64_t *nedges_out /* host */, void *hip_stream);
 const char *sc_graph_error(void);
 void sc_graph_release(void);
 void sc_graph_set_blocks(int blocks);

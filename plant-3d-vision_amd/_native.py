@@ -159,6 +159,8 @@ _SIGNATURES = {
     "sc_radius": ("i", ["p", "i", "q", "p", "i", "q", "d", "i", "p", "p", "p", "p", "q", "i", "p", "p", "p"]),
     "sc_graph_distances": ("i", ["q", "p", "i", "p", "p", "q", "i", "p", "p", "q", "i", "q", "i", "p", "p", "p"]),
     "sc_graph_components": ("i", ["q", "p", "i", "p", "q", "p", "q", "p", "i", "i", "p", "p", "p"]),
+    "sc_graph_quotient": ("i", ["q", "p", "i", "p", "p", "q", "i", "p", "p", "q", "p", "q", "p", "p", "i", "i", "p", "p", "p", "p", "p", "q",
+                                "p", "p", "p"]),
     "sc_graph_error": ("s", []),
     "sc_graph_release": ("v", []),
     "sc_graph_set_blocks": ("v", ["i"]),

@@ -157,6 +157,19 @@ def graph_rows(rows, n=None, extra=None):
                            tdevice=tdev, keep=parts)
 
 
+def node_ids(g, a, what):
+    """One int32 id per node of ``g`` (a ``graph_rows`` record), of the rows' kind and on their device: the ``ids`` record
+    of ``a``.  ``what`` ("key", "labels") words the refusals."""
+    if is_tensor(a) != bool(g.on_device):
+        raise ValueError(f"rows and {what} must be all arrays or all CUDA tensors")
+    k = ids(a, what)
+    if k.n != g.n:
+        raise ValueError(f"one {what.rstrip('s')} per node")
+    if k.on_device and k.tdevice != g.tdevice:
+        raise ValueError(f"rows and {what} must be on one device")
+    return k
+
+
 def same(things, what):
     """The one value all ``things`` share, or the refusal that lists the values they take."""
     if any(t != things[0] for t in things):

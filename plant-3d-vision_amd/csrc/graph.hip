@@ -1,4 +1,5 @@
-// graph.hip -- distances to a root and connected components over the rows of sc_knn / sc_radius.
+// graph.hip -- distances to a root, connected components and the quotient under a labelling (DESIGN.md 21,
+// graph_quotient.inl) over the rows of sc_knn / sc_radius.
 //
 // The two graph steps of the reference's XU skeleton (plant3dvision/proc3d.py:212-426): what
 // nx.dijkstra_predecessor_and_distance(g, root) returns as distances, and nx.connected_components, of whole graphs or
@@ -42,7 +43,7 @@ constexpr unsigned long long kInfBits = 0x7FF0000000000000ull;
 thread_local UnitError g_err;
 std::atomic<int> g_blocks{0};  // sc_graph_set_blocks
 
-enum : unsigned { kBadIndex = 1, kBadOffsets = 2, kBadWeight = 4, kBadExtra = 8, kBadExtraWeight = 16 };
+enum : unsigned { kBadIndex = 1, kBadOffsets = 2, kBadWeight = 4, kBadExtra = 8, kBadExtraWeight = 16, kBadLabel = 32 };
 
 // The arcs as the caller gave them, in device memory: E places of rows, then M extra pairs.
 struct Arcs {
@@ -96,13 +97,14 @@ __device__ __forceinline__ bool arc_of(const Arcs &g, int64_t t, int &i, int &j,
 
 // ---- the judge of device inputs (rule G4) ------------------------------------------------------------------------
 // Reads every array within its stated length only, whatever it holds; the entry waits for the flag before any other
-// launch touches the arrays.
-__global__ __launch_bounds__(kB) void graph_flags_kernel(Arcs g, unsigned int *flag) {
+// launch touches the arrays.  labels: NULL, or the N labels of sc_graph_quotient, each below L (rule Q6).
+__global__ __launch_bounds__(kB) void graph_flags_kernel(Arcs g, const int32_t *__restrict__ labels, int L, unsigned int *flag) {
     const int64_t stride = (int64_t)gridDim.x * kB;
     int64_t work = g.E > g.M ? g.E : g.M;
-    if (g.offsets && work < (int64_t)g.N + 1) work = (int64_t)g.N + 1;
+    if ((g.offsets || labels) && work < (int64_t)g.N + 1) work = (int64_t)g.N + 1;
     unsigned bad = 0;
     for (int64_t t = (int64_t)blockIdx.x * kB + threadIdx.x; t < work; t += stride) {
+        if (labels && t < g.N && labels[t] >= L) bad |= kBadLabel;
         if (t < g.E) {
             const int j = g.index[t];
             if (j >= g.N || j < (g.row_len ? -1 : 0)) bad |= kBadIndex;
@@ -244,11 +246,14 @@ WorkSlot g_slots[kUnitDevices];
 
 bool host_weight_ok(double x) { return x >= 0.0 && std::isfinite(x); }
 
+const char kBadLabelText[] = "label outside .. L - 1 (a negative label is an outside node)";
+
 const char *flag_text(unsigned bad) {
     if (bad & kBadOffsets) return "offsets must rise from 0 to E";
     if (bad & kBadIndex) return "index outside -1 .. N - 1 (-1 only in rows of fixed length)";
     if (bad & kBadWeight) return "weights must be finite and not negative";
     if (bad & kBadExtra) return "extra pair outside 0 .. N - 1";
+    if (bad & kBadLabel) return kBadLabelText;
     return "extra weights must be finite and not negative";
 }
 
@@ -375,7 +380,7 @@ int sc_graph_distances(int64_t N, const int64_t *offsets, int row_len, const int
             if (M) UNIT_TRY(hipMemcpyAsync(w + at.extra_w, extra_w, (size_t)M * 8, hipMemcpyHostToDevice, stream));
         } else {  // device arrays: the first kernel is the judge
             UNIT_TRY(hipMemsetAsync(flag, 0, 64, stream));
-            hipLaunchKernelGGL(graph_flags_kernel, dim3(grid_for(std::max(std::max(E, M), N + 1))), dim3(kB), 0, stream, g, flag);
+            hipLaunchKernelGGL(graph_flags_kernel, dim3(grid_for(std::max(std::max(E, M), N + 1))), dim3(kB), 0, stream, g, nullptr, 0, flag);
             UNIT_TRY(hipGetLastError());
             UNIT_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, stream));
             UNIT_TRY(call.sl.record(stream));
@@ -482,7 +487,7 @@ int sc_graph_components(int64_t N, const int64_t *offsets, int row_len, const in
             if (key) UNIT_TRY(hipMemcpyAsync(w + o_key, key, (size_t)N * 4, hipMemcpyHostToDevice, stream));
         } else {  // device arrays: the first kernel is the judge
             UNIT_TRY(hipMemsetAsync(flag, 0, 64, stream));
-            hipLaunchKernelGGL(graph_flags_kernel, dim3(grid_for(std::max(std::max(E, M), N + 1))), dim3(kB), 0, stream, g, flag);
+            hipLaunchKernelGGL(graph_flags_kernel, dim3(grid_for(std::max(std::max(E, M), N + 1))), dim3(kB), 0, stream, g, nullptr, 0, flag);
             UNIT_TRY(hipGetLastError());
             UNIT_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, stream));
             UNIT_TRY(call.sl.record(stream));
@@ -516,3 +521,5 @@ done:
 void sc_graph_release(void) { release_slots(g_slots); }
 
 }  // extern "C"
+
+#include "graph_quotient.inl"  // sc_graph_quotient

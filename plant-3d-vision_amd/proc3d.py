@@ -55,7 +55,7 @@ def release_device_buffers():
 
 
 def release_graph_buffers():
-    """Give back the device work buffers ``graph_distances`` and ``graph_components`` keep between calls
+    """Give back the device work buffers ``graph_distances``, ``graph_components`` and ``graph_quotient`` keep between calls
     (``sc_graph_release``; they are kept only while they are at most 1 GiB).  It stands beside
     ``release_device_buffers``, whose five entries in ``RELEASES`` stay what they are: call both to give everything back."""
     from . import _native as nat
@@ -723,16 +723,8 @@ def graph_components(rows, key=None, n=None, extra=None, device=0):
     from . import _native as nat, _operands as ops
 
     g = ops.graph_rows(rows, n, extra)
-    kptr = 0
-    if key is not None:
-        if ops.is_tensor(key) != bool(g.on_device):
-            raise ValueError("rows and key must be all arrays or all CUDA tensors")
-        k = ops.ids(key, "key")
-        if k.n != g.n:
-            raise ValueError("one key per node")
-        if k.on_device and k.tdevice != g.tdevice:
-            raise ValueError("rows and key must be on one device")
-        kptr = k.ptr
+    k = None if key is None else ops.node_ids(g, key, "key")
+    kptr = 0 if k is None else k.ptr
     count = np.zeros(1, dtype=np.int32)
     if g.on_device:
         import torch
@@ -787,20 +779,93 @@ def _host(a):
     return a.cpu().numpy() if ops.is_tensor(a) else np.asarray(a)
 
 
-def distance_to_root_clusters(points, rows, root_index, bin_size, extra=None, device=0):
+QUOTIENT_FIRST_EDGES = 4096  # places for cluster edges in graph_quotient's first ask; a second ask follows when there are more
+
+
+def graph_quotient(rows, labels, n_labels, points=None, key=None, extra=None, weights=False, device=0):
+    """The quotient of the graph the rows span under a labelling, on the GPU (``sc_graph_quotient``,
+    ``csrc/graph_quotient.inl``): the clusters renumbered, their member counts and centres, and the edges
+    of ``nx.quotient_graph`` with their weights -- everything :func:`distance_to_root_clusters` does behind its
+    components.
+
+    rows, extra : as for :func:`graph_distances`.
+    labels : int32 ``[N]`` of the rows' kind, each below ``n_labels``; a negative label puts the node outside.
+    key : ``None`` or int32 ``[N]``; points : ``None`` or float64 ``[N, 3]``; both of the rows' kind.
+    weights : also sum the edge weights (the rows' values are then judged as :func:`graph_distances` judges them).
+
+    Returns ``(cluster int32 [N], counts int32 [C], centers float64 [C, 3] | None, edges int32 [K, 2], edge_weights
+    float64 [K] | None)``, NumPy arrays for arrays and CUDA tensors for tensors, by the rules Q1..Q4 of
+    ``include/spacecarve.h``: labels with members are ranked by ``(least key of the members, smallest member)``;
+    ``centers[c]`` is ``np.bincount(cluster, weights=coordinate) / count`` bit for bit; ``edges`` are the sorted pairs
+    ``(a < b)`` of clusters joined by an arc; an edge's weight is the sum, in rising ``(i, j)``, over the undirected node
+    pairs ``{i < j}`` that join the two clusters of the least weight of the pair's arcs -- ``nx.quotient_graph``'s
+    ``weight`` up to summation order.  The first ask has room for ``QUOTIENT_FIRST_EDGES`` edges; when there are more the
+    function asks a second time (rule Q5).  No nodes: empty results, no native call.  There is no CPU fallback."""
+    from . import _native as nat, _operands as ops
+
+    g = ops.graph_rows(rows, None, extra)
+    lab = ops.node_ids(g, labels, "labels")
+    n_labels = int(n_labels)
+    if not 0 <= n_labels <= g.n:
+        raise ValueError(f"n_labels must be 0 .. {g.n}, the node count")
+    k = None if key is None else ops.node_ids(g, key, "key")
+    pts = None
+    if points is not None:
+        if ops.is_tensor(points) != bool(g.on_device):
+            raise ValueError("rows and points must be all arrays or all CUDA tensors")
+        pts = ops.points(points, "points")
+        if pts.n != g.n:
+            raise ValueError("one point per node")
+        if pts.on_device and pts.points.device != g.tdevice:
+            raise ValueError("rows and points must be on one device")
+    want_w = bool(weights)
+    if g.on_device:
+        import torch
+
+        def empty(shape, dtype):
+            return torch.empty(shape, dtype=getattr(torch, dtype), device=g.tdevice)
+    else:
+        def empty(shape, dtype):
+            return np.empty(shape, dtype=dtype)
+    cluster, counts = empty((g.n,), "int32"), empty((n_labels,), "int32")
+    centers = None if pts is None else empty((n_labels, 3), "float64")
+    nclusters, nedges = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64)
+    edges, edge_w = empty((0, 2), "int32"), empty((0,), "float64") if want_w else None
+    if g.n:
+        dev, stream = _graph_place(g, device)
+        capacity = max(0, int(QUOTIENT_FIRST_EDGES))
+        for _ in range(2):
+            edges, edge_w = empty((capacity, 2), "int32"), empty((capacity,), "float64") if want_w else None
+            _graph_call("sc_graph_quotient", g.n, g.offsets, g.row_len, g.index, g.values if want_w else 0, g.E, 1, g.extra,
+                        g.extra_w if want_w else 0, g.M, lab.ptr, n_labels, 0 if k is None else k.ptr, 0 if pts is None else pts.ptr,
+                        g.on_device, int(dev), ops.ptr_of(cluster), ops.ptr_of(counts) if n_labels else 0,
+                        0 if centers is None or not n_labels else ops.ptr_of(centers), ops.ptr_of(edges) if capacity else 0,
+                        ops.ptr_of(edge_w) if want_w and capacity else 0, capacity, nat.addr(nclusters), nat.addr(nedges), int(stream))
+            if int(nedges[0]) <= capacity:
+                break
+            capacity = int(nedges[0])
+    c, e = int(nclusters[0]), int(nedges[0])
+    return cluster, counts[:c], None if centers is None else centers[:c], edges[:e], edge_w[:e] if want_w else None
+
+
+def distance_to_root_clusters(points, rows, root_index, bin_size, extra=None, device=0, weights=False):
     """The clusters of the reference's ``distance_to_root_clusters`` (``proc3d.py:266-329``) as arrays: the nodes are cut
     into bins of their distance to the root, a cluster is a connected component of one bin, and two clusters are joined
-    where an arc joins their nodes.  The distances and the components are computed on the GPU (:func:`graph_distances`,
-    :func:`graph_components` with the bins as keys); the bins are NumPy expressions (torch's for tensors), the
-    renumbering, the centres and the cluster edges host NumPy.
+    where an arc joins their nodes.  Everything but the bins is computed on the GPU: the distances
+    (:func:`graph_distances`), the components (:func:`graph_components` with the bins as keys) and, in one call, the
+    renumbering, the centres and the cluster edges (:func:`graph_quotient`); the bins are NumPy expressions (torch's for
+    tensors).  With tensors nothing of the size of the nodes or the arcs crosses the bus: host points are uploaded once,
+    device points are read in place.
 
-    Returns ``(cluster, centers float64 [C, 3], cluster_edges int32 [K, 2], distances)``; ``cluster`` (int32 ``[N]``) and
-    ``distances`` (float64 ``[N]``) are NumPy arrays or CUDA tensors as the rows are:
+    Returns ``(cluster, centers float64 [C, 3], cluster_edges int32 [K, 2], distances)``, with ``weights=True`` also
+    ``edge_weights float64 [K]``; ``cluster`` (int32 ``[N]``) and ``distances`` (float64 ``[N]``) are NumPy arrays or CUDA
+    tensors as the rows are, the others NumPy arrays:
       * ``n_bins = max(1, ceil(max finite d / bin_size))``, ``bin = min(floor(d / bin_size), n_bins - 1)``, ``-1`` for
         unreached nodes;
       * clusters are numbered by ``(bin, smallest member)``; unreached nodes have cluster ``-1``;
       * ``centers[c]`` is ``np.bincount(cluster, weights=coordinate) / count``;
-      * ``cluster_edges`` are the unique pairs ``(a < b)`` of distinct clusters joined by an arc, sorted.
+      * ``cluster_edges`` are the unique pairs ``(a < b)`` of distinct clusters joined by an arc, sorted;
+      * ``edge_weights[e]`` is the ``weight`` ``nx.quotient_graph`` gives the edge, up to summation order (rule Q4).
 
     Deviations: the reference function cannot be executed -- ``n = c[0]`` on a set raises ``TypeError`` on
     the first component (``proc3d.py:320``); its ``bisect`` cut is shifted by one sorted place (the first node of a bin
@@ -808,7 +873,6 @@ def distance_to_root_clusters(points, rows, root_index, bin_size, extra=None, de
     from . import _operands as ops
 
     pts = ops.points(points, "points")
-    xyz = _host(pts.points)
     g = ops.graph_rows(rows, pts.n, extra)
     bin_size = float(bin_size)
     if not (bin_size > 0.0 and bin_size != float("inf")):
@@ -820,47 +884,22 @@ def distance_to_root_clusters(points, rows, root_index, bin_size, extra=None, de
         n_bins = max(1, int(torch.ceil(d[finite].max() / bin_size).item())) if g.n else 1
         bins = torch.clamp(torch.floor(torch.where(finite, d, torch.zeros_like(d)) / bin_size), max=n_bins - 1).to(torch.int32)
         bins = torch.where(finite, bins, torch.full_like(bins, -1)).contiguous()
+        xyz = pts.points if pts.on_device else torch.from_numpy(pts.points).to(g.tdevice)
     else:
         finite = np.isfinite(d)
         n_bins = max(1, int(np.ceil(d[finite].max() / bin_size))) if g.n else 1
         bins = np.minimum(np.floor(np.where(finite, d, 0.0) / bin_size), n_bins - 1).astype(np.int32)
         bins = np.where(finite, bins, np.int32(-1)).astype(np.int32)
+        xyz = _host(pts.points)
     labels, count = graph_components(rows, key=bins, extra=extra, device=device)
-
-    # the host tail: components by (bin, smallest member), centres, the quotient's edges
-    lab, hbins = _host(labels).astype(np.int64), _host(bins)
-    used = lab >= 0
-    _, first = np.unique(lab[used], return_index=True)  # labels rise with the smallest member: first[c] finds it
-    smallest = np.flatnonzero(used)[first]
-    order = np.lexsort((smallest, hbins[smallest]))
-    renumber = np.empty(count, dtype=np.int64)
-    renumber[order] = np.arange(count)
-    cluster = np.where(used, renumber[np.where(used, lab, 0)] if count else -1, -1).astype(np.int32)
-    counts = np.bincount(cluster[used], minlength=count).astype(np.float64)
-    centers = np.stack([np.bincount(cluster[used], weights=xyz[used, c], minlength=count) / counts for c in range(3)], axis=1).reshape(-1, 3)
-    index = _host(g.arcs).reshape(-1).astype(np.int64)
-    if g.row_len:
-        src = np.repeat(np.arange(g.n, dtype=np.int64), g.row_len)
-    else:
-        src = np.repeat(np.arange(g.n, dtype=np.int64), np.diff(_host(g.offsets_data)))
-    keep = index >= 0
-    src, dst = src[keep], index[keep]
-    if g.M:
-        more = _host(g.extra_data).astype(np.int64)
-        src, dst = np.concatenate([src, more[:, 0]]), np.concatenate([dst, more[:, 1]])
-    ca, cb = cluster[src].astype(np.int64), cluster[dst].astype(np.int64)
-    cross = (ca >= 0) & (cb >= 0) & (ca != cb)
-    lo, hi = np.minimum(ca[cross], cb[cross]), np.maximum(ca[cross], cb[cross])
-    pairs = np.unique(lo * max(count, 1) + hi)
-    cluster_edges = np.stack([pairs // max(count, 1), pairs % max(count, 1)], axis=1).astype(np.int32).reshape(-1, 2)
-    if g.on_device:
-        import torch
-        cluster = torch.from_numpy(cluster).to(g.tdevice)
-    return cluster, centers, cluster_edges, d
+    cluster, _, centers, cluster_edges, edge_w = graph_quotient(rows, labels, count, points=xyz, key=bins, extra=extra, weights=weights,
+                                                                device=device)
+    out = (cluster, _host(centers), _host(cluster_edges), d)
+    return out + (_host(edge_w),) if weights else out
 
 
-def skeleton_from_distance_to_root_clusters(pcd, root_index, binsize, k, connect_all_points=True, device=0):
-    """The XU method (``proc3d.py:392-426``; same signature, ``device`` added): the k-nearest-neighbour graph of the cloud
+def skeleton_from_distance_to_root_clusters(pcd, root_index, binsize, k, connect_all_points=True, device=0, weighted=False):
+    """The XU method (``proc3d.py:392-426``; same signature, ``device`` and ``weighted`` added): the k-nearest-neighbour graph of the cloud
     (:func:`knn_points`), connected when ``connect_all_points`` (:func:`graph_components`, :func:`connect_edges`), its
     nodes clustered by distance to ``root_index`` (:func:`distance_to_root_clusters`), and the minimum spanning tree of
     the cluster graph.
@@ -869,9 +908,13 @@ def skeleton_from_distance_to_root_clusters(pcd, root_index, binsize, k, connect
     ``0..C-1`` carry ``center`` and whose edges are the cluster edges in sorted order; ``cluster_values`` is the dict
     ``{node: cluster}``, unreached nodes absent as in the reference.  Raises ``ImportError`` without networkx.
 
-    Deviation: the reference's ``quotient_graph`` weights a cluster edge with the sum of the arc weights between the two
-    clusters, added in set-iteration order; ours carry no weight (every edge counts 1), so the tree is Kruskal's over
-    the sorted pairs.  The deviations of :func:`distance_to_root_clusters` and :func:`connect_edges` hold here too."""
+    weighted : give every cluster edge its ``weight``, the sum of the weights of the node edges between the two clusters
+        (:func:`graph_quotient`, rule Q4), before ``nx.minimum_spanning_tree``: the reference's tree.
+
+    Deviation, for the default only: the reference's ``quotient_graph`` weights a cluster edge with the sum of the edge
+    weights between the two clusters, added in set-iteration order; without ``weighted`` ours carry no weight (every edge
+    counts 1), so the tree is Kruskal's over the sorted pairs.  With ``weighted`` the weights are the reference's up to
+    summation order.  The deviations of :func:`distance_to_root_clusters` and :func:`connect_edges` hold here too."""
     try:
         import networkx as nx
     except ImportError as e:
@@ -888,9 +931,13 @@ def skeleton_from_distance_to_root_clusters(pcd, root_index, binsize, k, connect
         labels, count = graph_components(rows, device=device)
         if count > 1:
             extra = connect_edges(pts.points, labels, root_index, device=device)
-    cluster, centers, cluster_edges, _ = distance_to_root_clusters(pts.points, rows, root_index, binsize, extra=extra, device=device)
+    got = distance_to_root_clusters(pts.points, rows, root_index, binsize, extra=extra, device=device, weights=bool(weighted))
+    cluster, centers, cluster_edges, edge_w = got[0], got[1], got[2], got[4] if weighted else None
     g = nx.Graph()
     for c in range(len(centers)):
         g.add_node(c, center=centers[c])
-    g.add_edges_from((int(a), int(b)) for a, b in cluster_edges.tolist())
+    if weighted:
+        g.add_weighted_edges_from((int(a), int(b), float(w)) for (a, b), w in zip(cluster_edges.tolist(), edge_w.tolist()))
+    else:
+        g.add_edges_from((int(a), int(b)) for a, b in cluster_edges.tolist())
     return nx.minimum_spanning_tree(g), {int(v): int(c) for v, c in enumerate(cluster.tolist()) if c >= 0}

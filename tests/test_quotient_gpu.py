@@ -1,0 +1,217 @@
+"""GPU: ``proc3d.graph_quotient`` (``sc_graph_quotient``, csrc/graph_quotient.inl) and the weighted forms of
+``distance_to_root_clusters`` / ``skeleton_from_distance_to_root_clusters`` against the checker
+(tests/quotient_oracle.py, which tests/test_quotient_host.py holds against networkx).  Every comparison is bit for bit,
+from arrays and from tensors."""
+import numpy as np
+import pytest
+
+from plant3dvision_amd import _native as nat
+from plant3dvision_amd import proc3d
+from tests import quotient_oracle as oracle
+
+pytestmark = pytest.mark.gpu
+
+
+def on_device(a):
+    import torch
+    if a is None:
+        return None
+    if isinstance(a, tuple):
+        return tuple(on_device(x) for x in a)
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else a
+
+
+def check(rows, labels, n_labels, points=None, key=None, extra=None):
+    """One quotient, with and without weights, from arrays and from tensors, against the checker; returns the checker's."""
+    labels = np.asarray(labels, dtype=np.int32)
+    key = None if key is None else np.asarray(key, dtype=np.int32)
+    want = oracle.quotient(rows, labels, n_labels, points=points, key=key, extra=extra, weights=True)
+    for form in (lambda x: x, on_device):
+        for weights in (True, False):
+            got = proc3d.graph_quotient(form(rows), form(labels), n_labels, points=form(points), key=form(key), extra=form(extra),
+                                        weights=weights)
+            assert all((type(a) is np.ndarray) == (form is not on_device) for a in got if a is not None)
+            names = ("cluster", "counts", "centers", "edges", "edge weights")
+            for name, a, b in zip(names, got, want):
+                if b is None or (name == "edge weights" and not weights):
+                    assert a is None, name
+                else:
+                    assert oracle.same_bits(host(a), b), name
+    return want
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 257, 1025])
+def test_sizes(gpu_device, n):
+    rng = np.random.default_rng(100 + n)
+    pts = rng.uniform(0.0, 1.0, size=(n, 3))
+    slab = (pts[:, 0] * 3).astype(np.int32)
+    slab[rng.random(n) < 0.1] = -1  # outside nodes
+    key = (rng.integers(-5, 5, size=n)).astype(np.int32)  # negative entries: the least key is a signed one
+    seen = 0
+    for rows in (proc3d.knn_points(pts, pts, 2), proc3d.knn_points(pts, pts, 5), proc3d.radius_points(pts, pts, 1.2 * (1.0 / n) ** (1.0 / 3.0))):
+        labels, count = proc3d.graph_components(rows, key=slab)
+        cluster, counts, _, edges, _ = check(rows, labels, count, points=pts, key=key)
+        assert len(counts) == count and np.array_equal(cluster < 0, slab < 0)
+        seen += len(edges)
+        check(rows, labels, count)  # no key: G3's numbering stays
+    assert n < 63 or seen > 0
+
+
+@pytest.mark.parametrize("with_key", [False, True])
+def test_labels_in_any_order_with_empty_ones(gpu_device, with_key):
+    rng = np.random.default_rng(31)
+    n, n_labels = 300, 40
+    pts = rng.uniform(0.0, 1.0, size=(n, 3))
+    rows = proc3d.knn_points(pts, pts, 6)
+    names = rng.permutation(n_labels)[:25]  # 15 labels stay empty
+    labels = names[rng.integers(0, 25, size=n)].astype(np.int32)
+    labels[rng.random(n) < 0.1] = -1
+    labels[0] = -3
+    key = rng.integers(-2 ** 31, 2 ** 31, size=n).astype(np.int32) if with_key else None
+    cluster, counts, centers, edges, _ = check(rows, labels, n_labels, points=pts, key=key)
+    assert len(counts) <= 25 < n_labels and len(edges) > len(counts)
+    firsts = [int(np.flatnonzero(cluster == c)[0]) for c in range(len(counts))]
+    assert (firsts == sorted(firsts)) == (not with_key)
+
+
+def test_one_cluster_and_capped_grids(gpu_device):
+    rng = np.random.default_rng(32)
+    pts = rng.normal(size=(1025, 3)) * 1e3
+    rows = proc3d.knn_points(pts, pts, 4)
+    zeros = np.zeros(1025, dtype=np.int32)
+    cluster, counts, centers, edges, _ = check(rows, zeros, 1, points=pts)
+    assert counts.tolist() == [1025] and len(edges) == 0
+    assert np.array_equal(centers[0], [np.bincount(zeros, weights=pts[:, a])[0] / 1025.0 for a in range(3)])
+    nat.backend().call("sc_graph_set_blocks", 1)  # one block: every grid-stride loop goes past its first trip
+    try:
+        check(rows, zeros, 3, points=pts)
+        blob = np.random.default_rng(33).uniform(0.0, 1.0, size=(700, 3))
+        labels = (np.arange(700) % 9 - 1).astype(np.int32)
+        check(proc3d.knn_points(blob, blob, 6), labels, 8, points=blob, key=(np.arange(700) % 5 - 2).astype(np.int32))
+        check(proc3d.radius_points(blob, blob, 0.12), labels, 8, points=blob)
+    finally:
+        nat.backend().call("sc_graph_set_blocks", 0)
+
+
+def test_every_node_its_own_cluster_and_the_second_ask(gpu_device, monkeypatch):
+    monkeypatch.setattr(proc3d, "QUOTIENT_FIRST_EDGES", 1)
+    rng = np.random.default_rng(34)
+    pts = rng.uniform(0.0, 1.0, size=(257, 3))
+    rows = proc3d.knn_points(pts, pts, 4)
+    cluster, counts, centers, edges, edge_w = check(rows, np.arange(257, dtype=np.int32), 257, points=pts)
+    assert np.array_equal(cluster, np.arange(257)) and (counts == 1).all() and np.array_equal(centers, pts) and len(edges) > 257
+    want_e, want_w = proc3d.knn_edges(pts, 4)  # the folded node edges themselves, self-loops among them
+    loops = want_e[:, 0] == want_e[:, 1]
+    assert np.array_equal(edges, want_e[~loops]) and np.array_equal(edge_w, want_w[~loops])
+
+
+def test_the_order_of_summation_shows(gpu_device):
+    tiny = 5e-324
+    pts = np.array([[1e16, tiny, 1.0], [1.0, tiny, np.nan], [-1e16, -tiny, 2.0], [-0.0, tiny, 3.0],  # cluster 0: x sums to 0, not 1
+                    [1.0, 1e-310, -0.0], [1e16, 2e-310, -0.0], [-1e16, -3e-310, -0.0],                # cluster 1: x sums to 0 again
+                    [-0.0, -0.0, 1e308], [-0.0, -0.0, 1e308]])                                         # cluster 2: -0 + -0, an overflow
+    labels = np.array([2, 2, 2, 2, 5, 5, 5, 7, 7], dtype=np.int32)
+    rows = (np.array([[1], [2], [3], [4], [5], [6], [7], [8], [0]], dtype=np.int32), np.ones((9, 1)))
+    cluster, counts, centers, edges, edge_w = check(rows, labels, 8, points=pts)
+    assert counts.tolist() == [4, 3, 2] and edges.tolist() == [[0, 1], [0, 2], [1, 2]] and edge_w.tolist() == [1.0, 1.0, 1.0]
+    assert centers[0, 0] == 0.0 and np.isnan(centers[0, 2]) and centers[1, 0] == 0.0 and np.isinf(centers[2, 2])
+    assert centers[0, 1] == 0.0 and not np.signbit(centers[2, 0])  # 2 tiny / 4 rounds to zero; the sum starts at +0.0
+
+
+def test_hand_made_rows(gpu_device):
+    inf = np.inf
+    # arcs given one way only (0 -> 2, 3 -> 1), the two directions of 1 - 2 with weights 3 and 2 (d2 9 and 4), a self-arc, -1 places
+    index = np.array([[2, -1, 0], [2, -1, -1], [1, -1, -1], [1, 3, -1], [-1, -1, -1]], dtype=np.int32)
+    d2 = np.array([[16.0, inf, 0.0], [9.0, inf, inf], [4.0, inf, inf], [25.0, 0.0, inf], [inf, inf, inf]])
+    labels = np.array([0, 0, 1, 1, 2], dtype=np.int32)
+    cluster, counts, _, edges, edge_w = check((index, d2), labels, 3)
+    assert counts.tolist() == [2, 2, 1] and edges.tolist() == [[0, 1]] and edge_w.tolist() == [(4.0 + 2.0) + 5.0]
+    # extra pairs create the edges to cluster 2; a repeated extra pair with a smaller weight wins; an extra self-pair counts nothing
+    extra = (np.array([[4, 0], [3, 4], [4, 3], [4, 4], [2, 1]], dtype=np.int32), np.array([0.5, 7.0, 6.0, 1.0, 1.5]))
+    _, _, _, edges, edge_w = check((index, d2), labels, 3, extra=extra)
+    assert edges.tolist() == [[0, 1], [0, 2], [1, 2]] and edge_w.tolist() == [(4.0 + 1.5) + 5.0, 0.5, 6.0]
+    # the same arcs as CSR rows; labels 2 and 0 swap places under a key
+    offsets = np.array([0, 2, 3, 4, 6, 6], dtype=np.int64)
+    flat_i, flat_d = np.array([2, 0, 2, 1, 1, 3], dtype=np.int32), np.array([16.0, 0.0, 9.0, 4.0, 25.0, 0.0])
+    cluster, _, _, edges, edge_w = check((offsets, flat_i, flat_d), labels, 3, key=[5, 5, 0, 0, -1], extra=extra)
+    assert cluster.tolist() == [2, 2, 1, 1, 0] and edges.tolist() == [[0, 1], [0, 2], [1, 2]] and edge_w.tolist() == [6.0, 0.5, (4.0 + 1.5) + 5.0]
+    # plain weights (weights_squared off) go through the library directly: the same rows with d2 read as distances
+    b = nat.backend()
+    out_c, out_n = np.zeros(5, np.int32), np.zeros(3, np.int32)
+    out_e, out_w = np.zeros((4, 2), np.int32), np.zeros(4)
+    nc, ne = np.zeros(1, np.int32), np.zeros(1, np.int64)
+    for squared, want in ((1, (4.0 + 2.0) + 5.0), (0, (16.0 + 4.0) + 25.0)):
+        rc = b.call("sc_graph_quotient", 5, 0, 3, nat.addr(index), nat.addr(d2), 15, squared, 0, 0, 0, nat.addr(labels), 3, 0, 0, 0, 0,
+                    nat.addr(out_c), nat.addr(out_n), 0, nat.addr(out_e), nat.addr(out_w), 4, nat.addr(nc), nat.addr(ne), 0)
+        assert rc == nat.SC_OK and (nc[0], ne[0]) == (3, 1) and out_e[0].tolist() == [0, 1] and out_w[0] == want
+    # rule Q5: too little room reports K and leaves the rows alone
+    out_e[:], out_w[:] = -7, -7.0
+    rows5 = (np.array([[1], [2], [3], [0]], dtype=np.int32), np.ones((4, 1)))
+    lab5, out_n4 = np.arange(4, dtype=np.int32), np.zeros(4, np.int32)
+    rc = b.call("sc_graph_quotient", 4, 0, 1, nat.addr(rows5[0]), nat.addr(rows5[1]), 4, 1, 0, 0, 0, nat.addr(lab5), 4, 0, 0, 0, 0,
+                nat.addr(out_c), nat.addr(out_n4), 0, nat.addr(out_e), nat.addr(out_w), 3, nat.addr(nc), nat.addr(ne), 0)
+    assert rc == nat.SC_OK and (nc[0], ne[0]) == (4, 4) and (out_e == -7).all() and (out_w == -7.0).all()
+
+
+def test_a_label_too_large_and_the_call_after(gpu_device):
+    rows = (np.array([[1], [2], [0]], dtype=np.int32), np.ones((3, 1)))
+    for form in (lambda x: x, on_device):
+        for bad in ([0, 2, 1], [5, 0, 0]):
+            with pytest.raises(ValueError, match="label outside"):
+                proc3d.graph_quotient(form(rows), form(np.array(bad, dtype=np.int32)), 2)
+            cluster, counts, _, edges, _ = proc3d.graph_quotient(form(rows), form(np.array([1, -1, 0], dtype=np.int32)), 2)
+            assert host(cluster).tolist() == [0, -1, 1] and host(counts).tolist() == [1, 1] and host(edges).tolist() == [[0, 1]]
+        with pytest.raises(ValueError, match="weights must be finite"):  # judged with weights only
+            proc3d.graph_quotient(form((rows[0], np.array([[1.0], [np.nan], [1.0]]))), form(np.array([0, 1, 1], dtype=np.int32)), 2, weights=True)
+        got = proc3d.graph_quotient(form((rows[0], np.array([[1.0], [np.nan], [1.0]]))), form(np.array([0, 1, 1], dtype=np.int32)), 2)
+        assert host(got[3]).tolist() == [[0, 1]]
+
+
+def _blobs():
+    rng = np.random.default_rng(8)
+    centres = np.array([[0, 0, 0], [6, 0, 0], [0, 7, 0], [5, 5, 5], [-6, 1, 2]], dtype=np.float64)
+    return np.concatenate([c + rng.uniform(-1.0, 1.0, size=(40, 3)) for c in centres])
+
+
+@pytest.mark.parametrize("connect", [True, False])
+def test_weighted_clusters_and_the_reference_tree(gpu_device, connect):
+    import networkx as nx
+    pts = _blobs()
+    k, root, bin_size = 5, 7, 0.8
+    rows = proc3d.knn_points(pts, pts, k)
+    extra = None
+    if connect:
+        labels, _ = proc3d.graph_components(rows)
+        extra = proc3d.connect_edges(pts, labels, root)
+    plain = proc3d.distance_to_root_clusters(pts, rows, root, bin_size, extra=extra)
+    for form in (lambda x: x, on_device):
+        got = proc3d.distance_to_root_clusters(pts, form(rows), root, bin_size, extra=form(extra), weights=True)
+        assert len(got) == 5 and all(oracle.same_bits(host(a), b) for a, b in zip(got, plain))
+        assert type(got[1]) is np.ndarray and type(got[2]) is np.ndarray and type(got[4]) is np.ndarray
+    cluster, centers, cluster_edges, d, edge_w = got[0].cpu().numpy(), got[1], got[2], got[3], got[4]
+    if connect:
+        assert len(centers) == 46 and len(cluster_edges) == 64
+    g = nx.Graph()
+    g.add_nodes_from(range(len(pts)))
+    for i, j, w in oracle.arcs_of(rows, extra)[1]:
+        g.add_edge(i, j, weight=w)
+    sets = [frozenset(np.flatnonzero(cluster == c).tolist()) for c in range(len(centers))]
+    q = nx.quotient_graph(g.subgraph(np.flatnonzero(cluster >= 0).tolist()), sets, relabel=True)
+    assert sorted((min(a, b), max(a, b)) for a, b in q.edges()) == [tuple(e) for e in cluster_edges.tolist()]
+    terms = oracle.pairs_per_edge(rows, cluster, extra)
+    for (a, b), w in zip(cluster_edges.tolist(), edge_w.tolist()):
+        assert abs(w - q[a][b]["weight"]) <= 2 * terms[(a, b)] * 2.0 ** -53 * q[a][b]["weight"]
+    want = sorted((min(a, b), max(a, b)) for a, b in nx.minimum_spanning_tree(q).edges())
+    cloud = proc3d.PointCloud(pts, None)
+    tree, values = proc3d.skeleton_from_distance_to_root_clusters(cloud, root, bin_size, k, connect_all_points=connect, weighted=True)
+    assert nx.is_tree(tree) and sorted(tree.nodes) == list(range(len(centers)))
+    assert sorted((min(a, b), max(a, b)) for a, b in tree.edges()) == want
+    assert values == {v: int(c) for v, c in enumerate(cluster.tolist()) if c >= 0}
+    assert all(np.array_equal(tree.nodes[c]["center"], centers[c]) for c in tree.nodes)
+    assert all(tree[a][b]["weight"] == w for (a, b), w in zip(cluster_edges.tolist(), edge_w.tolist()) if tree.has_edge(a, b))
+    default, _ = proc3d.skeleton_from_distance_to_root_clusters(cloud, root, bin_size, k, connect_all_points=connect)
+    assert nx.is_tree(default) and all("weight" not in default[a][b] for a, b in default.edges())
