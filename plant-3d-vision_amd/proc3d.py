@@ -1,6 +1,8 @@
 """Voxel <-> world convention of the reference (``plant3dvision/proc3d.py:28-65``), pinned
 by its ``tests/unit/test_proc3d.py:12-30``: voxel centres sit at ``origin + index *
 voxel_size`` -- the same rule the kernels use (``kernels/backprojection.c:71-73``)."""
+import math
+
 import numpy as np
 
 
@@ -848,6 +850,14 @@ def graph_quotient(rows, labels, n_labels, points=None, key=None, extra=None, we
     return cluster, counts[:c], None if centers is None else centers[:c], edges[:e], edge_w[:e] if want_w else None
 
 
+def _bin_count(largest, bin_size):
+    """``max(1, ceil(largest / bin_size))`` of the float64 quotient, refused where the bins, int32 keys, could not hold it."""
+    top = float(largest) / bin_size  # an overflow gives inf
+    if not math.isfinite(top) or math.ceil(top) - 1 > 2 ** 31 - 1:
+        raise ValueError(f"bin_size {bin_size!r} is too small for distances up to {float(largest)!r}: the last bin's number must fit int32")
+    return max(1, math.ceil(top))
+
+
 def distance_to_root_clusters(points, rows, root_index, bin_size, extra=None, device=0, weights=False):
     """The clusters of the reference's ``distance_to_root_clusters`` (``proc3d.py:266-329``) as arrays: the nodes are cut
     into bins of their distance to the root, a cluster is a connected component of one bin, and two clusters are joined
@@ -861,7 +871,8 @@ def distance_to_root_clusters(points, rows, root_index, bin_size, extra=None, de
     ``edge_weights float64 [K]``; ``cluster`` (int32 ``[N]``) and ``distances`` (float64 ``[N]``) are NumPy arrays or CUDA
     tensors as the rows are, the others NumPy arrays:
       * ``n_bins = max(1, ceil(max finite d / bin_size))``, ``bin = min(floor(d / bin_size), n_bins - 1)``, ``-1`` for
-        unreached nodes;
+        unreached nodes; a ``bin_size`` so small that the quotient overflows or ``n_bins - 1`` does not fit int32 raises
+        ``ValueError``;
       * clusters are numbered by ``(bin, smallest member)``; unreached nodes have cluster ``-1``;
       * ``centers[c]`` is ``np.bincount(cluster, weights=coordinate) / count``;
       * ``cluster_edges`` are the unique pairs ``(a < b)`` of distinct clusters joined by an arc, sorted;
@@ -881,13 +892,13 @@ def distance_to_root_clusters(points, rows, root_index, bin_size, extra=None, de
     if g.on_device:
         import torch
         finite = torch.isfinite(d)
-        n_bins = max(1, int(torch.ceil(d[finite].max() / bin_size).item())) if g.n else 1
+        n_bins = _bin_count(d[finite].max().item(), bin_size) if g.n else 1
         bins = torch.clamp(torch.floor(torch.where(finite, d, torch.zeros_like(d)) / bin_size), max=n_bins - 1).to(torch.int32)
         bins = torch.where(finite, bins, torch.full_like(bins, -1)).contiguous()
         xyz = pts.points if pts.on_device else torch.from_numpy(pts.points).to(g.tdevice)
     else:
         finite = np.isfinite(d)
-        n_bins = max(1, int(np.ceil(d[finite].max() / bin_size))) if g.n else 1
+        n_bins = _bin_count(d[finite].max(), bin_size) if g.n else 1
         bins = np.minimum(np.floor(np.where(finite, d, 0.0) / bin_size), n_bins - 1).astype(np.int32)
         bins = np.where(finite, bins, np.int32(-1)).astype(np.int32)
         xyz = _host(pts.points)

@@ -169,6 +169,35 @@ def knn_rows(points, k):
     return index, out
 
 
+SCATTER_RADIUS = 0.055  # about 0.7 neighbours a point among 1025 uniform ones: half the stripped rows are empty
+
+
+def scattered_cloud():
+    """1025 uniform points, the first and the last two moved far from all others: with ``SCATTER_RADIUS`` their rows hold
+    themselves alone."""
+    pts = np.random.default_rng(77).uniform(0.0, 1.0, size=(1025, 3))
+    pts[[0, 1023, 1024]] += np.array([[50.0, 0.0, 0.0], [0.0, 60.0, 0.0], [0.0, 0.0, 70.0]])
+    return pts
+
+
+def strip_self_arcs(rows):
+    """CSR rows without the places ``index == row``, and the properties the tests of empty rows stand on, asserted from
+    the stripped rows themselves: a third of the rows at least is empty, a third is not, row 0 and the last two are
+    empty, and somewhere three empty rows follow one another."""
+    offsets, index, d2 = (np.asarray(a) for a in rows)
+    n = len(offsets) - 1
+    row = np.repeat(np.arange(n), np.diff(offsets))
+    keep = index != row
+    length = np.bincount(row[keep], minlength=n)
+    out = (np.concatenate([[0], np.cumsum(length)]).astype(np.int64), index[keep].astype(np.int32), d2[keep].astype(np.float64))
+    empty = np.diff(out[0]) == 0
+    assert 3 * empty.sum() >= n and 3 * (~empty).sum() >= n
+    assert empty[0] and empty[n - 2] and empty[n - 1]
+    assert (empty[:-2] & empty[1:-1] & empty[2:]).any()
+    assert keep.sum() == len(out[1]) > 0 and not (out[1] == np.repeat(np.arange(n), np.diff(out[0]))).any()
+    return out
+
+
 def radius_rows(points, r):
     points = np.asarray(points, dtype=np.float64)
     n = len(points)

@@ -94,6 +94,204 @@ def test_rounds_past_the_first_wait_and_capped_grids(gpu_device):
         nat.backend().call("sc_graph_set_blocks", 0)
 
 
+W = nat.SC_GRAPH_ROUNDS_PER_WAIT
+
+
+def _chain(n, d2):
+    """Rows of length 1: node i points at i + 1, the last place is unused."""
+    index = np.arange(1, n + 1, dtype=np.int32).reshape(n, 1)
+    index[-1, 0] = -1
+    return index, np.asarray(d2, dtype=np.float64).reshape(n, 1)
+
+
+@pytest.mark.parametrize("n", [W - 1, W, W + 1, 2 * W, 2 * W + 1])
+def test_chains_end_on_either_side_of_a_wait(gpu_device, n):
+    """A chain's frontier is the nodes one hop further: the number of rounds is exact, and the last live round falls
+    on, before and behind the round after which the host looks at the header."""
+    rows = _chain(n, np.random.default_rng(n).uniform(1.0, 4.0, size=n))
+    for root in (0, n - 1, n // 3):  # from the far end every arc is used backwards
+        want = oracle.distances(rows, root)
+        assert np.isfinite(want).all()
+        for form in (lambda x: x, on_device):
+            d, rounds = proc3d.graph_distances(form(rows), root, return_rounds=True)
+            assert rounds == max(root, n - 1 - root) + 1, (root, rounds)
+            assert np.array_equal(host(d), want)
+    check_graph(rows, n // 3)
+
+
+def _fan(extra_weight):
+    """A chain of unit arcs and extra pairs from node 0 to every node from 2 on."""
+    n = 2 * W + 3
+    far = np.arange(2, n, dtype=np.int32)
+    extra = (np.stack([np.zeros_like(far), far], axis=1), np.array([extra_weight(v) for v in far.tolist()], dtype=np.float64))
+    return n, _chain(n, np.ones(n)), extra
+
+
+def test_nodes_that_fall_again_and_again(gpu_device):
+    """Round 0 lowers node v to 2 v through its extra pair; the chain then lowers it again, in the end to v: nodes re-enter
+    the frontier many times (the stamps).  Inside a round a node may be read after it fell, so the count is not fixed."""
+    n, rows, extra = _fan(lambda v: 2.0 * v)
+    for blocks in (0, 1):
+        nat.backend().call("sc_graph_set_blocks", blocks)
+        try:
+            d, _, count = check_graph(rows, 0, extra=extra)  # 1 <= rounds <= n is asserted there
+        finally:
+            nat.backend().call("sc_graph_set_blocks", 0)
+        assert d.tolist() == [float(v) for v in range(n)] and count == 1
+
+
+def test_ties_lower_nothing(gpu_device):
+    """The extra pairs weigh what the chain's walk does: round 0 reaches every node, round 1 finds only equal sums and
+    lowers nothing (rule G2 asks for less, not for less or equal), and there is no round 2."""
+    n, rows, extra = _fan(float)
+    d, _, _ = check_graph(rows, 0, extra=extra)
+    assert d.tolist() == [float(v) for v in range(n)]
+    for form in (lambda x: x, on_device):
+        assert proc3d.graph_distances(form(rows), 0, extra=form(extra), return_rounds=True)[1] == 2
+
+
+def test_sums_that_overflow_stay_unreached(gpu_device):
+    rows = (np.full((4, 1), -1, dtype=np.int32), np.full((4, 1), np.inf))
+    extra = (np.array([[0, 1], [1, 2], [2, 3]], dtype=np.int32), np.full(3, 1e308))
+    d, labels, count = check_graph(rows, 0, extra=extra)
+    assert d.tolist() == [0.0, 1e308, np.inf, np.inf] and count == 1
+
+
+# ---- rows without arcs ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def stripped(gpu_device):
+    """The radius rows of the scattered cloud without their self-arcs: runs of empty rows, at both ends too."""
+    pts = oracle.scattered_cloud()
+    return pts, oracle.strip_self_arcs(proc3d.radius_points(pts, pts, oracle.SCATTER_RADIUS))
+
+
+def test_csr_rows_without_self_arcs(gpu_device, stripped):
+    _, rows = stripped
+    busy = int(np.flatnonzero(np.diff(rows[0]) > 0)[0])
+    key = (np.arange(1025) % 3 - 1).astype(np.int32)
+    for blocks in (0, 1):
+        nat.backend().call("sc_graph_set_blocks", blocks)
+        try:
+            for k in (None, key):
+                d, _, count = check_graph(rows, busy, key=k)
+                assert 1 < np.isfinite(d).sum() < 1025
+                d, _, _ = check_graph(rows, 0, key=k)  # the root's own row is empty
+                assert d[0] == 0.0 and np.isinf(d[1:]).all()
+        finally:
+            nat.backend().call("sc_graph_set_blocks", 0)
+
+
+NO_ARCS = {"csr": (np.zeros(66, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0)),
+           "fixed": (np.full((65, 3), -1, dtype=np.int32), np.full((65, 3), np.inf))}
+ONLY_EXTRA = (np.array([[64, 0], [3, 64], [0, 64]], dtype=np.int32), np.array([2.0, 0.25, 1.5]))
+
+
+@pytest.mark.parametrize("form", sorted(NO_ARCS))
+def test_graphs_without_arcs(gpu_device, form):
+    """E == 0 (no index array at all, an empty CUDA tensor) and rows of unused places; then extra pairs as the only arcs."""
+    rows = NO_ARCS[form]
+    for root in (0, 64):
+        d, labels, count = check_graph(rows, root)
+        assert np.isinf(d).sum() == 64 and d[root] == 0.0 and count == 65 and np.array_equal(labels, np.arange(65))
+    d, labels, count = check_graph(rows, 0, extra=ONLY_EXTRA)
+    assert d[64] == 1.5 and d[3] == 1.75 and np.isinf(d).sum() == 62 and count == 63
+    key = (np.arange(65) % 2).astype(np.int32)
+    key[3] = -1
+    d, labels, count = check_graph(rows, 3, extra=ONLY_EXTRA, key=key)
+    assert d[64] == 0.25 and d[0] == 1.75 and count == 63 and labels[3] == -1 and labels[64] == labels[0] == 0
+
+
+# ---- streams and the life of the work buffers ------------------------------------------------------------------------
+def test_streams_refusals_and_work_buffers(gpu_device):
+    """The three entries share one slot of work buffers: calls on two streams, a call that has to grow the buffers behind
+    another's work, a call the device judge refuses in between, ``release_graph_buffers`` and the host-array route."""
+    import torch
+    from tests import quotient_oracle
+    rng = np.random.default_rng(51)
+    sp, lp = rng.uniform(0.0, 1.0, size=(300, 3)), rng.uniform(0.0, 1.0, size=(6000, 3))
+    small, large = proc3d.knn_points(sp, sp, 4), proc3d.knn_points(lp, lp, 8)
+    want = {}
+    for name, rows, pts in (("small", small, sp), ("large", large, lp)):
+        d = oracle.distances(rows, 5)
+        labels, count = oracle.components(rows)
+        slab = (pts[:, 0] * 6).astype(np.int32)
+        q = quotient_oracle.quotient(rows, slab, 6, points=pts, weights=True)
+        assert len(q[1]) == 6 and len(q[3]) >= 5
+        want[name] = (d, labels, count, slab, q)
+    proc3d.release_graph_buffers()  # whatever earlier tests left: the first call allocates
+    dev = {name: (on_device(rows), torch.from_numpy(want[name][3]).cuda(), torch.from_numpy(pts).cuda())
+           for name, rows, pts in (("small", small, sp), ("large", large, lp))}
+    bad_index = small[0].copy()
+    bad_index[299, 3] = 300  # the last place: the judge reads inside the stated lengths only
+    bad = (torch.from_numpy(bad_index).cuda(), dev["small"][0][1])
+
+    def ask(name):
+        rows, slab, pts = dev[name]
+        return (proc3d.graph_distances(rows, 5), proc3d.graph_components(rows), proc3d.graph_quotient(rows, slab, 6, points=pts, weights=True))
+
+    def same(got, name):
+        d, labels, count, _, q = want[name]
+        assert np.array_equal(host(got[0]), d) and np.array_equal(host(got[1][0]), labels) and got[1][1] == count
+        assert all(quotient_oracle.same_bits(host(a), b) for a, b in zip(got[2], q))
+
+    side = torch.cuda.Stream(device=gpu_device)
+    side.wait_stream(torch.cuda.current_stream(gpu_device))  # the uploads
+    r1 = ask("small")
+    with torch.cuda.stream(side):
+        r2 = ask("large")  # a second stream; grows the buffers behind the first call
+    r3 = ask("small")
+    for entry in (lambda: proc3d.graph_distances(bad, 5), lambda: proc3d.graph_components(bad),
+                  lambda: proc3d.graph_quotient(bad, dev["small"][1], 6, points=dev["small"][2], weights=True)):
+        with pytest.raises(ValueError, match="index outside"):
+            entry()
+    r4 = ask("small")
+    side.synchronize()
+    torch.cuda.current_stream(gpu_device).synchronize()
+    for got, name in ((r1, "small"), (r2, "large"), (r3, "small"), (r4, "small")):
+        same(got, name)
+    proc3d.release_graph_buffers()
+    same(ask("small"), "small")  # in fresh buffers
+    for name, rows, pts in (("small", small, sp), ("large", large, lp)):  # the host-array route
+        same((proc3d.graph_distances(rows, 5), proc3d.graph_components(rows),
+              proc3d.graph_quotient(rows, want[name][3], 6, points=pts, weights=True)), name)
+    proc3d.release_graph_buffers()
+    same(ask("large"), "large")
+
+
+def test_bins_at_the_edge_of_int32(gpu_device):
+    """The smallest ``bin_size`` whose last bin still fits int32 is accepted and gives the checker's clusters; the float64
+    just below it is refused, from arrays and from tensors."""
+    import math
+    pts = _blobs()
+    rows = proc3d.knn_points(pts, pts, 5)
+    d = oracle.distances(rows, 7)
+    top = float(d[np.isfinite(d)].max())
+
+    def fits(b):  # the rule, in Python's integers: n_bins - 1 <= 2^31 - 1
+        return math.isfinite(top / b) and math.ceil(top / b) - 1 <= 2 ** 31 - 1
+
+    good = top / 2.0 ** 31
+    for _ in range(8):
+        if fits(good):
+            break
+        good = float(np.nextafter(good, np.inf))
+    for _ in range(8):
+        if not fits(float(np.nextafter(good, 0.0))):
+            break
+        good = float(np.nextafter(good, 0.0))
+    refused = float(np.nextafter(good, 0.0))
+    assert fits(good) and not fits(refused) and math.ceil(top / good) == 2 ** 31
+    want = oracle.clusters(pts, rows, 7, good)
+    assert oracle.bins_of(d, good).max() == 2 ** 31 - 1
+    for form in (lambda x: x, on_device):
+        for weights in (False, True):
+            with pytest.raises(ValueError, match="bin_size"):
+                proc3d.distance_to_root_clusters(pts, form(rows), 7, refused, weights=weights)
+            got = proc3d.distance_to_root_clusters(pts, form(rows), 7, good, weights=weights)
+            for a, b in zip(got, want):
+                assert host(a).dtype == b.dtype and np.array_equal(host(a), b)
+
+
 def test_sqrt_is_numpys(gpu_device):
     d2 = np.array([2.0, 0.1, np.nextafter(1.0, 2.0), 1e-300, 1e300, 3.0, 1e-320, 0.0])
     n = len(d2) + 1

@@ -95,8 +95,74 @@ def test_checker_clusters_equal_the_subgraph_loop(name):
     assert sorted((min(a, b), max(a, b)) for a, b in q.edges()) == [tuple(e) for e in cluster_edges.tolist()]
 
 
+def test_checker_keeps_inf_where_a_sum_overflows():
+    """1e308 + 1e308 is +inf, which is not below the +inf of an unreached node: the node stays unreached, as in networkx
+    and scipy."""
+    rows = (np.full((4, 1), -1, dtype=np.int32), np.full((4, 1), np.inf))
+    extra = (np.array([[0, 1], [1, 2], [2, 3]], dtype=np.int32), np.full(3, 1e308))
+    got = oracle.distances(rows, 0, extra)
+    assert got.tolist() == [0.0, 1e308, np.inf, np.inf]
+    g = nx.Graph()
+    g.add_nodes_from(range(4))
+    g.add_weighted_edges_from((int(a), int(b), float(w)) for (a, b), w in zip(extra[0].tolist(), extra[1].tolist()))
+    _, dist = nx.dijkstra_predecessor_and_distance(g, 0)
+    assert [dist.get(v, np.inf) for v in range(4)] == got.tolist()
+    with np.errstate(over="ignore"):
+        m = sparse.csr_matrix((np.tile(extra[1], 2), (np.concatenate([extra[0][:, 0], extra[0][:, 1]]), np.concatenate([extra[0][:, 1], extra[0][:, 0]]))),
+                              shape=(4, 4))
+        assert np.array_equal(got, csgraph.dijkstra(m, directed=True, indices=0))
+    labels, count = oracle.components(rows, None, extra)
+    assert labels.tolist() == [0, 0, 0, 0] and count == 1  # joined all the same: the components read no weight
+
+
+def test_strip_self_arcs_of_the_scattered_cloud():
+    """The input of the empty-row tests of the GPU files, made here by brute force: the properties hold, the arcs are the
+    same without the self-arcs."""
+    rows = oracle.radius_rows(oracle.scattered_cloud(), oracle.SCATTER_RADIUS)
+    stripped = oracle.strip_self_arcs(rows)
+    assert oracle.arcs_of(stripped) == oracle.arcs_of(rows)
+    assert np.array_equal(oracle.distances(stripped, 0), [0.0] + [np.inf] * 1024)
+
+
+# ---- the bins of distance_to_root_clusters -------------------------------------------------------------------------
+def _fixed_distances(monkeypatch, d, want_weights=False):
+    """``proc3d`` with its three device calls replaced: the distances are ``d``, the keys the components get are kept."""
+    seen = {}
+    n = len(d)
+
+    def components(rows, key=None, **kw):
+        seen["bins"] = np.array(key)
+        return np.zeros(n, np.int32), 1
+
+    def quotient(rows, labels, n_labels, **kw):
+        return np.zeros(n, np.int32), np.array([n], np.int32), np.zeros((1, 3)), np.zeros((0, 2), np.int32), np.zeros(0) if kw.get("weights") else None
+
+    monkeypatch.setattr(proc3d, "graph_distances", lambda rows, root, **kw: np.array(d, dtype=np.float64))
+    monkeypatch.setattr(proc3d, "graph_components", components)
+    monkeypatch.setattr(proc3d, "graph_quotient", quotient)
+    return seen
+
+
+def test_bins_that_do_not_fit_int32_are_refused(monkeypatch):
+    seen = _fixed_distances(monkeypatch, [0.0, 1.0, 0.5])
+    pts = np.zeros((3, 3))
+    for bad in (1e-12, 5e-324, np.nextafter(2.0 ** -31, 0.0)):  # 1e12 bins; a quotient that overflows; 2^31 + 1 bins
+        with pytest.raises(ValueError, match="bin_size"):
+            proc3d.distance_to_root_clusters(pts, ROWS, 0, bad)
+        assert seen == {}
+    out = proc3d.distance_to_root_clusters(pts, ROWS, 0, 2.0 ** -31)  # 2^31 bins: the last one is 2^31 - 1
+    assert len(out) == 4 and seen["bins"].dtype == np.int32 and seen["bins"].tolist() == [0, 2 ** 31 - 1, 2 ** 30]
+    seen.clear()
+    _fixed_distances(monkeypatch, [0.0, np.inf, 1e300])
+    with pytest.raises(ValueError, match="bin_size"):
+        proc3d.distance_to_root_clusters(pts, ROWS, 0, 1e-10)  # 1e310 overflows
+    seen = _fixed_distances(monkeypatch, [np.inf, 0.0, np.inf])  # the root alone: one bin whatever its size
+    proc3d.distance_to_root_clusters(pts, ROWS, 1, 5e-324)
+    assert seen["bins"].tolist() == [-1, 0, -1]
+
+
 # ---- what the wrappers refuse and do without a device -------------------------------------------------------------
-ROWS = (np.array([[1, -1], [0, 2], [1, -1]], dtype=np.int32), np.array([[1.0, np.inf], [1.0, 4.0], [4.0, np.inf]]))
+ROWS =(np.array([[1, -1], [0, 2], [1, -1]], dtype=np.int32), np.array([[1.0, np.inf], [1.0, 4.0], [4.0, np.inf]]))
 
 
 def test_refusals_that_need_no_device():

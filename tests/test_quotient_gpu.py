@@ -7,6 +7,7 @@ import pytest
 
 from plant3dvision_amd import _native as nat
 from plant3dvision_amd import proc3d
+from tests import graph_oracle
 from tests import quotient_oracle as oracle
 
 pytestmark = pytest.mark.gpu
@@ -25,11 +26,11 @@ def host(a):
     return a.cpu().numpy() if hasattr(a, "cpu") else a
 
 
-def check(rows, labels, n_labels, points=None, key=None, extra=None):
+def check(rows, labels, n_labels, points=None, key=None, extra=None, checker=oracle.quotient):
     """One quotient, with and without weights, from arrays and from tensors, against the checker; returns the checker's."""
     labels = np.asarray(labels, dtype=np.int32)
     key = None if key is None else np.asarray(key, dtype=np.int32)
-    want = oracle.quotient(rows, labels, n_labels, points=points, key=key, extra=extra, weights=True)
+    want = checker(rows, labels, n_labels, points=points, key=key, extra=extra, weights=True)
     for form in (lambda x: x, on_device):
         for weights in (True, False):
             got = proc3d.graph_quotient(form(rows), form(labels), n_labels, points=form(points), key=form(key), extra=form(extra),
@@ -155,6 +156,114 @@ def test_hand_made_rows(gpu_device):
     rc = b.call("sc_graph_quotient", 4, 0, 1, nat.addr(rows5[0]), nat.addr(rows5[1]), 4, 1, 0, 0, 0, nat.addr(lab5), 4, 0, 0, 0, 0,
                 nat.addr(out_c), nat.addr(out_n4), 0, nat.addr(out_e), nat.addr(out_w), 3, nat.addr(nc), nat.addr(ne), 0)
     assert rc == nat.SC_OK and (nc[0], ne[0]) == (4, 4) and (out_e == -7).all() and (out_w == -7.0).all()
+
+
+# ---- rows without arcs ---------------------------------------------------------------------------------------------
+def test_csr_rows_without_self_arcs(gpu_device):
+    """Runs of empty CSR rows, at both ends too (tests/graph_oracle.py asserts them): the row of a place is found by a
+    binary search that has to step over them."""
+    pts = graph_oracle.scattered_cloud()
+    rows = graph_oracle.strip_self_arcs(proc3d.radius_points(pts, pts, graph_oracle.SCATTER_RADIUS))
+    key = np.random.default_rng(35).integers(-5, 5, size=1025).astype(np.int32)
+    labels, count = graph_oracle.components(rows)
+    assert 342 < count < 1025
+    for blocks in (0, 1):
+        nat.backend().call("sc_graph_set_blocks", blocks)
+        try:
+            _, counts, _, edges, _ = check(rows, labels, count, points=pts, key=key)
+            assert len(counts) == count and len(edges) == 0  # whole components: no arc leaves one
+            slab = np.clip(pts[:, 1] * 4, 0, 3).astype(np.int32)
+            slab[::7] = -1
+            _, _, _, edges, _ = check(rows, slab, 4, points=pts)
+            assert len(edges) == 3  # the slabs in a row, numbered by their smallest members
+        finally:
+            nat.backend().call("sc_graph_set_blocks", 0)
+
+
+NO_ARCS = {"csr": (np.zeros(66, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0)),
+           "fixed": (np.full((65, 3), -1, dtype=np.int32), np.full((65, 3), np.inf))}
+
+
+@pytest.mark.parametrize("form", sorted(NO_ARCS))
+def test_graphs_without_arcs(gpu_device, form):
+    """E == 0 (no index array at all, an empty CUDA tensor) and rows of unused places; then extra pairs as the only arcs."""
+    rows, own = NO_ARCS[form], np.arange(65, dtype=np.int32)
+    pts = np.random.default_rng(36).normal(size=(65, 3))
+    _, counts, centers, edges, _ = check(rows, own, 65, points=pts)
+    assert len(counts) == 65 and len(edges) == 0 and np.array_equal(centers, pts)
+    _, counts, _, edges, _ = check(rows, own, 65, key=-own)
+    assert len(counts) == 65 and len(edges) == 0
+    extra = (np.array([[64, 0], [3, 64], [0, 64]], dtype=np.int32), np.array([2.0, 0.25, 1.5]))
+    _, _, _, edges, edge_w = check(rows, own, 65, points=pts, extra=extra)
+    assert edges.tolist() == [[0, 64], [3, 64]] and edge_w.tolist() == [1.5, 0.25]
+    _, counts, _, edges, edge_w = check(rows, own // 2, 33, extra=extra)
+    assert len(counts) == 33 and edges.tolist() == [[0, 32], [1, 32]] and edge_w.tolist() == [1.5, 0.25]
+
+
+# ---- the sizes at which the sorts and scans change their algorithm -------------------------------------------------------
+def test_twenty_thousand_points(gpu_device):
+    """Scans over many tiles and sorts past one block (rocPRIM's merge sort); more cluster edges than the first ask has
+    room for, so the second ask runs at size.  The quotient is held against ``quotient_np``, which
+    tests/test_quotient_host.py holds against the loops; distances and components against the loops themselves."""
+    n = 20000
+    rng = np.random.default_rng(37)
+    pts = rng.uniform(0.0, 1.0, size=(n, 3))
+    rows = proc3d.knn_points(pts, pts, 6)
+    cell = np.floor(pts * 10.0).astype(np.int32)
+    slab = (cell[:, 0] + 10 * cell[:, 1] + 100 * cell[:, 2]).astype(np.int32)
+    slab[rng.random(n) < 0.1] = -1  # outside nodes
+    key = rng.integers(-5, 5, size=n).astype(np.int32)
+    want_d = graph_oracle.distances(rows, 11)
+    want_l, want_c = graph_oracle.components(rows, slab)
+    assert np.isfinite(want_d).sum() > n // 2
+    for form in (lambda x: x, on_device):
+        assert np.array_equal(host(proc3d.graph_distances(form(rows), 11)), want_d)
+        labels, count = proc3d.graph_components(form(rows), key=form(slab))
+        assert np.array_equal(host(labels), want_l) and count == want_c
+    _, counts, _, edges, _ = check(rows, want_l, want_c, points=pts, key=key, checker=oracle.quotient_np)
+    assert len(counts) == want_c > 1000 and len(edges) > proc3d.QUOTIENT_FIRST_EDGES
+    check(rows, want_l, want_c, checker=oracle.quotient_np)
+
+
+MERGE_SORT_LIMIT = 1024 * 1024
+
+
+def _strided_rows(n):
+    """Rows ``[n, 8]`` on a ring: node i points at i + 1, 2, 3, 5, 7, 11, 13 and at i - 1, so the last column gives the
+    pairs of the first again, from the other side and with another weight."""
+    rng = np.random.default_rng(n)
+    strides = np.array([1, 2, 3, 5, 7, 11, 13, n - 1], dtype=np.int64)
+    index = ((np.arange(n, dtype=np.int64)[:, None] + strides[None, :]) % n).astype(np.int32)
+    d2 = rng.uniform(0.5, 2.0, size=(n, 8))
+    assert np.array_equal(index[1:, 7], np.arange(n - 1)) and np.array_equal(index[:-1, 0], np.arange(1, n))
+    assert (d2[1:, 7] < d2[:-1, 0]).any() and (d2[1:, 7] > d2[:-1, 0]).any()  # the least weight comes from either side
+    return (index, d2), rng.normal(size=(n, 3)) * 1e3
+
+
+@pytest.mark.parametrize("labelling", ["own", "halves"])
+@pytest.mark.parametrize("n", [MERGE_SORT_LIMIT // 8, MERGE_SORT_LIMIT // 8 + 1])
+def test_across_the_merge_sort_limit(gpu_device, n, labelling):
+    """A = 8 n arcs at and just above T = ``rocprim::radix_sort_config<>::merge_sort_limit``, 1024 * 1024 in the installed
+    rocPRIM (``rocprim/device/device_radix_sort_config.hpp``, the default of ``MergeSortLimit``; hipCUB's ``DeviceRadixSort``
+    passes the default config).  ``radix_sort_impl`` in ``rocprim/device/device_radix_sort.hpp`` sorts a count up to one
+    block's items (256 * 4 at the most) in a single block, a count up to T with keys wider than 2 bytes by merge sort,
+    and a larger one by onesweep.  The unit sizes its one temporary buffer with A and then sorts X <= A crossing arcs:
+    with every node its own cluster X == A (merge sort at its limit for A == T, onesweep for A > T), with nodes in
+    pairs X <= T < A at the larger n: merge sort inside storage that onesweep was asked about.  The edge weights rest on
+    both sorts being stable in either algorithm."""
+    T = MERGE_SORT_LIMIT
+    rows, pts = _strided_rows(n)
+    A = 8 * n
+    labels = np.arange(n, dtype=np.int32) if labelling == "own" else (np.arange(n) // 2).astype(np.int32)
+    cluster, counts, _, edges, _ = check(rows, labels, n, points=pts, checker=oracle.quotient_np)
+    X = oracle.crossing_np(rows, cluster)
+    print(f"T = {T}, A = {A}, X = {X}, C = {len(counts)}, K = {len(edges)}")
+    assert (A == T) == (n == T // 8) and (A > T) == (n == T // 8 + 1)
+    if labelling == "own":
+        assert X == A and len(counts) == n and len(edges) == 7 * n
+    else:
+        assert len(counts) == (n + 1) // 2 and 4096 < X <= T and (n == T // 8 or T < A)
+    assert len(edges) > proc3d.QUOTIENT_FIRST_EDGES
 
 
 def test_a_label_too_large_and_the_call_after(gpu_device):

@@ -71,8 +71,89 @@ def test_weighted_tree_is_networkx_tree_and_the_unweighted_is_not(blob_case):
     assert sorted((min(a, b), max(a, b)) for a, b in nx.minimum_spanning_tree(u).edges()) != want
 
 
+# ---- the whole-array checker of the large GPU cases against the loops -------------------------------------------------
+def _np_cases():
+    """name -> the arguments of ``quotient``: every form of input tests/test_quotient_gpu.py feeds, at small sizes."""
+    rng = np.random.default_rng(61)
+    out = {}
+    for n in (1, 2, 65, 300):
+        pts = rng.uniform(0.0, 1.0, size=(n, 3))
+        slab = (pts[:, 0] * 3).astype(np.int32)
+        slab[rng.random(n) < 0.1] = -1  # outside nodes
+        key = rng.integers(-5, 5, size=n).astype(np.int32)  # keys with negatives
+        for name, rows in (("knn", oracle.d2_rows_knn(pts, 5)), ("csr", graph_oracle.radius_rows(pts, 1.2 * (1.0 / n) ** (1.0 / 3.0)))):
+            labels, count = graph_oracle.components(rows, slab)
+            out[f"{name} {n} slabs, key"] = dict(rows=rows, labels=labels, n_labels=count, points=pts, key=key)
+            out[f"{name} {n} slabs"] = dict(rows=rows, labels=labels, n_labels=count)
+    n, n_labels = 300, 40
+    pts = rng.uniform(0.0, 1.0, size=(n, 3))
+    names = rng.permutation(n_labels)[:25]  # 15 labels stay empty
+    labels = names[rng.integers(0, 25, size=n)].astype(np.int32)
+    labels[rng.random(n) < 0.1] = -1
+    labels[0] = -3
+    rows = oracle.d2_rows_knn(pts, 6)
+    out["labels in any order, empty ones"] = dict(rows=rows, labels=labels, n_labels=n_labels, points=pts)
+    out["labels in any order, wide keys"] = dict(rows=rows, labels=labels, n_labels=n_labels, points=pts,
+                                                 key=rng.integers(-2 ** 31, 2 ** 31, size=n).astype(np.int32))
+    out["every node its own cluster"] = dict(rows=rows, labels=np.arange(n, dtype=np.int32), n_labels=n, points=pts)
+    out["one cluster"] = dict(rows=rows, labels=np.zeros(n, dtype=np.int32), n_labels=3, points=pts)
+    out["nobody inside"] = dict(rows=rows, labels=np.full(n, -1, dtype=np.int32), n_labels=5, points=pts, key=np.zeros(n, np.int32))
+    out["no labels offered"] = dict(rows=rows, labels=np.full(n, -1, dtype=np.int32), n_labels=0)
+    inf, tiny = np.inf, 5e-324
+    index = np.array([[2, -1, 0], [2, -1, -1], [1, -1, -1], [1, 3, -1], [-1, -1, -1]], dtype=np.int32)  # the hand-made rows
+    d2 = np.array([[16.0, inf, 0.0], [9.0, inf, inf], [4.0, inf, inf], [25.0, 0.0, inf], [inf, inf, inf]])
+    extra = (np.array([[4, 0], [3, 4], [4, 3], [4, 4], [2, 1]], dtype=np.int32), np.array([0.5, 7.0, 6.0, 1.0, 1.5]))  # repeated pairs
+    out["hand-made rows"] = dict(rows=(index, d2), labels=np.array([0, 0, 1, 1, 2], dtype=np.int32), n_labels=3)
+    out["hand-made rows, extras"] = dict(rows=(index, d2), labels=np.array([0, 0, 1, 1, 2], dtype=np.int32), n_labels=3, extra=extra)
+    out["hand-made csr, extras, key"] = dict(rows=(np.array([0, 2, 3, 4, 6, 6], dtype=np.int64), np.array([2, 0, 2, 1, 1, 3], dtype=np.int32),
+                                                   np.array([16.0, 0.0, 9.0, 4.0, 25.0, 0.0])),
+                                             labels=np.array([0, 0, 1, 1, 2], dtype=np.int32), n_labels=3, key=np.array([5, 5, 0, 0, -1], np.int32),
+                                             extra=extra)
+    out["no arcs, csr"] = dict(rows=(np.zeros(66, np.int64), np.zeros(0, np.int32), np.zeros(0)), labels=np.arange(65, dtype=np.int32), n_labels=65,
+                               points=rng.normal(size=(65, 3)))
+    out["extras alone"] = dict(rows=(np.full((65, 2), -1, np.int32), np.full((65, 2), inf)), labels=np.arange(65, dtype=np.int32), n_labels=65,
+                               extra=(np.array([[0, 64], [64, 0], [7, 3]], dtype=np.int32), np.array([2.0, 1.0, 3.0])))
+    pts = np.array([[1e16, tiny, 1.0], [1.0, tiny, np.nan], [-1e16, -tiny, 2.0], [-0.0, tiny, 3.0],  # test_the_order_of_summation_shows
+                    [1.0, 1e-310, -0.0], [1e16, 2e-310, -0.0], [-1e16, -3e-310, -0.0], [-0.0, -0.0, 1e308], [-0.0, -0.0, 1e308]])
+    out["the order of summation shows"] = dict(rows=(np.array([[1], [2], [3], [4], [5], [6], [7], [8], [0]], dtype=np.int32), np.ones((9, 1))),
+                                               labels=np.array([2, 2, 2, 2, 5, 5, 5, 7, 7], dtype=np.int32), n_labels=8, points=pts)
+    # a few thousand arcs whose weights span 30 decades, many per cluster pair: every order of a sum gives other bits
+    n = 400
+    index = rng.integers(0, n, size=(n, 12)).astype(np.int32)
+    index[rng.random(index.shape) < 0.05] = -1
+    out["heavy-tailed weights"] = dict(rows=(index, 10.0 ** rng.uniform(-30.0, 30.0, size=index.shape)), labels=rng.integers(-1, 6, size=n).astype(np.int32),
+                                       n_labels=6, points=rng.normal(size=(n, 3)) * 10.0 ** rng.uniform(-8.0, 8.0, size=(n, 3)),
+                                       key=rng.integers(-3, 3, size=n).astype(np.int32),
+                                       extra=(rng.integers(0, n, size=(500, 2)).astype(np.int32), 10.0 ** rng.uniform(-30.0, 30.0, size=500)))
+    return out
+
+
+NP_CASES = _np_cases()
+
+
+@pytest.mark.parametrize("name", sorted(NP_CASES))
+def test_the_array_checker_equals_the_loops(name):
+    case = NP_CASES[name]
+    want = oracle.quotient(weights=True, **case)
+    got = oracle.quotient_np(weights=True, **case)
+    for what, a, b in zip(("cluster", "counts", "centers", "edges", "edge weights"), got, want):
+        assert (a is None and b is None) or oracle.same_bits(a, b), what
+    assert oracle.quotient_np(weights=False, **case)[4] is None
+    crossing = sum(1 for i, j, _ in oracle.arcs_of(case["rows"], case.get("extra"))[1] if want[0][i] >= 0 and want[0][j] >= 0 and want[0][i] != want[0][j])
+    assert oracle.crossing_np(case["rows"], want[0], case.get("extra")) == crossing
+    if name == "heavy-tailed weights":  # the order shows: the same terms summed from the other end give other bits
+        assert len(want[3]) == 15 and crossing > 3000
+        terms = oracle.node_edges(oracle.arcs_of(case["rows"], case["extra"])[1])
+        back = {}
+        for (i, j), w in sorted(terms.items(), reverse=True):
+            a, b = sorted((int(want[0][i]), int(want[0][j])))
+            if a >= 0 and a != b:
+                back[(a, b)] = back.get((a, b), 0.0) + w
+        assert any(back[tuple(e)] != w for e, w in zip(want[3].tolist(), want[4].tolist()))
+
+
 # ---- what the library refuses without a device (rule Q6) ------------------------------------------------------------
-INDEX = np.array([[1, -1], [0, 2], [1, -1]], dtype=np.int32)
+INDEX =np.array([[1, -1], [0, 2], [1, -1]], dtype=np.int32)
 D2 = np.array([[1.0, np.inf], [1.0, 4.0], [4.0, np.inf]])
 ROWS = (INDEX, D2)
 
@@ -210,6 +291,23 @@ def test_no_nodes_no_native_call(monkeypatch):
         got = proc3d.distance_to_root_clusters(np.zeros((0, 3)), rows, 0, 1.0, weights=True)
         assert len(got) == 5 and got[4].shape == (0,) and got[2].shape == (0, 2)
     assert stub.asked == []
+
+
+def test_weighted_clusters_refuse_bins_that_do_not_fit_int32(monkeypatch):
+    """The weighted form goes through the same bins: refused before any device call, accepted at 2^31 bins exactly."""
+    stub = _Stub(edges=0, clusters=1)
+    monkeypatch.setattr(nat, "_backend", stub)
+    monkeypatch.setattr(proc3d, "graph_distances", lambda rows, root, **kw: np.array([0.0, 1.0, 0.5]))
+    for bad in (1e-12, 5e-324, np.nextafter(2.0 ** -31, 0.0)):
+        with pytest.raises(ValueError, match="bin_size"):
+            proc3d.distance_to_root_clusters(np.zeros((3, 3)), ROWS, 0, bad, weights=True)
+    assert stub.asked == []
+    keys = []
+    components = proc3d.graph_components
+    monkeypatch.setattr(proc3d, "graph_components", lambda rows, key=None, **kw: (keys.append(np.array(key)), components(rows, key=key, **kw))[1])
+    out = proc3d.distance_to_root_clusters(np.zeros((3, 3)), ROWS, 0, 2.0 ** -31, weights=True)
+    assert len(out) == 5 and keys[0].dtype == np.int32 and keys[0].tolist() == [0, 2 ** 31 - 1, 2 ** 30]
+    assert [a[0] for a in stub.asked] == ["sc_graph_components", "sc_graph_quotient"]
 
 
 def test_the_call_is_in_the_headers_order(monkeypatch):
