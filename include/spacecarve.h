@@ -899,6 +899,45 @@ int sc_graph_quotient(int64_t N, const int64_t *offsets /* [N + 1] or NULL */, i
                       int32_t *cluster_out /* [N] */, int32_t *counts_out /* [L] */, double *centers_out /* [L, 3] or NULL */,
                       int32_t *edges_out /* [capacity, 2] */, double *edge_w_out /* [capacity] or NULL */, int64_t capacity,
                       int32_t *nclusters_out /* host */, int64_t *nedges_out /* host */, void *hip_stream);
+/*
+ * The edges that connect the labels of a cloud to the root's: what the reference's connect_graph
+ * (plant3dvision/proc3d.py:212-263) adds to a graph to make it connected, in an order-free form, on the GPU.  It is
+ * Prim's algorithm over the labels, started at the root's.  points double [N][3], labels int32 [N] (sc_graph_components'
+ * labels_out, or any other labelling), L the label bound.  on_device (one flag for every array and output), the slots,
+ * the error getter and the grid cap are sc_graph_distances'.
+ *   C1. the set and the rounds: R starts as the nodes whose label is labels[root].  While a node lies outside R, the
+ *       pair (i not in R, j in R) with the least key (d2, i, j), compared lexicographically, becomes edge number m,
+ *       stored as edges_out[m] = (i, j) with weights_out[m] = sqrt(d2), and every node with labels[i]'s label joins R.
+ *       d2 is rule N1's ((dx dx) + (dy dy)) + (dz dz) in binary64 without contraction, bitwise symmetric; the square
+ *       root is correctly rounded (G1).  *nedges_out is the number of labels that have members, minus one; places of
+ *       edges_out int32 [L - 1][2] and weights_out double [L - 1] behind that count stay untouched;
+ *   C2. labels need not be components: any labelling 0 .. L - 1 is taken as given, labels without members are allowed.
+ *       Nothing depends on how members are ordered inside a label: ties are decided by the key (d2, i, j), never by
+ *       the order in which anything arrives;
+ *   C3. refused (SC_ERR_INVALID): N outside 0 .. 2^31 - 1; L outside 1 .. N (for N > 0); a label outside 0 .. L - 1; a
+ *       root outside 0 .. N - 1; a non-finite coordinate (as N5 refuses them); NULL points, labels or nedges_out; NULL
+ *       edges_out or weights_out when L > 1; the device ordinal.  Host arrays are judged before the first device call;
+ *       device arrays by a first kernel that only judges and reads labels[0 .. N) and points[0 .. 3 N) and nothing
+ *       else, and the entry waits for its flag before any other launch.  N == 0 makes no device call and gives
+ *       *nedges_out = 0;
+ *   C4. bounds: every loop has a bound fixed before it starts; no wavefront waits on another, no kernel persists or
+ *       spins, there is no floating-point atomic; blocks meet only at kernel boundaries (and in the integer counters
+ *       that lay the points out in label order, where C2 makes the order irrelevant).  One launch per round: round 0
+ *       lets the root's label join, round r > 0 writes edge r - 1.  min(SC_GRAPH_ROUNDS_PER_WAIT, L) rounds are
+ *       enqueued, then the entry waits and reads C, the number of labels with members; the C - 1 - (rounds run) that
+ *       remain are enqueued in one go and waited for.  A round behind the last edge, or one that finds nobody outside,
+ *       returns at once.  Labels left outside after L - 1 edge rounds are SC_ERR_DEVICE.  Waits in all: the judge's
+ *       (device arrays only), one after the first rounds, one after the rest (device arrays: only when rounds remain;
+ *       host arrays with C > 1: always, the edges go home in front of it);
+ *   C5. work buffers, on the slots as above and under the same 1 GiB keep policy: per node 40 bytes (the coordinates
+ *       and the index in label order, the best (d2, j)); per label 12 bytes; 32 bytes per block of the grid; scan
+ *       storage; for host arrays copies of points and labels (28 bytes per node) and of the outputs (16 per label).
+ * Work is at most N^2 / 2 evaluations of d2 however many labels there are: a node is offered every other node once.
+ */
+int sc_graph_connect(int64_t N, const double *points /* [N, 3] */, const int32_t *labels /* [N] */, int64_t L, int64_t root,
+                     int on_device /* where every array and output lives */, int device,
+                     int32_t *edges_out /* [L - 1, 2] */, double *weights_out /* [L - 1] */, int64_t *nedges_out /* host */,
+                     void *hip_stream);
 const char *sc_graph_error(void);
 void sc_graph_release(void);
 void sc_graph_set_blocks(int blocks);

@@ -161,6 +161,7 @@ _SIGNATURES = {
     "sc_graph_components": ("i", ["q", "p", "i", "p", "q", "p", "q", "p", "i", "i", "p", "p", "p"]),
     "sc_graph_quotient": ("i", ["q", "p", "i", "p", "p", "q", "i", "p", "p", "q", "p", "q", "p", "p", "i", "i", "p", "p", "p", "p", "p", "q",
                                 "p", "p", "p"]),
+    "sc_graph_connect": ("i", ["q", "p", "p", "q", "q", "i", "i", "p", "p", "p", "p"]),
     "sc_graph_error": ("s", []),
     "sc_graph_release": ("v", []),
     "sc_graph_set_blocks": ("v", ["i"]),

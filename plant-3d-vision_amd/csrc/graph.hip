@@ -1,5 +1,6 @@
 // graph.hip -- distances to a root, connected components and the quotient under a labelling (DESIGN.md 21,
-// graph_quotient.inl) over the rows of sc_knn / sc_radius.
+// graph_quotient.inl) over the rows of sc_knn / sc_radius; the edges that connect the components (DESIGN.md 22,
+// graph_connect.inl).
 //
 // The two graph steps of the reference's XU skeleton (plant3dvision/proc3d.py:212-426): what
 // nx.dijkstra_predecessor_and_distance(g, root) returns as distances, and nx.connected_components, of whole graphs or
@@ -28,6 +29,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "sc_points.h"
 #include "sc_unionfind.h"
 #include "sc_unit.h"
 
@@ -523,3 +525,4 @@ void sc_graph_release(void) { release_slots(g_slots); }
 }  // extern "C"
 
 #include "graph_quotient.inl"  // sc_graph_quotient
+#include "graph_connect.inl"   // sc_graph_connect

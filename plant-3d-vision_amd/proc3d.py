@@ -740,40 +740,62 @@ def graph_components(rows, key=None, n=None, extra=None, device=0):
     return labels, int(count[0])
 
 
-def connect_edges(points, labels, root_index, device=0):
+def connect_edges(points, labels, root_index, device=0, n_labels=None):
     """The edges the reference's ``connect_graph`` (``proc3d.py:212-263``) adds to make a graph connected, in an
-    order-free form.  ``labels``: the component of every point (:func:`graph_components`).  While a point lies outside
-    the root's component ``R``: among all pairs ``(i not in R, j in R)`` the one with the least key ``(d2, i, j)`` -- found
-    with :func:`nearest_points` ``(outside, inside)`` on the GPU -- becomes an edge of weight ``sqrt(d2)``, and the whole
-    component of ``i`` joins ``R`` (a host relabel).
+    order-free form, on the GPU (``sc_graph_connect``, ``csrc/graph_connect.inl``).  ``labels``: the
+    component of every point (:func:`graph_components`), or any other labelling.  While a point lies outside the root's
+    label ``R``: among all pairs ``(i not in R, j in R)`` the one with the least key ``(d2, i, j)`` becomes an edge of
+    weight ``sqrt(d2)``, and every point with ``i``'s label joins ``R`` (rules C1, C2 of ``include/spacecarve.h``; ``d2``
+    is rule N1's).
 
-    Returns ``(edges int32 [M, 2], weights float64 [M])``, ``M = components - 1``, each edge as ``(i, j)``: feed them to
-    :func:`graph_distances` / :func:`graph_components` as ``extra``.
+    points, labels : an array-like ``[n, 3]`` (or a :class:`PointCloud`) and any integers ``[n]`` -- they are compacted to
+        ``0 .. L - 1`` on the host before the call -- -> NumPy results; or a contiguous float64 CUDA tensor ``[n, 3]`` and
+        a contiguous int32 CUDA tensor ``[n]`` of labels ``0 .. n_labels - 1`` on one device, read in place on torch's
+        current stream -> CUDA tensors on that device.  Mixed kinds raise ``ValueError``.
+    n_labels : the label bound of tensor labels, :func:`graph_components`' count; ``None`` asks the device for
+        ``labels.max() + 1``, which costs one wait.  With arrays it is ignored (the compaction gives it).
+
+    Returns ``(edges int32 [M, 2], weights float64 [M])``, ``M = (labels with members) - 1``, each edge as ``(i, j)``:
+    feed them to :func:`graph_distances` / :func:`graph_components` / :func:`graph_quotient` as ``extra``.  No points, one
+    label (``n_labels <= 1``, or host labels that are all the root's): empty results, no native call.  A label outside
+    ``0 .. n_labels - 1`` and a non-finite coordinate raise ``ValueError`` (rule C3).  There is no CPU fallback.
 
     Deviation: the reference stores ``nnorm``, the norm of the LAST point its loop visited, as the new edge's weight where
     it means ``minnorm`` (``proc3d.py:262-263``); ours is the minimum, the length of the edge."""
-    from . import _operands as ops
+    from . import _native as nat, _operands as ops
 
     p = ops.points(points, "points")
-    if p.on_device:
-        raise ValueError("connect_edges takes host points (the components are relabelled on the host)")
-    lab = np.asarray(labels.cpu() if ops.is_tensor(labels) else labels).astype(np.int64).reshape(-1)
-    if lab.shape[0] != p.n:
+    if ops.is_tensor(labels) != bool(p.on_device):
+        raise ValueError("points and labels must be both arrays (or a cloud) or both CUDA tensors")
+    lab = ops.ids(labels, "labels").data if p.on_device else np.asarray(labels).reshape(-1)
+    if len(lab) != p.n:
         raise ValueError("one label per point")
+    if p.on_device and lab.device != p.points.device:
+        raise ValueError("points and labels must be on one device")
     root = int(root_index)
     if p.n and not 0 <= root < p.n:
         raise ValueError(f"root_index must be 0 .. {p.n - 1}")
-    edges, weights = [], []
-    inside = lab == lab[root] if p.n else np.zeros(0, dtype=bool)
-    while not inside.all():
-        out_ids, in_ids = np.flatnonzero(~inside), np.flatnonzero(inside)
-        index, d2 = nearest_points(p.points[out_ids], p.points[in_ids], device=device)
-        a = int(np.argmin(d2))  # the first least d2: the smallest i; nearest_points gave it its smallest j (rule N2)
-        i, j = int(out_ids[a]), int(in_ids[index[a]])
-        edges.append((i, j))
-        weights.append(np.sqrt(d2[a]))
-        inside |= lab == lab[i]
-    return np.array(edges, dtype=np.int32).reshape(-1, 2), np.array(weights, dtype=np.float64)
+    if p.on_device:
+        import torch
+
+        def empty(shape, dtype):
+            return torch.empty(shape, dtype=getattr(torch, dtype), device=p.points.device)
+        L = 0 if not p.n else int(n_labels) if n_labels is not None else int(lab.max()) + 1
+    else:
+        def empty(shape, dtype):
+            return np.empty(shape, dtype=dtype)
+        values, lab = np.unique(lab, return_inverse=True)  # any integers -> 0 .. L - 1
+        lab = np.ascontiguousarray(lab.reshape(-1), dtype=np.int32)
+        L = len(values)
+    if p.n == 0 or L <= 1:
+        return empty((0, 2), "int32"), empty((0,), "float64")
+    dev, stream = ops.tensor_place(p.points) if p.on_device else (int(device), 0)
+    edges, weights = empty((L - 1, 2), "int32"), empty((L - 1,), "float64")
+    count = np.zeros(1, dtype=np.int64)
+    _graph_call("sc_graph_connect", p.n, p.ptr, ops.ptr_of(lab), L, root, p.on_device, int(dev), ops.ptr_of(edges), ops.ptr_of(weights), nat.addr(count),
+                int(stream))
+    m = int(count[0])
+    return edges[:m], weights[:m]
 
 
 def _host(a):
@@ -915,6 +937,10 @@ def skeleton_from_distance_to_root_clusters(pcd, root_index, binsize, k, connect
     nodes clustered by distance to ``root_index`` (:func:`distance_to_root_clusters`), and the minimum spanning tree of
     the cluster graph.
 
+    pcd : an array-like ``[n, 3]`` or a :class:`PointCloud`, uploaded once to ``device``; or a contiguous float64 CUDA
+        tensor ``[n, 3]``, taken in place (``device`` is then the tensor's).  Every step runs device to device on torch's
+        current stream; what comes home is ``cluster [n]``, the centres, the cluster edges and their weights.
+
     Returns ``(tree, cluster_values)``: ``tree`` is ``nx.minimum_spanning_tree`` of the ``networkx.Graph`` whose nodes
     ``0..C-1`` carry ``center`` and whose edges are the cluster edges in sorted order; ``cluster_values`` is the dict
     ``{node: cluster}``, unreached nodes absent as in the reference.  Raises ``ImportError`` without networkx.
@@ -935,15 +961,18 @@ def skeleton_from_distance_to_root_clusters(pcd, root_index, binsize, k, connect
 
     pts = ops.points(pcd, "points")
     if pts.on_device:
-        raise ValueError("skeleton_from_distance_to_root_clusters takes host points")
-    rows = knn_points(pts.points, pts.points, int(k), device=device)
+        xyz = pts.points
+    else:  # the one upload: every step below reads and writes device memory
+        import torch
+        xyz = torch.from_numpy(pts.points).to(f"cuda:{int(device)}")
+    rows = knn_points(xyz, xyz, int(k))
     extra = None
     if connect_all_points and pts.n:
-        labels, count = graph_components(rows, device=device)
+        labels, count = graph_components(rows)
         if count > 1:
-            extra = connect_edges(pts.points, labels, root_index, device=device)
-    got = distance_to_root_clusters(pts.points, rows, root_index, binsize, extra=extra, device=device, weights=bool(weighted))
-    cluster, centers, cluster_edges, edge_w = got[0], got[1], got[2], got[4] if weighted else None
+            extra = connect_edges(xyz, labels, root_index, n_labels=count)
+    got = distance_to_root_clusters(xyz, rows, root_index, binsize, extra=extra, weights=bool(weighted))
+    cluster, centers, cluster_edges, edge_w = _host(got[0]), got[1], got[2], got[4] if weighted else None
     g = nx.Graph()
     for c in range(len(centers)):
         g.add_node(c, center=centers[c])
